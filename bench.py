@@ -16,6 +16,10 @@ Inputs are synthetic geodesic arrays resident in HBM before the time
 "all-active" variant (rmin=0, rmax=inf, z_width=inf, nothing pre-injection) is used so that every
 ray-sample goes through the full MLP (evaluated points == total points).
 
+`--dump-outputs DIR` writes what the last timed step returned to its caller (bench.dump_outputs) -- the loss vector, the
+images, the parameters and the Adam moments after the step -- as DIR/<name>.npy; the inputs are seeded, so two builds run with
+the same arguments can be compared output for output.  `ms_per_step` is the wall time of the K timed steps / K.
+
 Prints ONE JSON line on rank 0.  `roofline` refers to the MLP kernel with the largest share of the step.  SURVEY 8(d) puts the
 fused MLP, forward and backward, on the MFMA roofline: `roofline.bound` is "mfma", `achieved` = ALGORITHMIC flops per launch
 (SURVEY 8(d)'s per-point figure x the points one launch evaluates) / that kernel's average launch duration, `frac` =
@@ -110,7 +114,41 @@ def parse():
     ap.add_argument('--other-configs', dest='other_configs', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--cpu-rays', type=int, default=2048, help='rays of one frame in the CPU-baseline sample')
     ap.add_argument('--cpu-seconds', type=float, default=25.0, help='time budget of the CPU-baseline thread sweep')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (loss, images, parameters, Adam moments) as '
+                         'DIR/<name>.npy (rank 0\'s share; at most 64 MB, see dump_outputs)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """Write each of `arrays` ({name: tensor or array}) as out_dir/<name>.npy: float64 where it is float64, float32 otherwise.
+    If together they exceed `cap` bytes, each is cut to its share of the cap: a sample of its flattened elements at indices drawn
+    (sorted) by a generator with a fixed seed, so that runs with the same arguments write the same elements.  Returns {name: shape}."""
+    host = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach()
+            a = (a if a.dtype == torch.float64 else a.float()).cpu().numpy()
+        a = np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, a in host.items():
+        if total > cap:
+            keep = max(1, a.size * cap // total)
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        shapes[name] = a.shape
+    return shapes
 
 
 def spawn_ranks(args):
@@ -120,10 +158,11 @@ def spawn_ranks(args):
     import socket
     n = args.gpus
     one_dev = os.environ.get('BHNERF_BENCH_ONE_DEVICE') == '1'
-    ndev = torch.cuda.device_count()
-    if ndev < n and not one_dev:
-        raise SystemExit('bench.py --gpus %d: only %d device(s) visible (BHNERF_BENCH_ONE_DEVICE=1 runs all ranks on '
-                         'cuda:0 over gloo, a testing aid)' % (n, ndev))
+    if not one_dev:             # (all ranks on cuda:0: no device count needed, and this process stays off the GPU)
+        ndev = torch.cuda.device_count()
+        if ndev < n:
+            raise SystemExit('bench.py --gpus %d: only %d device(s) visible (BHNERF_BENCH_ONE_DEVICE=1 runs all ranks on '
+                             'cuda:0 over gloo, a testing aid)' % (n, ndev))
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
@@ -669,8 +708,10 @@ def main():
     assert batch <= nt, 'frames per step exceed the movie length'
 
     def run_steps(o, n):
+        images = None
         for _ in range(n):
-            o.loss, o.state, _ = train_step(o.state, rt_args, indices=train_step.args[0].sample(batch))
+            o.loss, o.state, images = train_step(o.state, rt_args, indices=train_step.args[0].sample(batch))
+        return images
 
     def barrier():
         if world > 1:
@@ -690,11 +731,14 @@ def main():
     if timer:
         timer.reset()
     t0 = time.perf_counter()
-    run_steps(opt, args.steps)
+    images_last = run_steps(opt, args.steps)
     opt.state.finish_allreduce()        # (--overlap-allreduce: the last gradient's all-reduce + Adam belong to the K steps)
     barrier()
     elapsed = time.perf_counter() - t0
     eng.step_timer, eng.clock_probe = None, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': opt.loss, 'images': images_last, 'params': opt.state.flat,
+                                         'adam_m': opt.state.m, 'adam_v': opt.state.v})
     kern_loop = timer.kernel_ms(args.steps) if timer else None
     clocks_loop = clk_main.cpu().numpy().copy()
     if world > 1:

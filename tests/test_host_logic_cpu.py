@@ -263,3 +263,29 @@ def test_bench_roofline_bookkeeping():
     stamps = np.zeros(16, dtype=np.int64)
     stamps[8:12] = [1000, 50, 1000 + 1_850_000, 50 + 100_000]                              # slot 2: 1.85e6 core cycles in 1 ms
     assert bench.clock_mhz(stamps, bench.CLK_SLOT[bench.CHAIN_NAME]) == 1850.0 and bench.clock_mhz(stamps, 0) is None
+
+
+def test_bench_dump_outputs_dtypes_cap_and_fixed_sample(tmp_path):
+    """bench.dump_outputs: float64 stays float64, everything else (bf16 included) is written as float32; above the cap each
+    array is cut to its share by a seeded sample, the same elements on every call."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    small = {'loss': torch.tensor([1.5, 2.5], dtype=torch.float64), 'images': torch.arange(12, dtype=torch.bfloat16).reshape(1, 3, 4),
+             'params': np.arange(5, dtype=np.float32)}
+    shapes = bench.dump_outputs(str(tmp_path / 'a'), small)
+    assert shapes == {'loss': (2,), 'images': (1, 3, 4), 'params': (5,)}
+    loss, images = np.load(tmp_path / 'a' / 'loss.npy'), np.load(tmp_path / 'a' / 'images.npy')
+    assert loss.dtype == np.float64 and np.array_equal(loss, [1.5, 2.5])
+    assert images.dtype == np.float32 and np.array_equal(images, np.arange(12, dtype=np.float32).reshape(1, 3, 4))
+    big = {'x': np.random.default_rng(1).standard_normal(3000), 'y': np.random.default_rng(2).standard_normal(1000).astype(np.float32)}
+    cap = 8000
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), big, cap=cap)
+    files = sorted(os.listdir(tmp_path / 'b'))
+    assert files == ['x.npy', 'y.npy']
+    assert sum(np.load(tmp_path / 'b' / f).nbytes for f in files) <= cap
+    for f in files:
+        a, b = np.load(tmp_path / 'b' / f), np.load(tmp_path / 'c' / f)
+        assert a.size < big[f[0]].size and np.array_equal(a, b) and np.isin(a, big[f[0]]).all()

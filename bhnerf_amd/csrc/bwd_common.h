@@ -38,8 +38,8 @@ struct TapeLayout {
     // h = relu(a) = relu'(a) a and a = K^T h_{depth-1} + b give  dW_out[f] = sum_k K[k][f] G[k][f] + b[f] g[f]  with G, g the
     // (un-folded) weight and bias gradients of layer depth-1 (fused_bwd128.hip: reduce128_kernel).
     int drop_hd;
-    // generic bf16 path (round 5): the dW job of layer depth-1 reads the relu-bit words instead of the h_depth tiles and makes the
-    // output layer's row at its flush (dw_body2 LBITS); with drop_hd the forward does not store those tiles either
+    // generic bf16 path (round 5, never set: tape_layout): the dW job of layer depth-1 reads the relu-bit words instead of the h_depth
+    // tiles and makes the output layer's row at its flush (dw_body2 LBITS)
     int lbits;
     long long maskd_off, scratch_off;          // scratch: [5][128] f32 partial sums of that product (per input tile)
 };
@@ -51,10 +51,6 @@ struct BwdArgs {
     // dW jobs: job j = layer j (0..depth), workgroups [wg_begin[j], wg_begin[j+1])
     int wg_begin[BHN_MAX_LAYERS + 2];
     int accumulate;                            // 1: add to what the slabs already hold
-    int debug;                                 // measurement aid: 1 skip MFMA work, 2 skip tape loads
-    long long *ts_buf;                         // measurement aid: ring-step time stamps (debug bit 9)
-    long long wrap;                            // measurement aid (debug build): tape tile addresses wrap after this many groups
-    int policy;                                // measurement aid (debug build): 0 nt, 1 plain, 2 sc1 tape stores / loads
     float *dparams;
     long long kernel_off[BHN_MAX_LAYERS + 1], bias_off[BHN_MAX_LAYERS + 1];
     int in_dim[BHN_MAX_LAYERS + 1];

@@ -17,48 +17,13 @@
 #include "fused_common.h"
 #include "bwd_common.h"
 
-#ifndef BHN_CHAIN_STAMPS
-#define BHN_CHAIN_STAMPS 0      // 1: ring-step time stamps in the chain kernels (tools/dbg_chain_steps.py needs this build)
-#endif
-#ifndef BHN_JOBLB_W
-#define BHN_JOBLB_W 6           // LBITS: weight of that job's compute (mask expansion, the output row at the flush) in B tiles at width 256
-#endif
-#ifndef BHN_DROP_HD
-#define BHN_DROP_HD 0           // with LBITS, generic tape path: the training forward does not store the h_depth tiles (TapeLayout::drop_hd).
-#endif                          // OFF, as is LBITS: 9 GB less tape traffic per step at 4x256 (48.4 -> 39.5) and NOT faster -- the dW kernel does not get
-                                // faster with 18 % fewer bytes (it is issue-bound per group, not HBM-bound) and every variant of the forward's
-                                // change costs its ring steps 3 % (profiles/r5_ab_drop_hd_width256.txt).  The fused 4x128 path has it on (bwd128).
-#ifndef BHN_LBITS
-#define BHN_LBITS 0             // 1: the dW job of layer depth-1 works from the relu bits (dw_body2 LBITS) instead of the h_depth tiles (see BHN_DROP_HD)
-#endif
-#ifndef BHN_JOB1_W
-#define BHN_JOB1_W 13          // weight of the layer-1 dW job in B tiles at width 256 (measured optimum; scaled with the width)
-#endif
-#ifndef BHN_JOBL_W
-#define BHN_JOBL_W 7            // extra weight (in tiles at width 256, scaled with the width) of the layer depth-1 dW job when it rebuilds gA_{depth-1} and carries the output row
-                                // (round 5, re-swept without the layer-0 job, profiles/r5_dw_job_weights.txt: 6-7 beat 8 by 1.2 % of the dW kernel)
-#endif
-// Run-time measurement switches exist only in the debug build (make debug); the release kernels see the constant 0
-#ifdef BHN_DEBUG
-#define BHN_DBG(x) (x)
-#else
-#define BHN_DBG(x) 0
-#endif
-#ifndef BHN_GA0_CHAIN
-#define BHN_GA0_CHAIN 1          // bf16, width 256, depth >= 3: the delta chain accumulates dW_0 itself (TapeLayout::ga0_chain); 0: A/B builds
-#endif
-#ifndef BHN_GA0C_ABL
-#define BHN_GA0C_ABL 0           // measurement builds (dW_0 wrong): 1 no consumer (no extra MFMAs / staged-tile reads), 2 no staging writes, 4 no encoded-input DMA
-#endif
-#ifndef BHN_GA0C_DIST
-#define BHN_GA0C_DIST 4          // weight chunks in flight in that delta chain (its LDS also holds 64 KB of staging images)
-#endif
-#ifndef BHN_GA0C_SWZ
-#define BHN_GA0C_SWZ 1           // staging images of the gA_0 tiles with swizzled rows (chain_kernel: stage_off); 0: A/B builds
-#endif
-#ifndef BHN_TAPED_DIST
-#define BHN_TAPED_DIST 7         // weight chunks in flight in the training-forward / delta-chain kernels (bf16; 4 measured 2 % slower)
-#endif
+// dW job weights (bwd_run), in B tiles at width 256, scaled with the width
+static constexpr int JOB1_W = 13;        // the layer-1 job (measured optimum)
+static constexpr int JOBL_W = 7;         // extra weight of the layer depth-1 job when it rebuilds gA_{depth-1} and carries the output row
+                                         // (round 5, re-swept without the layer-0 job, profiles/r5_dw_job_weights.txt: 6-7 beat 8 by 1.2 % of the dW kernel)
+static constexpr int GA0C_DIST = 4;      // weight chunks in flight in the delta chain that accumulates dW_0 (its LDS also holds 64 KB of staging images)
+static constexpr int TAPED_DIST = 7;     // weight chunks in flight in the training-forward / delta-chain kernels (bf16; 4 measured 2 % slower)
+static constexpr int T8_NBUF = 4;        // ring depth of the 8-bit tape's dW jobs (8 = the bf16 jobs' bytes in flight: measured no faster, the jobs are VALU-bound)
 
 template <int W, class Pol>
 struct BwdGeom {
@@ -85,7 +50,7 @@ struct BwdGeom {
     static constexpr int GROUP_BYTES = Pol::TAPE8 ? MT * TAPE_TILE + (MT + 1) * TILE_BYTES : (2 * MT + 1) * TILE_BYTES;
     static constexpr int GROUP_BYTES_LAST2 = GROUP_BYTES + 1024;               // + the KiB that starts with the f32 dout (dw_body2 LAST)
     // chain kernels: prefetch distance of the LDS-DMA weight ring (RING_DIST_TAPED+1 buffers of one chunk)
-    static constexpr int RING_DIST_TAPED = (Pol::ELEM_BYTES == 2) ? BHN_TAPED_DIST : 3;
+    static constexpr int RING_DIST_TAPED = (Pol::ELEM_BYTES == 2) ? TAPED_DIST : 3;
     // dW kernel: LDS-DMA ring of NBUF groups (counted vmcnt, raw s_barrier); f32: 2 buffers
     static constexpr int NBUF = (Pol::ELEM_BYTES == 2) ? ((160 * 1024) / GROUP_BYTES >= 4 ? 4 : 3) : 2;
     static constexpr int NPIECE = GROUP_BYTES / 1024;               // 1 KiB = one wave-wide 16-B DMA
@@ -100,6 +65,9 @@ struct BwdGeom {
 // its FEATURE on the lane and 16 points in the registers -- the operand layout of the dW GEMM (K = points).  Exact
 // (one product by 1.0 per output), no LDS traffic, no waits; the points of a tile end up in the fixed order
 // p = (r&3) + 8(r>>2) + 4(lane>>5), the same for every tile, which a sum over points does not care about.
+// what becomes of a finished tile (TapePost::flags)
+enum { EMIT_NO_STORE = 1,        // (never set: see TapeEmit::store_native)
+       EMIT_OFF = 2 };           // the tile does not go to the tape (relu bits only, or not recorded)
 template <class Pol>
 struct TapeEmit {
     // identity k-steps, one fragment pair in LDS (read when needed: holding them costs 8 registers the 4x256 bf16
@@ -140,7 +108,7 @@ struct TapeEmit {
         t = Pol::mma(f1, id[1], t);
         return t;
     }
-    static DEVI void store(char *dst, const f32x16 &t, int dbg) {
+    static DEVI void store(char *dst, const f32x16 &t) {
         const int lane = threadIdx.x & 63;
         typename Pol::frag o[2];
 #pragma unroll
@@ -149,10 +117,7 @@ struct TapeEmit {
             for (int j = 0; j < 8; ++j) Pol::set(o[s], j, t[8 * s + j]);
         if constexpr (Pol::ELEM_BYTES == 2) {
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                if (!(dbg & 1)) __builtin_nontemporal_store(o[s], reinterpret_cast<typename Pol::frag *>(dst + s * 1024 + lane * 16));
-                else asm volatile("" ::"v"(o[s]));
-            }
+            for (int s = 0; s < 2; ++s) __builtin_nontemporal_store(o[s], reinterpret_cast<typename Pol::frag *>(dst + s * 1024 + lane * 16));
         } else {
 #pragma unroll
             for (int s = 0; s < 2; ++s)
@@ -176,30 +141,21 @@ struct TapeEmit {
         const int lane = threadIdx.x & 63, pt = lane & 31, h = lane >> 5;
         return 16 * (pt & 3) + 128 * s + 64 * h + 256 * (pt >> 2);
     }
-    static DEVI void store_native(char *dst, const typename Pol::frag &f0, const typename Pol::frag &f1, int dbg) {
-        if (BHN_DBG(dbg & 12)) {          // measurement: cache policy of the tape stores (4: plain, 8: sc1)
-            typename Pol::frag *p0 = reinterpret_cast<typename Pol::frag *>(dst + native_off(0));
-            typename Pol::frag *p1 = reinterpret_cast<typename Pol::frag *>(dst + native_off(1));
-            if (dbg & 4) { *p0 = f0; *p1 = f1; }
-            else {
-                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p0), "v"(f0) : "memory");
-                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p1), "v"(f1) : "memory");
-            }
-        } else if (!(dbg & 1)) {
+    // `flags`: the pending tile's EMIT_* flags (TapePost).  EMIT_NO_STORE is never set; the test stays because hipcc allocates
+    // the delta chains differently without it (the 4x256 one measured 5 % slower).
+    static DEVI void store_native(char *dst, const typename Pol::frag &f0, const typename Pol::frag &f1, int flags = 0) {
+        if (!(flags & EMIT_NO_STORE)) {
             __builtin_nontemporal_store(f0, reinterpret_cast<typename Pol::frag *>(dst + native_off(0)));
             __builtin_nontemporal_store(f1, reinterpret_cast<typename Pol::frag *>(dst + native_off(1)));
-        } else {
-            asm volatile("" ::"v"(f0), "v"(f1));
-        }
+        } else asm volatile("" ::"v"(f0), "v"(f1));
     }
-    DEVI void emit(char *dst, const typename Pol::frag &f0, const typename Pol::frag &f1, int dbg) const {
-        if (dbg & 2) return;
+    DEVI void emit(char *dst, const typename Pol::frag &f0, const typename Pol::frag &f1) const {
         if constexpr (Pol::ELEM_BYTES == 2) {
-            store_native(dst, f0, f1, dbg);
+            store_native(dst, f0, f1);
         } else {
             typename Pol::frag id[2];
             load_id(id);
-            store(dst, transpose(f0, f1, id), dbg);
+            store(dst, transpose(f0, f1, id));
         }
     }
 };
@@ -299,11 +255,9 @@ struct Ga0Consumer {
     const char *ga, *enc;        // staged gA_0 tiles / encoded-input tiles of the eight source waves (2 KiB apart)
     int trl;                     // tr_lane_off(): the encoded-input tiles (DMA'd from the tape: its slot layout)
     int trl_ga;                  // the same for the staged gA_0 tiles, whose odd 256-byte rows swap their 64-byte lane halves (ga0_stage_swz)
-#ifndef BHN_GA0C_PF
-#define BHN_GA0C_PF 2            // fragment pairs in flight in the consumer block (8 registers each); round 6 re-sweep: 2 beats 3 and 4 by 1 % of the kernel (profiles/r6_tunable_sweep.txt)
-#endif
+    // fragment pairs in flight in the consumer block (8 registers each); round 6 re-sweep: 2 beats 3 and 4 by 1 % of the kernel (profiles/r6_tunable_sweep.txt)
+    static constexpr int PF = 2;
     DEVI void run(f32x16 &acc, int npairs) const {
-        constexpr int PF = BHN_GA0C_PF;
         bf16x8 a[PF], b[PF];
 #pragma unroll
         for (int p = 0; p < PF - 1; ++p) {
@@ -336,7 +290,7 @@ struct TapePost {
     unsigned *mword, *stash;
     unsigned &macc;
     bool hi, last;          // odd tile of the word (8-bit tape: of the tile pair) / last tile of the layer (stores a half-filled word when MT is odd)
-    int edbg;
+    int flags;              // EMIT_*
     const TapeEmit<Pol> &em;
     typename Pol::frag id[2];
     f32x16 tr;
@@ -346,9 +300,9 @@ struct TapePost {
     unsigned &t8_amax;       // (two bf16 magnitudes: the packed maximum over the dwords of the recorded tiles; an f32 maximum over
                              //  the accumulators in elems() made hipcc spill 70 registers in the delta chain)
     DEVI TapePost(const f32x16 &p, typename Pol::frag &a, typename Pol::frag &b, unsigned mask_in, const TapeEmit<Pol> &em_, char *dst_,
-                  unsigned *mword_, unsigned *stash_, unsigned &macc_, bool hi_, bool last_, int edbg_, float t8_sc_, unsigned &t8_amax_)
+                  unsigned *mword_, unsigned *stash_, unsigned &macc_, bool hi_, bool last_, int flags_, float t8_sc_, unsigned &t8_amax_)
         : pend(p), d0(a), d1(b), mask(RELU ? 0u : Pol::mask_spread(mask_in)), dst(dst_), mword(mword_), stash(stash_),
-          macc(macc_), hi(hi_), last(last_), edbg(edbg_), em(em_), t8_sc(t8_sc_), t8_amax(t8_amax_) {}
+          macc(macc_), hi(hi_), last(last_), flags(flags_), em(em_), t8_sc(t8_sc_), t8_amax(t8_amax_) {}
     template <int R0, int N>
     DEVI void elems() {
         if constexpr (RELU) pack_elems<Pol, R0, N>(pend, d0, d1, mask);
@@ -407,7 +361,7 @@ struct TapePost {
             }
         }
         if constexpr (Pol::ELEM_BYTES != 2) {
-            if (!(edbg & 2)) tr = TapeEmit<Pol>::transpose(d0, d1, id);
+            if (!(flags & EMIT_OFF)) tr = TapeEmit<Pol>::transpose(d0, d1, id);
         }
     }
     DEVI void store_tile() {
@@ -421,15 +375,10 @@ struct TapePost {
                 return;
             }
         }
-        if (edbg & 2) return;
-        if (BHN_DROP_HD != 0 && (edbg & 16)) {                // (TapeLayout::drop_hd on a ring kernel: the emission's two stores, four bytes each, `dst` = a line of the tape's scratch area)
-            __builtin_nontemporal_store(0u, reinterpret_cast<unsigned *>(dst));
-            __builtin_nontemporal_store(0u, reinterpret_cast<unsigned *>(dst) + 1);
-            return;
-        }
+        if (flags & EMIT_OFF) return;
         if constexpr (Pol::TAPE8) store_tile8();
-        else if constexpr (Pol::ELEM_BYTES == 2) TapeEmit<Pol>::store_native(dst, d0, d1, edbg);
-        else TapeEmit<Pol>::store(dst, tr, edbg);
+        else if constexpr (Pol::ELEM_BYTES == 2) TapeEmit<Pol>::store_native(dst, d0, d1, flags);
+        else TapeEmit<Pol>::store(dst, tr);
     }
     unsigned w = 0;                             // the pair rounded in the previous k-step (pack_pipe)
     DEVI void at(int t) {
@@ -444,22 +393,19 @@ struct TapePost {
             if (t == 6) elems<12, 2>();
             if (t == 7) elems<14, 2>();
         }
-        if (Pol::ELEM_BYTES != 2 && t == 6 && !(edbg & 2)) em.load_id(id);
+        if (Pol::ELEM_BYTES != 2 && t == 6 && !(flags & EMIT_OFF)) em.load_id(id);
         if (t == 10) bits_and_transpose();
         if (t == 12) store_tile();
     }
     DEVI void all() {
         elems<0, 16>();
-        if (Pol::ELEM_BYTES != 2 && !(edbg & 2)) em.load_id(id);
+        if (Pol::ELEM_BYTES != 2 && !(flags & EMIT_OFF)) em.load_id(id);
         bits_and_transpose();
         store_tile();
     }
     DEVI void finish() {}
 };
 
-#ifdef BHN_DEBUG
-void *bhn_debug_buffer();
-#endif
 // ---------------------------------------------------------------------------------------------
 // chain kernel
 // ---------------------------------------------------------------------------------------------
@@ -488,7 +434,6 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     constexpr bool T8 = Pol::TAPE8;
     const FusedArgs &a = A.f;
     clock_stamp(a.clk, MODE == MODE_CHAIN ? BHN_CLK_CHAIN : BHN_CLK_FWD_TRAIN, 0);
-    const int edbg = BHN_DBG(((A.debug >> 6) & 3) | (A.policy << 2));  // measurement aid for the tape emission (bits 2,3: store policy)
     constexpr int sdbg = 0;                        // (a run-time MFMA-skip flag put every MFMA in its own basic block)
     // the delta chain's transposed image never uses the two encoded-input fragments of a chunk: its ring copies (and its steps
     // stream) only the KS hidden fragments; the training forward (bf16) keeps them in a resident block of their own (EncBlock)
@@ -497,19 +442,16 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     constexpr bool ENCR = MODE != MODE_CHAIN && EB::ON && !RES;
     constexpr int NFR = ((MODE == MODE_CHAIN && KS >= 8) || ENCR) ? KS : KS + 2;
     using RG = DmaRing<RES ? CB : NFR * Pol::FRAG_BYTES, Pol::NWAVES, GA0C>;     // (GA0C: transposed LDS reads in the kernel -> asm DMA)
-    constexpr int DIST = GA0C ? BHN_GA0C_DIST : BG::RING_DIST_TAPED;
-    using RS = std::conditional_t<RES, ResidentRing<RG, CB, MT>, RingState<RG, CB, DIST, false, MT, BHN_CHAIN_STAMPS != 0>>;
+    constexpr int DIST = GA0C ? GA0C_DIST : BG::RING_DIST_TAPED;
+    using RS = std::conditional_t<RES, ResidentRing<RG, CB, MT>, RingState<RG, CB, DIST, false, MT>>;
     // stores guaranteed younger than chunk c+2 at the end of step c (RingState::step_end): every interval between
     // two DMA issues holds the >= ES stores of one pending-tile emission; with >= 16 k-steps the running step's
     // own emission (k-step 12) also follows its DMA issue (k-step 9).  The DMA pieces of the DIST-2 younger chunks
     // cancel out of the balance, so only this store count has to be a lower bound (relu-bit words, epilogue stores and
     // prefetch loads only add slack); the exceptions are the steps right after a layer-0 step without h_1 emission.
     constexpr int ES = T8 ? 1 : (Pol::ELEM_BYTES == 2) ? 2 : 4;        // global stores of one tile emission
-#ifndef BHN_YS_EXTRA
-#define BHN_YS_EXTRA 0          // EXPERIMENT ONLY (-DBHN_YS_EXTRA=n): lets n more stores stay in flight than the ring proof allows
-#endif                          // (racy: wrong results possible) -- measures what the in-order vmcnt coupling of stores and weight DMA costs
-    constexpr int YS = ES * (DIST - 2) + ((KS >= 16 && Pol::ELEM_BYTES == 2) ? ES : 0) + BHN_YS_EXTRA;   // (f32: kept conservative)
-    constexpr int YS0 = ES * (DIST - 2) + BHN_YS_EXTRA;                // steps whose own stores precede their DMA issue
+    constexpr int YS = ES * (DIST - 2) + ((KS >= 16 && Pol::ELEM_BYTES == 2) ? ES : 0);   // (f32: kept conservative)
+    constexpr int YS0 = ES * (DIST - 2);                               // steps whose own stores precede their DMA issue
     constexpr int YS_L1r = (KS >= 16) ? YS - ES : 0;                   // first steps of layer 1 when h_1 is not emitted
     constexpr int YS_L1 = YS_L1r > 0 ? YS_L1r : 0;
     const int NCF = (MODE == MODE_CHAIN) ? 0 : PK::fwd_chunks(A.f.depth);
@@ -536,7 +478,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     // 4 r .. 4 r + 3) swapped.  A ds_write_b128 retires 8 consecutive lanes (128 bytes) per LDS cycle -- points 8 i .. 8 i + 7 of one lane
     // half, i.e. the first 64 bytes of two consecutive rows: the same 16 banks twice in the plain layout (SQ_LDS_BANK_CONFLICT 6.7 % of
     // this kernel's LDS cycles in round 5).  The consumer's transposed reads gather whole rows and only swap the halves back.
-    const int stage_off = TapeEmit<Pol>::native_off(0) ^ ((GA0C && BHN_GA0C_SWZ) ? ((int)(threadIdx.x >> 2) & 1) << 6 : 0);
+    const int stage_off = TapeEmit<Pol>::native_off(0) ^ (GA0C ? ((int)(threadIdx.x >> 2) & 1) << 6 : 0);
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, pl = lane & 31, h = lane >> 5;
     const int wvu = __builtin_amdgcn_readfirstlane(wv);           // the wave index as a scalar: tape addresses stay in SGPRs
@@ -640,7 +582,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     f32x16 cacc0 = {}, cacc1 = {};
     Ga0Consumer cons;
     cons.trl = tr_lane_off(); cons.ga = cons.enc = nullptr;
-    cons.trl_ga = cons.trl ^ ((GA0C && BHN_GA0C_SWZ) ? ((int)(threadIdx.x >> 5) & 1) << 6 : 0);      // (a read's two row pairs: rows g >> 1 and + 2 -- the parity is lane >> 5)
+    cons.trl_ga = cons.trl ^ (GA0C ? ((int)(threadIdx.x >> 5) & 1) << 6 : 0);      // (a read's two row pairs: rows g >> 1 and + 2 -- the parity is lane >> 5)
     int tpar = 0;                                    // parity of the tile: which encS image it uses
     bool have_prev = false;                          // the previous tile's gA_0 tiles MT-2, MT-1 are staged and not yet consumed
     bool has_next = false;                           // this workgroup has another tile after the running one (its inputs are being prefetched)
@@ -652,7 +594,6 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
         const long long p = (MODE != MODE_CHAIN) ? in.p : cin.p;
         const bool inb = (MODE != MODE_CHAIN) ? in.inb : cin.inb;
         const long long q = tile * Pol::NWAVES + wvu;                    // 32-point group on the tape
-        const long long qs = BHN_DBG(A.wrap) ? q % A.wrap : q;           // (debug: h / gA tiles wrap into a cache-resident window)
         unsigned *mask_g = A.t.fused128 ? nullptr : reinterpret_cast<unsigned *>(A.tape + A.t.mask_off) + q * (long long)(a.depth * MW * 64);
         // (TapeLayout::drop_hd: the relu bits of the last hidden layer, recorded in place of its output tiles)
         unsigned *maskd_g = (MODE == MODE_FWD_TRAIN && A.t.drop_hd && A.t.fused128) ? reinterpret_cast<unsigned *>(A.tape + A.t.maskd_off) + q * (long long)(MW * 64) + lane : nullptr;
@@ -660,7 +601,6 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
         frag enc[2], act[KS], next[KS];
         bool live = false;
         float e = 0.f;
-        if (BHN_CHAIN_STAMPS && have_ring) rs.ts = (A.ts_buf && blockIdx.x == 0 && tile == 3 * (long long)gridDim.x) ? A.ts_buf + __builtin_amdgcn_readfirstlane(wv) * 64 : nullptr;
         if constexpr (MODE != MODE_CHAIN) {
             point_prologue<Pol, DEG>(a, in, enc, live);
             // the encoded inputs are the B operand of dW_0 and of the skip layer
@@ -669,10 +609,10 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                 // it the fused dW GEMMs of fused_bwd128.hip (and the delta chain's own dW_0, ga0_chain) produce the bias gradients
                 frag e1 = enc[1];
                 if (h) Pol::set(e1, 7, 1.f);
-                em.emit(A.tape + A.t.enc_off + q * TB, enc[0], e1, edbg);
-            } else em.emit(A.tape + A.t.enc_off + q * TB, enc[0], enc[1], edbg);
+                em.emit(A.tape + A.t.enc_off + q * TB, enc[0], e1);
+            } else em.emit(A.tape + A.t.enc_off + q * TB, enc[0], enc[1]);
             const bool drop_h1 = A.t.drop_h1;
-            if (drop_h1 && !A.t.fused128 && !(edbg & 2)) {        // ... and, as they are, the A operand from which dW_1 recomputes h_1
+            if (drop_h1 && !A.t.fused128) {        // ... and, as they are, the A operand from which dW_1 recomputes h_1
                 __builtin_nontemporal_store(enc[0], reinterpret_cast<frag *>(A.tape + A.t.encp_off + q * TB + lane * 16));
                 __builtin_nontemporal_store(enc[1], reinterpret_cast<frag *>(A.tape + A.t.encp_off + q * TB + Pol::FRAG_BYTES + lane * 16));
             }
@@ -682,7 +622,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                 char *dst;
                 unsigned *mword, *stash;
                 unsigned macc;
-                int edbg;
+                int flags;                       // 0 (EMIT_*: kept for the same reason as in TapeEmit::store_native)
                 DEVI void tile(int m, const f32x16 &acc, frag &d0, frag &d1) {
                     unsigned mk = 0;
                     pack_elems<Pol, 0, 16>(acc, d0, d1, mk);
@@ -692,10 +632,10 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                         if (mword) __builtin_nontemporal_store(macc, mword + (m >> 1) * 64);
                         if (stash) stash[(m >> 1) * 64] = macc;
                     }
-                    if (dst) em.emit(dst + (long long)m * TB, d0, d1, edbg);
+                    if (dst && !(flags & EMIT_OFF)) em.emit(dst + (long long)m * TB, d0, d1);
                 }
-            } l0{em, drop_h1 ? nullptr : A.tape + h_lin + lin_stride + qs * MT * TT, mask_g ? mask_g + lane : nullptr,
-                 nullptr, 0u, edbg};
+            } l0{em, drop_h1 ? nullptr : A.tape + h_lin + lin_stride + q * MT * TT, mask_g ? mask_g + lane : nullptr,
+                 nullptr, 0u, 0};
             f32x16 pend;
             layer0_step<W, Pol, RG, YS0, RS, Tile0, NFR>(rs, ap, enc, act, bias_lds, h, pend, l0);
             // ---- hidden layers 1..depth-1 and the output layer: the pending tile is (l-1, MT-1) at m = 0 ------
@@ -716,16 +656,15 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     frag &d0 = m == 0 ? act[KS - 2] : next[2 * (m > 0 ? m - 1 : 0)];
                     frag &d1 = m == 0 ? act[KS - 1] : next[2 * (m > 0 ? m - 1 : 0) + 1];
                     const int widx = (pl_layer * MW + (pm >> 1)) * 64 + lane;
-                    // h_depth: relu bits only (drop_hd).  fused128 (resident weights, no ring): no store at all; ring kernels: the
-                    // emission's two stores stay, four bytes each to a 256-KiB scratch area of the tape (bit 4; one line per tile: all on one line was a hot spot) -- the waits of the weight ring
-                    // count the stores of every step (YS above), and a step without them would need counts of its own
-                    constexpr bool CAN_HD = BHN_DROP_HD != 0 || (W == 128 && Pol::ELEM_BYTES == 2 && !T8);      // (fused128: width 128, bf16)
+                    // h_depth: relu bits only (drop_hd: fused128, whose training forward keeps its weights resident -- bwd_run checks
+                    // that; a ring kernel would have to keep the emission's stores, which the waits of the weight ring count (YS above))
+                    constexpr bool CAN_HD = W == 128 && Pol::ELEM_BYTES == 2 && !T8;
                     const bool no_hd = CAN_HD && A.t.drop_hd && pl_layer == a.depth - 1;
                     const bool no_h = (drop_h1 && pl_layer == 0) || (no_hd && RES);       // layer 0's last tile: relu bits only
-                    const int edbg_t = no_h ? (edbg | 2) : (no_hd ? (edbg | 16) : edbg);
-                    TapePost<Pol, true> post(pend, d0, d1, 0u, em, (no_hd && !RES) ? A.tape + A.t.scratch_off + (((q * MT + pm) & 4095) << 6) : A.tape + h_lin + (pl_layer + 1) * lin_stride + (qs * MT + pm) * TT,
+                    const int flags_t = no_h ? EMIT_OFF : 0;
+                    TapePost<Pol, true> post(pend, d0, d1, 0u, em, (no_hd && !RES) ? A.tape + A.t.scratch_off + (((q * MT + pm) & 4095) << 6) : A.tape + h_lin + (pl_layer + 1) * lin_stride + (q * MT + pm) * TT,
                                                  mask_g ? mask_g + widx : (no_hd && maskd_g ? maskd_g + (pm >> 1) * 64 : nullptr), nullptr,
-                                                 macc, pm & 1, pm == MT - 1, edbg_t, 1.f, t8_none);
+                                                 macc, pm & 1, pm == MT - 1, flags_t, 1.f, t8_none);
                     // bias rows of the next tile: (l, m+1), or the first tile of the next sequence part
                     const float *bn = (out || (m == MT - 1 && l + 1 > a.depth)) ? nullptr : bl + 32 * (m + 1);
                     if (out) bn = bias_lds;                           // next tile, layer 0
@@ -753,10 +692,8 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
             if constexpr (GA0C) {                    // this group's encoded-input tile (tape, slot 31 = 1) -> encS[tpar][wave]
                 const char *esrc = A.tape + A.t.enc_off + q * TB;
                 char *edst = encS + tpar * STG + wvu * TB;
-                if (!(BHN_GA0C_ABL & 4)) {
-                    dma_1k_asm<1>(esrc, edst);
-                    dma_1k_asm<1>(esrc + 1024, edst + 1024);
-                }
+                dma_1k_asm<1>(esrc, edst);
+                dma_1k_asm<1>(esrc + 1024, edst + 1024);
             }
         }
         // ---- e ; dE, dout -----------------------------------------------------------------------
@@ -778,12 +715,12 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                 // (8-bit tape: that job turns them into e4m3(dout / scale) -- which makes NaN of anything beyond 448 scale)
                 float dt = d;
                 if constexpr (T8) { const float lim = 448.f * t8_lds[a.depth - 1]; dt = __builtin_amdgcn_fmed3f(d, -lim, lim); }
-                if (h == 0 && !(edbg & 2)) __builtin_nontemporal_store(dt, reinterpret_cast<float *>(dgrp) + pl);
+                if (h == 0) __builtin_nontemporal_store(dt, reinterpret_cast<float *>(dgrp) + pl);
             } else {
                 // dout as a 32x32 (feature x point) tile whose feature 0 is dout: the A operand of dW_out
                 frag d0 = Pol::zero(), d1 = Pol::zero();
                 Pol::set(d0, 0, h == 0 ? d : 0.f);
-                em.emit(dgrp, d0, d1, edbg);
+                em.emit(dgrp, d0, d1);
             }
         }
         if constexpr (MODE == MODE_CHAIN) {
@@ -793,7 +730,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
             unsigned last_mask = 0xffffu;            // relu bits still to be applied to the pending tile of gA_{depth-1}
             {
                 const bool keep_ga = !A.t.drop_ga;                    // else the dW kernel rebuilds gA_{depth-1}
-                char *gdst = A.tape + ga_lin + (a.depth - 1) * lin_stride + qs * MT * TT;
+                char *gdst = A.tape + ga_lin + (a.depth - 1) * lin_stride + q * MT * TT;
                 if constexpr (Pol::ELEM_BYTES == 2) {
                     if (A.t.drop_ga) {
                         // W_out sits in the columns of this layer's transposed weight image (bhn_folds_wout): the B operand
@@ -841,7 +778,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                         for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
                             for (int j = 0; j < 8; ++j) Pol::set(dl[2 * m + s2], j, g[8 * s2 + j]);
-                        if (keep_ga) em.emit(gdst + m * TB, dl[2 * m], dl[2 * m + 1], edbg);
+                        if (keep_ga) em.emit(gdst + m * TB, dl[2 * m], dl[2 * m + 1]);
                     } else pend = g;
                 }
                 }
@@ -866,7 +803,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     frag &d1 = m == 0 ? dl[KS - 1] : next[2 * (m > 0 ? m - 1 : 0) + 1];
                     const bool no_ga = (A.t.drop_ga && pnd_layer == a.depth - 1) || (GA0C && pnd_layer == 0);     // gA_{depth-1}'s last tile: not recorded; GA0C: gA_0 is staged
                     // GA0C: a finished gA_0 tile goes to the LDS staging image gaS[tile & 1] instead of the tape
-                    const bool staged = GA0C && pnd_layer == 0 && !(BHN_GA0C_ABL & 2);
+                    const bool staged = GA0C && pnd_layer == 0;
                     char *stage = staged ? gaS + (pm & 1) * STG + wvu * TB : nullptr;
                     // GA0C: the consumer of this step is wave (m - 2) mod MT: in layer 1 it adds the gA_0 tile m - 2 (staged in step
                     // m - 1, published by that step's barrier) of all waves to its accumulator; in the first two steps of the NEXT
@@ -874,15 +811,15 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     bool cons_on = false;
                     const int ctile = (m + MT - 2) % MT;             // the gA_0 tile consumed in step m (of layer 1; m <= 1: of the next tile's first layer)
                     if constexpr (GA0C) {
-                        if (!(BHN_GA0C_ABL & 1) && wvu == ctile % NCW) {
+                        if (wvu == ctile % NCW) {
                             if (l == 1 && m >= 2) { cons_on = true; cons.ga = gaS + (m & 1) * STG; cons.enc = encS + tpar * STG; }
                             else if (l == a.depth - 1 && m <= 1 && have_prev) { cons_on = true; cons.ga = gaS + m * STG; cons.enc = encS + (tpar ^ 1) * STG; }
                         }
                     }
                     const float *bias_nx = (l == LEND && m == MT - 1) ? first_bias : zero_lds;
-                    char *tdst = A.tape + ga_lin + pnd_layer * lin_stride + (qs * MT + pm) * TT;
+                    char *tdst = A.tape + ga_lin + pnd_layer * lin_stride + (q * MT + pm) * TT;
                     TapePost<Pol, false, GA0C> post(pend, d0, d1, pnd_mask, em, tdst, nullptr, nullptr, no_acc, T8 && (pm & 1), false,
-                                                    no_ga ? (edbg | 2) : edbg, t8_sc, t8_amax);
+                                                    no_ga ? EMIT_OFF : 0, t8_sc, t8_amax);
                     post.stage = stage; post.stage_off = stage_off;
                     const f32x16 acc = ring_step<W, Pol, RG, TapePost<Pol, false, GA0C>, NFR, GA0C>(ch, chn, ap, dl, enc, false, bias_nx, post, dj, sdbg);
                     if constexpr (GA0C) {
@@ -893,7 +830,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     if constexpr (GA0C) {
                         // tile emissions (ES stores each) among this step and the DIST - 2 before it: none in the steps whose pending tile
                         // is a gA_0 tile (layer 1, m >= 1) or gA_{depth-1}'s (first step of a tile)
-                        static_assert(!GA0C || BHN_GA0C_DIST == 4, "the store counts below are written for a window of three steps");
+                        static_assert(!GA0C || GA0C_DIST == 4, "the store counts below are written for a window of three steps");
                         // The first two steps of a tile also have the tile top's operations inside their window -- two encoded-input DMA
                         // pieces, the dout store, and with a next tile the MW relu-bit words fetched at the end of the previous tile's last
                         // layer and the next tile's prefetch (MW relu-bit words, e): counting them keeps the HBM latency of those loads out
@@ -936,7 +873,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
             }
             if (a.depth > 1) {           // flush the last tile of gA_{LEND-1} (no further step to hide it behind)
                 TapePost<Pol, false, GA0C> post(pend, dl[KS - 2], dl[KS - 1], pnd_mask, em,
-                                              A.tape + ga_lin + (LEND - 1) * lin_stride + (qs * MT + MT - 1) * TT, nullptr, nullptr, no_acc, T8 && ((MT - 1) & 1), false, GA0C ? (edbg | 2) : edbg,
+                                              A.tape + ga_lin + (LEND - 1) * lin_stride + (q * MT + MT - 1) * TT, nullptr, nullptr, no_acc, T8 && ((MT - 1) & 1), false, GA0C ? EMIT_OFF : 0,
                                               t8_sc, t8_amax);
                 if constexpr (GA0C) { post.stage = gaS + ((MT - 1) & 1) * STG + wvu * TB; post.stage_off = stage_off; }     // consumed in the second step of the next tile
                 post.all();
@@ -1053,39 +990,32 @@ struct TapeStream {
     // 64 16-byte slots of a piece can be had for free by permuting these offsets (voffA, region 0).
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"      // (only: "inline asm clobber list contains reserved registers: M0")
-    template <int POLICY>
     static DEVI void dma(const u32x4 &rs, unsigned soff, unsigned m, unsigned voff) {
-        if constexpr (POLICY == 1)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds" ::"s"(m), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
-        else if constexpr (POLICY == 2)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds" ::"s"(m), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
-        else
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(m), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds" ::"s"(m), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
     }
 #pragma clang diagnostic pop
-    template <int POLICY, int I>
+    template <int I>
     DEVI void row(long long q, unsigned lb, u32x4 (&rs)[4]) const {
         constexpr int p0 = NW * I;
         if constexpr (uniform_row(I)) {                               // a whole row inside one region
             constexpr int r = region_of(p0), rel = (p0 - region_start(r)) * 1024;
             if constexpr (!(uniform_row(I - 1) && region_of(NW * (I - 1)) == r))      // first such row: the region's resource
                 rs[r] = rsrc(src[r] + wvu * 1024 + q * stride[r]);
-            dma<POLICY>(rs[r], (unsigned)rel, lb + (unsigned)(wvu * 1024 + region_lds(r) + rel), r == 0 ? voffA : (threadIdx.x & 63) * 16);
+            dma(rs[r], (unsigned)rel, lb + (unsigned)(wvu * 1024 + region_lds(r) + rel), r == 0 ? voffA : (threadIdx.x & 63) * 16);
         } else {                                                      // a row across regions / the ragged tail
             constexpr int k = mixed_before(I);
-            dma<POLICY>(rsrc(msrc[k] + q * mstride[k]), 0u, lb + (unsigned)mlds[k], (threadIdx.x & 63) * 16);
+            dma(rsrc(msrc[k] + q * mstride[k]), 0u, lb + (unsigned)mlds[k], (threadIdx.x & 63) * 16);
         }
     }
-    template <int POLICY, int... I>
+    template <int... I>
     DEVI void rows(long long q, unsigned lb, u32x4 (&rs)[4], std::integer_sequence<int, I...>) const {
-        (row<POLICY, I>(q, lb, rs), ...);
+        (row<I>(q, lb, rs), ...);
     }
     // group q -> LDS image at `buf`
-    template <int POLICY>
     DEVI void issue(long long q, char *buf) const {
         const unsigned lb = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<unsigned long long>(buf));
         u32x4 rs[4];                                                  // (indexed by compile-time constants only)
-        rows<POLICY>(q, lb, rs, std::make_integer_sequence<int, PPW>{});
+        rows(q, lb, rs, std::make_integer_sequence<int, PPW>{});
     }
 };
 
@@ -1210,27 +1140,20 @@ DEVI void dw_body(const BwdArgs &A, int job, char *smem) {
             // consumed; the counted wait leaves NBUF-2 younger groups in flight.  (f32: 2 buffers of 68 KB -- the DMA of
             // group q+1 runs under the MFMAs of group q, which are several times longer than an HBM round trip)
             constexpr int NBUF = BG::NBUF;
-            auto issue = [&](long long q, char *buf) {
-                q = q < q1 ? q : q1 - 1;
-                if (BHN_DBG(A.wrap)) q %= A.wrap;
-                if (BHN_DBG(A.policy == 1)) stream.template issue<0>(q, buf);
-                else if (BHN_DBG(A.policy == 2)) stream.template issue<2>(q, buf);
-                else stream.template issue<1>(q, buf);
-            };
+            auto issue = [&](long long q, char *buf) { stream.issue(q < q1 ? q : q1 - 1, buf); };
             constexpr int INFLIGHT = NBUF - 2;
             if (q0 < q1) {
 #pragma unroll
                 for (int j = 0; j < NBUF - 1; ++j) issue(q0 + j, smem + j * GB);
                 int it = 0;
                 for (long long q = q0; q < q1; ++q) {
-                    if (!BHN_DBG(A.debug & 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(INFLIGHT * PPW) : "memory");
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(INFLIGHT * PPW) : "memory");
                     __builtin_amdgcn_s_barrier();
                     asm volatile("" ::: "memory");      // the raw barrier is not a compiler fence: keep the
                                                          // DMA issue and the ds_reads below it
                     const int nx = (it == 0) ? NBUF - 1 : it - 1;
-                    if (!BHN_DBG(A.debug & 2)) issue(q + NBUF - 1, smem + nx * GB);
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (!BHN_DBG(A.debug & 1) && wave_works && has_tiles) compute_group(smem + it * GB);
+                    issue(q + NBUF - 1, smem + nx * GB);
+                    if (wave_works && has_tiles) compute_group(smem + it * GB);
                     it = (it == NBUF - 1) ? 0 : it + 1;
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1286,7 +1209,7 @@ DEVI void dw_body(const BwdArgs &A, int job, char *smem) {
 // The first version (dw_body above, still used by the f32 policy) ran per group: vmcnt wait -> barrier -> DMA issue ->
 // A-fragment LDS reads -> wait -> MFMAs; with the two waves of a SIMD in barrier lockstep everything in front of the
 // MFMAs was dead time for the matrix pipe (about 2600 cycles per group for 1024-1280 cycles of MFMA work; the
-// kernel took the same time whether its tape came from HBM or from an L2-resident window, tools/dbg_wrap.py).  Here
+// kernel took the same time whether its tape came from HBM or from an L2-resident window, round 2).  Here
 // group q+1 is published one barrier EARLY (the wait at the top of iteration q is for group q+1), so that while the
 // MFMAs of group q run, the A fragments of group q+1 are read from LDS and prepared (layer depth-1: gA rebuilt from
 // h_depth, the output layer's row; all: bias sums) and its first two B fragments are fetched.  Ring of 4 group buffers:
@@ -1319,29 +1242,19 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     constexpr int GB = OFF_D32 + (LAST ? 1024 : 0);
     static_assert(T8 || (OFF_D32 == BG::GROUP_BYTES && GB == (LAST ? BG::GROUP_BYTES_LAST2 : BG::GROUP_BYTES)), "group image");
     static_assert(GB <= BG::GROUP_BYTES + 1024, "group image larger than the host's LDS budget");
-#ifndef BHN_T8_NBUF
-#define BHN_T8_NBUF 4            // ring depth of the 8-bit tape's dW jobs (8 = the bf16 jobs' bytes in flight: measured no faster, the jobs are VALU-bound)
-#endif
-    constexpr int NB = (T8 && !make_h) ? BHN_T8_NBUF : 4;              // group buffers of the ring (a power of two)
+    constexpr int NB = (T8 && !make_h) ? T8_NBUF : 4;                  // group buffers of the ring (a power of two)
     static_assert((NB & (NB - 1)) == 0 && NB >= 4 && NB * GB <= 160 * 1024, "ring size");
     constexpr int nH = has_h ? MT : 0, nB = nH + ((JT == JT_FIRST || JT == JT_SKIP) ? 1 : 0);   // slab tile nB: the bias column
     constexpr int nBr = has_h ? MT : 1;                                // B tiles of the regular tile grid
     constexpr int WRR = BG::WRR, WCC = BG::WCC;
     constexpr int MPW = (MT + WRR - 1) / WRR, NPW = (nBr + WCC - 1) / WCC;
     static_assert(NPW <= 5, "one sweep");
-    constexpr bool B8 = T8 && has_h && !make_h;                       // the B tiles are 8-bit tape tiles too
-#ifndef BHN_T8_ABL
-#define BHN_T8_ABL 0             // measurement builds (results wrong): 1 no e4m3 MFMAs, 2 no A preparation, 4 no B sorting in the e4m3 jobs, 8 the tape stream only (no MFMA phase in any 8-bit job)
-#endif
-#ifndef BHN_T8_F8MFMA
-#define BHN_T8_F8MFMA 1          // 0 (A/B builds): widen both operands to bf16 in front of every MFMA (the first version)
-#endif
-    // both operands 8-bit: the weight-gradient tiles are accumulated by v_mfma_f32_32x32x16_fp8_fp8 straight from the sorted
-    // bytes (gA / scale times h; the scale is applied at the flush); bf16 is made only where bf16 code needs it (bias sums,
-    // the encoded-input tile, the output layer's row)
-    constexpr bool F8 = B8 && BHN_T8_F8MFMA != 0;
+    // the B tiles are 8-bit tape tiles too: with both operands 8-bit the weight-gradient tiles are accumulated by
+    // v_mfma_f32_32x32x16_fp8_fp8 straight from the sorted bytes (gA / scale times h; the scale is applied at the flush); bf16 is
+    // made only where bf16 code needs it (bias sums, the encoded-input tile, the output layer's row)
+    constexpr bool F8 = T8 && has_h && !make_h;
     static_assert(!T8 || MPW == 2, "8-bit tape: the A tiles come in pairs (width 256)");
-    static_assert(!B8 || NPW % 2 == 0, "8-bit tape: the B tiles come in pairs (width 256)");
+    static_assert(!F8 || NPW % 2 == 0, "8-bit tape: the B tiles come in pairs (width 256)");
     constexpr int ME = (MPW + WCC - 1) / WCC;                          // A tiles a wave pairs with the enc tile / the output row
     constexpr int NTOT = 2 * NPW;                                      // MFMA steps per group (k-step major)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: wave-uniform branches
@@ -1417,7 +1330,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
 #pragma unroll
     for (int ni = 0; ni < NPW; ++ni) {
         const int n = nbase + ni;
-        boff[ni] = has_h ? OFF_H + (n < nH ? n : 0) * (B8 ? TT : TB) : OFF_E;        // a column share that ends early repeats tile 0 (dropped at the flush)
+        boff[ni] = has_h ? OFF_H + (n < nH ? n : 0) * (F8 ? TT : TB) : OFF_E;        // a column share that ends early repeats tile 0 (dropped at the flush)
     }
     // LBITS: where this lane's feature (row lane & 31 of A tile T) sits in the forward's relu-bit words
     int lb_word[MPW];
@@ -1496,9 +1409,6 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     auto a_prep = [&](AState &st, int k, bool live) {
         const int s2 = k / MPW, mi = k % MPW;
         if constexpr (F8) {
-#if (BHN_T8_ABL & 2)
-            return;
-#endif
             if (mi == 0) {
                 const u32x4 rw = __builtin_bit_cast(u32x4, st.af[s2][0]);
                 Raw8 raw;
@@ -1615,11 +1525,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
             for (int t = 0; t < NTOT; ++t) {
                 const int u = t >> 1, e = t & 1;
                 if (e == 0 && u + 1 < NPAIR) {
-#if (BHN_T8_ABL & 4)
-                    const Pair8 pr = {rnext.lo, rnext.hi};
-#else
                     const Pair8 pr = tr8_sort(rnext);
-#endif
                     bnx = (u32x4){pr.a[0], pr.a[1], pr.b[0], pr.b[1]};
                     if (u + 2 < NPAIR) rnext = load_braw(gp, u + 2);
                 }
@@ -1629,13 +1535,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
                 const int s2 = t / NPW, ni = t % NPW;
                 const u32x2 bnow = e == 0 ? (u32x2){bcur[0], bcur[1]} : (u32x2){bcur[2], bcur[3]};
 #pragma unroll
-                for (int mi = 0; mi < MPW; ++mi) {
-#if (BHN_T8_ABL & 1)
-                    asm volatile("" :: "v"(cur.a8[s2][mi]), "v"(bnow));
-#else
-                    acc[mi][ni] = mma8(cur.a8[s2][mi], bnow, acc[mi][ni]);
-#endif
-                }
+                for (int mi = 0; mi < MPW; ++mi) acc[mi][ni] = mma8(cur.a8[s2][mi], bnow, acc[mi][ni]);
                 if constexpr (enc_extra) {
                     if (ni == NPW - 1) {
 #pragma unroll
@@ -1656,58 +1556,15 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
             }
             return;
         }
-        if constexpr (B8) {
-            // 8-bit B tiles come in pairs (tiles 2k, 2k+1 of the wave's share, one k-step = MFMA steps 2u, 2u+1): the raw
-            // read of pair u+1 is in flight while pair u is widened and used
-            constexpr int NPAIR = NTOT / 2;
-            frag bcur[2] = {bc[0], bc[1]}, bnx[2];
-            Raw8 rnext, rawn;
-            if (NPAIR > 1) rnext = load_braw(gp, 1);
-#pragma unroll
-            for (int t = 0; t < NTOT; ++t) {
-                const int u = t >> 1, e = t & 1;
-                if (e == 0 && u + 1 < NPAIR) {
-                    tr8_widen(rnext, 1.f, bnx[0], bnx[1]);
-                    if (u + 2 < NPAIR) rnext = load_braw(gp, u + 2);
-                }
-                if (enc_extra && (t % NPW) == (NPW >= 2 ? NPW - 2 : 0)) benc = tr_frag(gp + OFF_E, t / NPW, trl);
-                if (t == 0) a_load(gnext, nx);
-                __builtin_amdgcn_sched_barrier(0);
-                const int s2 = t / NPW, ni = t % NPW;
-#pragma unroll
-                for (int mi = 0; mi < MPW; ++mi) acc[mi][ni] = Pol::mma(cur.af[s2][mi], bcur[e], acc[mi][ni]);
-                if constexpr (enc_extra) {
-                    if (ni == NPW - 1) {
-#pragma unroll
-                        for (int mi = 0; mi < MPW; ++mi)
-                            if ((mi % WCC) == wc) acc_e[mi / WCC] = Pol::mma(cur.af[s2][mi], benc, acc_e[mi / WCC]);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < NPREP; ++k)
-                    if (t == (T_PREP + k < NTOT ? T_PREP + k : NTOT - 1)) a_prep(nx, k, live_next);
-                if (t == (NTOT >= 2 ? NTOT - 2 : 0)) rawn = load_braw(gnext, 0);
-                if (t == NTOT - 1) tr8_widen(rawn, 1.f, bn[0], bn[1]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (e == 1) { bcur[0] = bnx[0]; bcur[1] = bnx[1]; }
-            }
-            return;
-        }
         if constexpr (make_h) {
             bq[0] = load_b(gp, 0);
             if (NTOT > 1) bq[1] = load_b(gp, 1);
         } else {
             bq[0] = bc[0]; bq[1] = bc[1];
         }
-#ifndef BHN_DW_ABL_READS
-#define BHN_DW_ABL_READS 0       // measurement builds (dW wrong): 1 = every second B fragment is not read (the previous one is used again):
-#endif                           // 8 instead of 12 transposed fragment reads per 16 MFMAs -- the LDS traffic of 4 x 4 register blocking
 #pragma unroll
         for (int t = 0; t < NTOT; ++t) {
-            if (t + 2 < NTOT) {
-                if (BHN_DW_ABL_READS && ((t + 2) & 1)) bq[(t + 2) % 3] = bq[(t + 1) % 3];
-                else bq[(t + 2) % 3] = load_b(gp, t + 2);
-            }
+            if (t + 2 < NTOT) bq[(t + 2) % 3] = load_b(gp, t + 2);
             if (enc_extra && (t % NPW) == (NPW >= 2 ? NPW - 2 : 0)) benc = tr_frag(gp + OFF_E, t / NPW, trl);     // used at ni == NPW-1
             if (t == 0) a_load(gnext, nx);
             __builtin_amdgcn_sched_barrier(0);
@@ -1726,7 +1583,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
                 if (t == (T_PREP + k < NTOT ? T_PREP + k : NTOT - 1)) a_prep(nx, k, live_next);
             if constexpr (!make_h) {
                 if (t == (NTOT >= 2 ? NTOT - 2 : 0)) bn[0] = load_b(gnext, 0);
-                if (t == NTOT - 1) bn[1] = BHN_DW_ABL_READS ? bn[0] : load_b(gnext, NTOT > 1 ? 1 : 0);
+                if (t == NTOT - 1) bn[1] = load_b(gnext, NTOT > 1 ? 1 : 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1738,20 +1595,14 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     using Stream = TapeStream<Pol::NWAVES, PA, PH, PE, PD, OFF_H, OFF_E, OFF_D32>;
     constexpr int PPW = Stream::PPW;
     const Stream stream(srcA, LBITS ? (long long)A.f.depth * MWB : (long long)MT * TT, srcH, (long long)MT * TT, srcE, TB, srcD, A.t.dout_stride, wv);
-    auto issue = [&](long long q, char *buf) {
-        q = q < q1 ? q : q1 - 1;
-        if (BHN_DBG(A.wrap)) q %= A.wrap;
-        if (BHN_DBG(A.policy == 1)) stream.template issue<0>(q, buf);
-        else if (BHN_DBG(A.policy == 2)) stream.template issue<2>(q, buf);
-        else stream.template issue<1>(q, buf);
-    };
+    auto issue = [&](long long q, char *buf) { stream.issue(q < q1 ? q : q1 - 1, buf); };
     __syncthreads();                                            // W_0 / b_0 visible (HIDDEN1)
     if (q0 < q1) {
         AState sa, sb;
         frag ba[2], bb[2];
 #pragma unroll
         for (int j = 0; j < NB - 1; ++j) issue(q0 + j, smem + j * GB);
-        if (!BHN_DBG(A.debug & 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 2) * PPW) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 2) * PPW) : "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if constexpr (make_h) make_h_write(smem, make_h_mma(make_h_read(smem)));     // published by the first loop barrier
@@ -1762,24 +1613,22 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
             if constexpr (F8) {
                 const Pair8 pr = tr8_sort(load_braw(smem, 0));
                 ba[0] = __builtin_bit_cast(frag, (u32x4){pr.a[0], pr.a[1], pr.b[0], pr.b[1]});
-            } else if constexpr (B8) tr8_widen(load_braw(smem, 0), 1.f, ba[0], ba[1]);
-            else if constexpr (!make_h) { ba[0] = load_b(smem, 0); ba[1] = load_b(smem, NTOT > 1 ? 1 : 0); }
+            } else if constexpr (!make_h) { ba[0] = load_b(smem, 0); ba[1] = load_b(smem, NTOT > 1 ? 1 : 0); }
         }
         auto body = [&](AState &cur, AState &nx, frag (&bc)[2], frag (&bn)[2], long long q, int it) {
             // group q+1 has landed for this wave (q+2 .. q+NB-2 may still be in flight), then it is published to the workgroup
-            if (!BHN_DBG(A.debug & 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 3) * PPW) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 3) * PPW) : "memory");
             if constexpr (make_h) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's h-tile writes
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");      // the raw barrier is not a compiler fence
             // every wave has finished group q-1: its buffer takes group q+NB-1
-            if (!BHN_DBG(A.debug & 2)) issue(q + NB - 1, smem + ((it + NB - 1) & (NB - 1)) * GB);
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            issue(q + NB - 1, smem + ((it + NB - 1) & (NB - 1)) * GB);
             const char *gp = smem + it * GB;
             char *gnext = smem + ((it + 1) & (NB - 1)) * GB;
             const bool live_next = q + 1 < q1;
             f32x16 hacc = {};
             if constexpr (make_h) hacc = make_h_mma(make_h_read(gnext));
-            if (!BHN_DBG(A.debug & 1) && works && !(T8 && (BHN_T8_ABL & 8))) mma_phase(gp, cur, bc, gnext, nx, bn, live_next);
+            if (works) mma_phase(gp, cur, bc, gnext, nx, bn, live_next);
             if constexpr (make_h) {
                 if (live_next) make_h_write(gnext, hacc);
             }
@@ -1939,10 +1788,6 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
     clock_stamp(A.f.clk, BHN_CLK_DW, 0);
     int job = 0;
     while (job < depth && (int)blockIdx.x >= A.wg_begin[job + 1]) ++job;
-    if (BHN_DBG(A.debug >> 2) && (A.debug >> 2) - 1 != job) return;
-#ifdef BHN_T8_ONLY_JOB          // measurement builds: only this job of the 8-bit tape's dW kernel runs (the release build has no run-time switches)
-    if (Pol::TAPE8 && job != BHN_T8_ONLY_JOB) return;
-#endif
     if constexpr (Pol::ELEM_BYTES == 2) {           // bf16: software-pipelined bodies; the output layer rides on job depth-1
         const bool out_skip = (A.f.skip_mask >> depth) & 1;             // odd depths with do_skip
         if (job == depth) {                                               // (depth < 3 only)
@@ -2151,28 +1996,12 @@ int fused_fill_args(const bhn_model *m, int32_t mode, const void *packed, const 
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-#ifndef BHN_DEBUG
-static constexpr int g_bwd_stages = 7, g_bwd_debug = 0;
-#else
-// measurement build only: bit 0 chain kernel, bit 1 dW kernel, bit 2 reduce kernel (default all)
-static thread_local int g_bwd_stages = 7;
-static thread_local int g_bwd_debug = 0;
-static int dbg_env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
-extern "C" int bhn_debug_set_bwd_stages(int32_t mask) {
-    g_bwd_stages = mask & 7;
-    g_bwd_debug = (mask >> 3) & 0xFFF;    // bit 12: ring-step time stamps of one tile (tools/dbg_chain_steps.py); bit 3: dW kernel without MFMA work, bit 4: without tape loads,
-                                         // bits 5-8: run only dW job (value-1); bit 9: emit without global stores; bit 10: no emit
-    return BHN_OK;
-}
-#endif
-
 // the delta chain accumulates dW_0 itself (TapeLayout::ga0_chain): bf16, one gA_0 tile per wave (width 256),
 // depth >= 3 (the chain then starts from the folded W_out image: bhn_folds_wout)
 template <int W, class Pol>
 static constexpr bool ga0_chain_ok(int depth) {
     // (not the 8-bit tape mode: its delta chain has 16 registers less to spare and spills with the consumer's state)
-    return BHN_GA0_CHAIN != 0 && Pol::ELEM_BYTES == 2 && !Pol::TAPE8 &&
-           W / 32 == Pol::NWAVES && depth >= 3;
+    return Pol::ELEM_BYTES == 2 && !Pol::TAPE8 && W / 32 == Pol::NWAVES && depth >= 3;
 }
 
 template <int W, class Pol>
@@ -2183,17 +2012,16 @@ static void tape_layout(int depth, bool layer1_takes_enc, bool last_takes_enc, l
     t->drop_h1 = Pol::ELEM_BYTES == 2 && depth >= 2 && !layer1_takes_enc;
     long long off = 0;
     const long long per_tensor = NQ * BG::MT * (long long)BG::TAPE_TILE;
-    // (lbits / drop_hd: decided before the h tensors are laid out)
-    const bool lbits = BHN_LBITS != 0 && Pol::ELEM_BYTES == 2 && !Pol::TAPE8 && bhn_folds_wout(Pol::MODE, depth) && !last_takes_enc;
-    t->drop_hd = BHN_DROP_HD != 0 && lbits;
+    // (h_depth stays on this tape.  Recording only its relu bits -- TapeLayout::drop_hd, as the fused 4x128 path does -- moved 9 GB
+    //  less per step at 4x256 (48.4 -> 39.5) and was NOT faster: the dW kernel is issue-bound per group, not HBM-bound, and every
+    //  variant of the forward's change cost its ring steps 3 %, profiles/r5_ab_drop_hd_width256.txt)
     for (int l = 1; l <= depth; ++l) {
-        if ((l == 1 && t->drop_h1) || (l == depth && t->drop_hd)) { t->h_off[l] = -1; continue; }
+        if (l == 1 && t->drop_h1) { t->h_off[l] = -1; continue; }
         t->h_off[l] = off; off += per_tensor;
     }
     if (t->drop_h1) { t->encp_off = off; off += NQ * (long long)BG::TILE_BYTES; }
     t->drop_ga = bhn_folds_wout(Pol::MODE, depth);
     t->ga0_chain = ga0_chain_ok<W, Pol>(depth) && t->drop_ga;
-    t->lbits = BHN_LBITS != 0 && Pol::ELEM_BYTES == 2 && !Pol::TAPE8 && t->drop_ga && !last_takes_enc;
     for (int l = 0; l < depth; ++l) {
         if ((l == depth - 1 && t->drop_ga) || (l == 0 && t->ga0_chain)) { t->ga_off[l] = -1; continue; }
         t->ga_off[l] = off; off += per_tensor;
@@ -2210,7 +2038,6 @@ static void tape_layout(int depth, bool layer1_takes_enc, bool last_takes_enc, l
     t->mask_off = off; off += NQ * (long long)depth * ((BG::MT + 1) / 2) * 256;
     t->e_off = off; off += NQ * 128;
     off = (long long)align_up((size_t)off + 1024, 256);          // +1 KiB: the last dout piece is DMA'd as a full KiB
-    if (t->drop_hd) { t->scratch_off = off; off += 4096 * 64; }  // where the ring kernels' place-holder stores go (chain_kernel, no_hd): 4096 lines
     t->total = off;
 }
 
@@ -2265,14 +2092,7 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
     mode = bhn_norm_mode(mode);
     constexpr size_t t8_bytes = Pol::TAPE8 ? 256 : 0;                   // the 8-bit tape's state block, in front of the tape
     const int ncu = bhn_num_cus(device);
-#ifdef BHN_DEBUG
-    static const int grid_override = dbg_env_int("BHN_DEBUG_DW_GRID", 0);
-    static const int job1_w = dbg_env_int("BHN_DEBUG_JOB1_W", BHN_JOB1_W), jobl_w = dbg_env_int("BHN_DEBUG_JOBL_W", BHN_JOBL_W);
-    static const int joblb_w = dbg_env_int("BHN_DEBUG_JOBLB_W", BHN_JOBLB_W);
-#else
-    constexpr int grid_override = 0, job1_w = BHN_JOB1_W, jobl_w = BHN_JOBL_W, joblb_w = BHN_JOBLB_W;
-#endif
-    const int grid_dw = grid_override > 0 ? grid_override : ncu;        // one dW workgroup per CU
+    const int grid_dw = ncu;                                            // one dW workgroup per CU
     MlpShape s;
     {
         const int rcq = bhn_mlp_shape(m, &s);
@@ -2364,7 +2184,7 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
     // dW jobs: every layer gets workgroups in proportion to the tiles it streams per 32-point group (A + B), with
     // measured corrections for the two jobs that compute more than they stream (layer 1: recompute of h_1; layer depth-1:
     // rebuild of gA, output row).  Balancing the jobs so that each takes the same time when it runs ALONE
-    // (tools/dbg_dw.py) measured slower (5.0 vs 4.75 ms): run together they share the HBM stream, and the light
+    // (round 2) measured slower (5.0 vs 4.75 ms): run together they share the HBM stream, and the light
     // layer-0 job finishing early leaves its bandwidth to the others.
     {
         double work[BHN_MAX_LAYERS + 1], tot = 0;
@@ -2372,13 +2192,11 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
         for (int l = 0; l <= depth; ++l) {
             const int mtA = (l == depth) ? 0 : BG::MT;
             int nB = (l >= 1 ? BG::MT : 0) + ((l == 0 || s.skip_in[l]) ? 1 : 0);
-            if (l == 1 && t1.drop_h1) nB = job1_w * BG::MT / 8;   // reads only the encoded inputs instead of h_1 but has the
+            if (l == 1 && t1.drop_h1) nB = JOB1_W * BG::MT / 8;   // reads only the encoded inputs instead of h_1 but has the
                                                                   // same MFMA work + the recompute: not byte-bound any more
             work[l] = (double)(mtA + nB) + 0.5;
             // + the rebuild of gA and the output row (8-bit tape: the byte masks of that job are its long pole; 12 measured 2-3 % faster than 8)
-            if (l == depth - 1 && t1.drop_ga) work[l] += (Pol::TAPE8 ? 12 : jobl_w) * BG::MT / 8.0;
-            // LBITS: that job streams 1 KiB of relu bits in place of its MT A tiles
-            if (l == depth - 1 && t1.lbits) work[l] = (double)nB + 1.0 + joblb_w * BG::MT / 8.0;
+            if (l == depth - 1 && t1.drop_ga) work[l] += (Pol::TAPE8 ? 12 : JOBL_W) * BG::MT / 8.0;
             if constexpr (Pol::ELEM_BYTES == 4) {
                 // f32: the jobs are MFMA-bound (a 32x32x2 MFMA is 64 cycles; one 32x32 tile product over a 32-point
                 // group = 16 of them = 0.55 us at the observed 1.87 GHz) unless they stream more than ~34 GB/s per
@@ -2417,16 +2235,13 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
     size_t lds_dw = (size_t)BG::NBUF * BG::GROUP_BYTES + (t1.drop_h1 ? (size_t)2 * BG::MT * Pol::FRAG_BYTES + W * 4 : 0);
     if (t1.drop_ga && (size_t)BG::NBUF * BG::GROUP_BYTES_LAST2 > lds_dw) lds_dw = (size_t)BG::NBUF * BG::GROUP_BYTES_LAST2;
     if constexpr (Pol::TAPE8) {          // the 8-bit jobs other than layer 1's run a deeper ring of smaller group images (dw_body2: NB)
-        const size_t deep = (size_t)BHN_T8_NBUF * (2 * BG::MT * BG::TAPE_TILE + BG::TILE_BYTES + 1024);
+        const size_t deep = (size_t)T8_NBUF * (2 * BG::MT * BG::TAPE_TILE + BG::TILE_BYTES + 1024);
         if (deep > lds_dw) lds_dw = deep;
     }
-#ifndef BHN_RESIDENT
-#define BHN_RESIDENT 1           // 0: never keep the weight images resident in LDS (A/B builds)
-#endif
     // small networks: the training forward / the delta chain keep their whole chunk sequence in LDS and run without the
     // per-chunk barrier (ResidentRing), each when its own sequence fits
     const size_t res_fwd = (size_t)PK::fwd_chunks(depth) * PK::CHUNK_BYTES + lds_fixed, res_chn = (size_t)PK::bwd_chunks(depth) * PK::CHUNK_BYTES + lds_fixed;
-    constexpr bool CAN_RES = BHN_RESIDENT != 0 && W <= 128 && BHN_CHAIN_STAMPS == 0;     // (width 256: no second instantiation)
+    constexpr bool CAN_RES = W <= 128;                                  // (width 256: no second instantiation)
     const bool rf = CAN_RES && res_fwd <= 160 * 1024, rch = CAN_RES && res_chn <= 160 * 1024;
     auto k_fwd = rf ? chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, CAN_RES> : chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, false>;
     // (x12: the resident image + the ray-sum scratch of 12 groups: 154 KB at four Stokes planes)
@@ -2437,12 +2252,14 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
             k_fwd = chain_kernel<W, FPol, 3, MODE_FWD_TRAIN, CAN_RES>;
         }
     }
+    // (fused128: only the resident training forward records the relu bits of the last hidden layer in place of its h tiles, chain_kernel CAN_HD)
+    BHN_CHECK_ARG(!f128 || x12 || rf, "internal: the fused 4x128 training forward needs its weights resident (%zu bytes)", res_fwd);
     const unsigned nthr_fwd = (unsigned)nwf * 64u;
     constexpr bool CAN_GA0C = ga0_chain_ok<W, Pol>(3);                // (compile-time part of the condition: which widths instantiate it)
     auto k_chn = rch ? chain_kernel<W, Pol, 3, MODE_CHAIN, CAN_RES> : chain_kernel<W, Pol, 3, MODE_CHAIN, false>;
     if (ga0c) k_chn = chain_kernel<W, Pol, 3, MODE_CHAIN, false, CAN_GA0C>;
-    // ga0_chain: a ring of BHN_GA0C_DIST + 1 buffers of the KS fragments the chain streams, the fixed part, 4 staging images of one tile per wave
-    const size_t lds_ga0c = (size_t)(BHN_GA0C_DIST + 1) * PK::KS * Pol::FRAG_BYTES + lds_fixed + (size_t)4 * Pol::NWAVES * BG::TILE_BYTES;
+    // ga0_chain: a ring of GA0C_DIST + 1 buffers of the KS fragments the chain streams, the fixed part, 4 staging images of one tile per wave
+    const size_t lds_ga0c = (size_t)(GA0C_DIST + 1) * PK::KS * Pol::FRAG_BYTES + lds_fixed + (size_t)4 * Pol::NWAVES * BG::TILE_BYTES;
     const size_t lds_fwd = x12 ? res_fwd_x : rf ? res_fwd : (EncBlock<W, Pol>::ON ? lds_fwd_encr : lds_taped), lds_chn = ga0c ? lds_ga0c : rch ? res_chn : lds_taped;
     auto kdw = dw_kernel<W, Pol>;
     static DeviceOnce once;                 // per template instantiation and device
@@ -2480,12 +2297,6 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
         A.f.total_tiles = (long long)A.f.tiles_per_frame * nb;
         layout(A.f.total_tiles * nwf, &A.t);
         A.accumulate = pass > 0;
-        A.debug = g_bwd_debug;
-#ifdef BHN_DEBUG
-        A.ts_buf = (g_bwd_debug & 512) ? reinterpret_cast<long long *>(bhn_debug_buffer()) : nullptr;
-        A.wrap = dbg_env_int("BHN_DEBUG_WRAP", 0);
-        A.policy = dbg_env_int("BHN_DEBUG_POLICY", 0);
-#endif
         // (ga0_chain: later passes ACCUMULATE onto the dW_0 slabs of the first: never more workgroups than the first pass had)
         const long long grid = bhn_balanced_grid(A.f.total_tiles, (pass > 0 && A.n_chain_wg > 0 && A.n_chain_wg < ncu) ? A.n_chain_wg : ncu);
         if (pass == 0) A.n_chain_wg = (int)grid;
@@ -2513,34 +2324,32 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
             BHN_HIP(mark(2));
             continue;
         }
-        if (g_bwd_stages & 1) {
-            if (what == RUN_RECOMPUTE) {     // forward again (tape only: A.f.images is null), then the chain
-                hipLaunchKernelGGL(k_fwd, dim3((unsigned)grid), dim3(nthr_fwd), lds_fwd, st, A);
+        if (what == RUN_RECOMPUTE) {     // forward again (tape only: A.f.images is null), then the chain
+            hipLaunchKernelGGL(k_fwd, dim3((unsigned)grid), dim3(nthr_fwd), lds_fwd, st, A);
+            BHN_HIP(hipGetLastError());
+        }
+        if constexpr (Pol::TAPE8) {
+            if (t8_cal && pass == 0) {
+                // calibration: the delta chain once with nothing limited (its tape output is overwritten below); the
+                // ratios of its |gA_l| maxima to |dimages|max give this call's scales
+                hipLaunchKernelGGL(t8_open_kernel, dim3(1), dim3(64), 0, st, A.t8);
+                hipLaunchKernelGGL(k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), lds_chn, st, A);
+                hipLaunchKernelGGL(t8_update_kernel, dim3(1), dim3(64), 0, st, A.t8, depth);
+                hipLaunchKernelGGL(t8_prepare_kernel, dim3(1), dim3(64), 0, st, A.t8, depth, 0);
                 BHN_HIP(hipGetLastError());
             }
-            if constexpr (Pol::TAPE8) {
-                if (t8_cal && pass == 0) {
-                    // calibration: the delta chain once with nothing limited (its tape output is overwritten below); the
-                    // ratios of its |gA_l| maxima to |dimages|max give this call's scales
-                    hipLaunchKernelGGL(t8_open_kernel, dim3(1), dim3(64), 0, st, A.t8);
-                    hipLaunchKernelGGL(k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), lds_chn, st, A);
-                    hipLaunchKernelGGL(t8_update_kernel, dim3(1), dim3(64), 0, st, A.t8, depth);
-                    hipLaunchKernelGGL(t8_prepare_kernel, dim3(1), dim3(64), 0, st, A.t8, depth, 0);
-                    BHN_HIP(hipGetLastError());
-                }
-            }
-            hipLaunchKernelGGL(k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), lds_chn, st, A);
         }
+        hipLaunchKernelGGL(k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), lds_chn, st, A);
         BHN_HIP(hipGetLastError());
         BHN_HIP(mark(1));
-        if (g_bwd_stages & 2) hipLaunchKernelGGL(kdw, dim3((unsigned)A.wg_begin[depth + 1]), dim3(Pol::NTHREADS), lds_dw, st, A);
+        hipLaunchKernelGGL(kdw, dim3((unsigned)A.wg_begin[depth + 1]), dim3(Pol::NTHREADS), lds_dw, st, A);
         BHN_HIP(hipGetLastError());
         BHN_HIP(mark(2));
     }
     if (what != RUN_FWD_TRAIN && f128) {
         const int rcr = reduce128_launch(A, depth, nslabs128, st);
         if (rcr != BHN_OK) return rcr;
-    } else if (what != RUN_FWD_TRAIN && (g_bwd_stages & 4)) {
+    } else if (what != RUN_FWD_TRAIN) {
         A.chain_step = 1;
         if (ga0c && A.n_chain_wg > 16) {
             const int parts = 16;

@@ -34,17 +34,11 @@ struct PolBF16 {
     static constexpr int NWAVES = 8;            // 2 waves per SIMD, <=256 VGPRs each
     static constexpr int NTHREADS = NWAVES * 64;
     static constexpr int WPE = 2;               // waves per SIMD the kernels are built for (register budget 512 / WPE)
-#ifndef BHN_FWD_DIST
-#define BHN_FWD_DIST 4           // weight chunks in flight in the inference forward (6 measured 6 % slower here)
-#endif
-    static constexpr int FWD_DIST = BHN_FWD_DIST;
+    static constexpr int FWD_DIST = 4;          // weight chunks in flight in the inference forward (6 measured 6 % slower here)
     static constexpr int ELEM_BYTES = 2;
     static constexpr int FRAG_BYTES = 1024;     // 64 lanes x 8 bf16
     static constexpr bool TAPE8 = false;        // (PolBF16T8: the h / gA tape tiles in 8 bits)
-#ifndef BHN_LDS_PF
-#define BHN_LDS_PF 4
-#endif
-    static constexpr int LDS_PREFETCH = BHN_LDS_PF;      // A fragments in flight + 1 (ring_step); 6 / 8 measured no faster
+    static constexpr int LDS_PREFETCH = 4;      // A fragments in flight + 1 (ring_step); 6 / 8 measured no faster
     static constexpr bool PHASE_LAG = false;    // RingState LAG: measured 5 % slower in the render kernel, off
     using frag = bf16x8;
     static DEVI frag zero() { frag f; for (int j = 0; j < 8; ++j) f[j] = (__bf16)0.f; return f; }
@@ -422,7 +416,6 @@ DEVI void point_prologue(const FusedArgs &a, const PointIn &in, typename Pol::fr
     // sin(2^i u_k) on half 0 / cos(2^i u_k) on half 1 (n = 3 + 3 i + k, i < deg); bhn_pack_weights puts the reference's rows
     // [u | sin block | cos block], network.py:118-122, on these slots, unused slots meet zero weight rows.  The degree is a
     // run-time argument: a wave-uniform branch per octave.
-#if BHN_ENC_PAIRS
     float reg[16];
 #pragma unroll
     for (int n = 0; n < 16; ++n) reg[n] = 0.f;
@@ -459,40 +452,6 @@ DEVI void point_prologue(const FusedArgs &a, const PointIn &in, typename Pol::fr
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j) Pol::set(enc[ks], j, reg[8 * ks + j]);
-#else
-    float feat[BHN_ENC_PAD];
-#pragma unroll
-    for (int q = 0; q < BHN_ENC_PAD; ++q) feat[q] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) feat[k] = u[k];
-#pragma unroll
-    for (int i = 0; i < BHN_DEG_MAX; ++i) {
-        if (i < a.deg) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float arg = u[k] * (float)(1 << i);
-                float sv, cv;
-                if (Pol::FAST_TRIG) {
-                    const float rev = __builtin_amdgcn_fractf(arg * 0.15915494309189535f);
-                    sv = __builtin_amdgcn_sinf(rev);
-                    cv = __builtin_amdgcn_cosf(rev);
-                } else {
-                    sincosf(arg, &sv, &cv);
-                }
-                feat[3 + 3 * i + k] = sv;
-                feat[3 + 3 * BHN_DEG_MAX + 3 * i + k] = cv;
-            }
-        }
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v0 = feat[16 * ks + phi16(0, j)];
-            const float v1 = feat[16 * ks + phi16(1, j)];
-            Pol::set(enc[ks], j, h ? v1 : v0);
-        }
-#endif
 }
 
 // bias rows of output tile m as the initial accumulator: acc[r] = bias[32m + (r&3)+8(r>>2)+4h]
@@ -633,24 +592,6 @@ struct PackPost {
     DEVI void finish() {}                       // (behind the last k-step of the ring step)
 };
 
-// EXPERIMENT (-DBHN_PRIO_MODE=n, round 3): issue priority of the two waves of a SIMD inside a ring step.  With equal
-// priority the older wave of a SIMD wins every arbitration: per-step stamps show it finishing its MFMAs ~500 cycles before
-// its partner and then waiting at the barrier.  1: static s_setprio 1 for waves NW/2.. (set once, RingState::start);
-// 2 / 3 / 4: the two halves swap priority every 1 / 2 / 4 k-steps.
-#ifndef BHN_PRIO_MODE
-#define BHN_PRIO_MODE 0
-#endif
-DEVI void prio_flip(int t, int wvu) {
-    if constexpr (BHN_PRIO_MODE >= 2) {
-        constexpr int P = BHN_PRIO_MODE == 2 ? 1 : BHN_PRIO_MODE == 3 ? 2 : 4;
-        if (t % P == 0) {
-            const bool up = ((t / P) & 1) != 0;
-            if (wvu >= 4) { if (up) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-            else { if (up) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
-        }
-    }
-}
-
 // One output tile of a hidden / output / delta-chain layer: acc = ap.bias + sum_ks A[ks] . src[ks] (+ the enc
 // block when with_enc), A streamed from the ring chunk `ch`; reads the head of the next chunk `chn` and the bias
 // rows `bias_next` of the next tile before returning (both consumed after the barrier).
@@ -681,7 +622,6 @@ DEVI f32x16 ring_step(const char *ch, const char *chn, APipe<Pol> &ap, const typ
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < KS; ++t) {
-        prio_flip(t, dma.wvu);
         a[(t + PF - 1) % PF] = stream_frag<Pol, NF>(ch, chn, t + PF - 1, lane);
         if (do_mma) acc = Pol::mma(a[t % PF], src[t], acc);
         if (do_post && KS >= 16) post.at(t);
@@ -921,7 +861,6 @@ struct RingState {
         dbg = dbg_; cur = 0; issue_c = 0; lag = LAG ? lag_ : 0; ts = nullptr;
         o_cur = 0; o_nxt = CBL; o_prv = (NB - 1) * CBL;
         wvu = opaque(__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
-        if constexpr (BHN_PRIO_MODE == 1) { if (wvu >= 4) __builtin_amdgcn_s_setprio(1); }
 #pragma unroll
         for (int j = 0; j < DIST; ++j) RG::issue(DmaJob{true, next_src(), ring + j * CBL, rs, wvu, rsa});
         RG::template wait_younger<RG::PPW * (DIST - 2)>();

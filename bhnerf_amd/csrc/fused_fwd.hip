@@ -140,8 +140,9 @@ extern "C" int bhn_pack_weights(const bhn_model *m, int32_t mode, const float *p
 // ---------------------------------------------------------------------------------------------
 // forward kernel
 // ---------------------------------------------------------------------------------------------
-// DBG: measurement build (bit 128: per-wave time stamps [compute done, barrier passed] of the ring steps of one tile); (tools/dbg_fwd_ablate.py): a.debug bits knock out one cost at a time -- 1 hidden/output MFMAs,
-// 2 relu+pack, 4 weight DMA + its waits, 8 barriers, 16 posenc trig, 32 epilogue.  Results are then meaningless.
+// DBG: measurement build of the width-128 kernels (bit 128: per-wave time stamps [compute done, barrier passed] of the ring steps of one
+// tile); (tools/dbg_fwd128_ablate.py): a.debug bits knock out one cost at a time -- 1 hidden/output MFMAs, 2 relu+pack, 4 weight DMA +
+// its waits, 8 barriers, 16 posenc trig, 32 epilogue.  Results are then meaningless.
 // RES: the whole weight image resident in LDS (ResidentRing: no DMA, no per-chunk barrier), when it fits
 template <int W, class Pol, int DEG, bool RENDER, bool DBG = false, bool RES = false>
 __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(Pol::WPE, Pol::WPE))) void fused_fwd_kernel(FusedArgs a) {
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
 
     // weight ring (LDS-DMA), software-pipelined steps: fused_common.h "Software-pipelined ring steps"
     RS rs;
-    rs.start(ring, a.packed + a.fwd_off, PK::fwd_chunks(a.depth), nullptr, 0, dbg, (wv >= Pol::NWAVES / 2 && !(a.debug & 64)) ? 1 : 0);
+    rs.start(ring, a.packed + a.fwd_off, PK::fwd_chunks(a.depth), nullptr, 0, dbg, wv >= Pol::NWAVES / 2 ? 1 : 0);
     if (rs.lag) rs.idle_step();
     APipe<Pol> ap;
     ap.prime(rs.ch(), bias_lds);
@@ -283,21 +284,15 @@ int fused_fill_args(const bhn_model *m, int32_t mode, const void *packed, const 
     a->fd_tpf = FastDiv::make((unsigned)a->tiles_per_frame);
     a->fd_G = FastDiv::make((unsigned)a->G);
     a->ray_direct = a->ray_idx ? (geom->ray_span == 1 || geom->ray_span == 2) : (a->G <= 33 || (a->G <= 64 && a->G % 32 == 0));
-#ifdef BHN_FORCE_RAY_DIRECT          // measurement build: per-wave atomics whatever the ray layout (pixel sums then depend on the arrival order)
-    a->ray_direct = 1;
-#endif
     return BHN_OK;
 }
 
 
-#ifndef BHN_RESIDENT
-#define BHN_RESIDENT 1           // 0: never keep the weight image resident in LDS (A/B builds)
-#endif
 template <int W, class Pol, bool RENDER, bool DBG = false, bool RES = false>
 static int launch_fwd_w(FusedArgs &a, hipStream_t st) {
     using PK = Pack<W, Pol>;
     const size_t lds_fixed = (size_t)(a.depth + 1) * W * 4 + RaySum<Pol::NWAVES>::bytes(a.Sx);
-    if constexpr (!RES && !DBG && W <= 128 && BHN_RESIDENT != 0 && Pol::ELEM_BYTES == 2) {     // (f32, one wave per SIMD: measured 11 % slower resident)
+    if constexpr (!RES && !DBG && W <= 128 && Pol::ELEM_BYTES == 2) {     // (f32, one wave per SIMD: measured 11 % slower resident)
         // small networks: all chunks of the forward image resident in LDS, waves run without the per-chunk barrier
         if ((size_t)PK::fwd_chunks(a.depth) * PK::CHUNK_BYTES + lds_fixed <= 160 * 1024) return launch_fwd_w<W, Pol, RENDER, DBG, true>(a, st);
     }
@@ -351,14 +346,14 @@ static int launch_fwd(FusedArgs &a, int width, hipStream_t st) {
 
 #ifdef BHN_DEBUG
 // Measurement build only (make debug -> libbhnerf_hip_dbg.so, include/bhnerf_hip_debug.h): low 4 bits 1 = production
-// kernel (default), 3 = ablation build of the 4x256 render kernel with the flags of fused_fwd_kernel<DBG> in bits 4.. .
+// kernel (default), 3 = ablation build of the width-128 render kernel with the flags of fused_fwd_kernel<DBG> in bits 4.. .
 static thread_local int g_fwd_variant = 1;
 extern "C" int bhn_debug_set_fwd_variant(int32_t v) {
     g_fwd_variant = v;
     return BHN_OK;
 }
 static void *g_dbg_buf = nullptr;
-void *bhn_debug_buffer() {        // 4 KiB device scratch of the measurement builds (time stamps)
+static void *bhn_debug_buffer() {        // 4 KiB device scratch of the measurement builds (time stamps)
     if (!g_dbg_buf) {
         if (hipMalloc(&g_dbg_buf, 4096) != hipSuccess) return nullptr;
         (void)hipMemset(g_dbg_buf, 0, 4096);
@@ -403,14 +398,7 @@ extern "C" int bhn_render_fwd(const bhn_model *m, int32_t mode, const void *pack
     a.images = images;
     BHN_HIP(hipMemsetAsync(images, 0, sizeof(float) * (size_t)a.B * a.Sx * a.R, (hipStream_t)stream));
 #ifdef BHN_DEBUG
-    a.debug = (g_fwd_variant >> 4) & 64;                                       // bit 64: no phase lag (A/B measurements)
-    if (mode == BHN_BF16 && s.width == 256 && (g_fwd_variant & 15) == 3) {     // ablation build, see fused_fwd_kernel
-        a.debug = g_fwd_variant >> 4;                                          // includes bit 64
-        a.emission = reinterpret_cast<float *>(bhn_debug_buffer());
-        BHN_CHECK_ARG(a.emission, "no debug buffer");
-        return launch_fwd_w<256, PolBF16, true, true>(a, (hipStream_t)stream);
-    }
-    if (mode == BHN_BF16 && s.width == 128 && (g_fwd_variant & 15) == 3) {     // round 6: the same ablation flags on the resident-weights kernel of width 128
+    if (mode == BHN_BF16 && s.width == 128 && (g_fwd_variant & 15) == 3) {     // ablation build of the resident-weights kernel, see fused_fwd_kernel
         a.debug = g_fwd_variant >> 4;
         a.emission = reinterpret_cast<float *>(bhn_debug_buffer());
         BHN_CHECK_ARG(a.emission, "no debug buffer");

@@ -1,8 +1,7 @@
-"""Energy budget of the training step (round 4): every kernel of the step, and isolated parts of the dW
-kernel (debug build), run back to back for S seconds each while tools/smi_sample.py samples the board beside it; the
-windows are joined with the telemetry afterwards (mode `join`).
+"""Energy budget of the training step (round 4): every kernel of the step run back to back for S seconds
+each while tools/smi_sample.py samples the board beside it; the windows are joined with the telemetry afterwards (mode `join`).
 
-    python3 tools/energy_rows.py run <seconds> [width]  >> rows.txt        (release or debug library via BHNERF_HIP_LIB)
+    python3 tools/energy_rows.py run <seconds> [width]  >> rows.txt
     python3 tools/energy_rows.py join telemetry.txt rows.txt [rows2.txt ...]
 
 Row format (same as tools/energy_bench.hip / step_bench.hip): name, `unix t0 .. t1`, launches, ms each."""
@@ -24,8 +23,6 @@ def run(sec, width):
     flat = eng.flatten(network.MLP(4, width).init(1, 21)); eng.pack(flat)
     tM0 = engine.frame_offsets(np.linspace(0, 1, B), 0.0, geo['t_injection'], constants.GM_c3('hr'), dev)
     dimg = torch.rand((B, 1, geom.R), device=dev) * 1e-3
-    lib = _hip.lib()
-    dbg = hasattr(lib, 'bhn_debug_set_bwd_stages') and 'dbg' in os.environ.get('BHNERF_HIP_LIB', '')
     pts = B * geom.P
 
     def loop(name, fn, per_launch=1):
@@ -43,20 +40,13 @@ def run(sec, width):
         print('%-28s unix %.1f .. %.1f  %4d launches %8.3f ms each  width %d  points %d' % (name, t0, t1, n, ms / n, width, pts), flush=True)
 
     eng.render_train(geom, tM0); eng.render_bwd_tape(geom, tM0, dimg)
-    if not dbg:
-        loop('inference_fwd', lambda: eng.render(geom, tM0))
-        loop('train_fwd', lambda: eng.render_train(geom, tM0))
-        loop('bwd(chain+dw+reduce)', lambda: eng.render_bwd_tape(geom, tM0, dimg))
+    loop('inference_fwd', lambda: eng.render(geom, tM0))
+    loop('train_fwd', lambda: eng.render_train(geom, tM0))
+    loop('bwd(chain+dw+reduce)', lambda: eng.render_bwd_tape(geom, tM0, dimg))
 
-        def step():
-            eng.render_train(geom, tM0); eng.render_bwd_tape(geom, tM0, dimg)
-        loop('fwd+bwd', step)
-    else:
-        rt = lambda: eng.render_bwd_tape(geom, tM0, dimg)
-        for name, mask in [('chain_only', 1), ('dw_full', 2), ('dw_stream_only(no mfma)', 2 | 8), ('dw_compute_only(no loads)', 2 | 16)]:
-            lib.bhn_debug_set_bwd_stages(mask)
-            loop(name, rt)
-        lib.bhn_debug_set_bwd_stages(7)
+    def step():
+        eng.render_train(geom, tM0); eng.render_bwd_tape(geom, tM0, dimg)
+    loop('fwd+bwd', step)
 
 
 def join(tele, rows):

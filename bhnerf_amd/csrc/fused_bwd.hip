@@ -2400,6 +2400,7 @@ static int bwd_entry(int what, const bhn_model *m, int32_t mode, const void *pac
         BHN_CHECK_ARG(!ev, "per-kernel events are not available for posenc_deg > 4 / net_width > 256");
         if (what == RUN_FWD_TRAIN) {
             BHN_CHECK_ARG(images, "null pointer");
+            BHN_CHECK_ARG(workspace, "null workspace");            // (gen_forward: no workspace = the plain render)
             return gen_forward(true, m, mode, packed, geom, fr, images, (hipStream_t)stream, workspace, workspace_bytes);
         }
         return gen_backward(what == RUN_BWD_TAPE, m, mode, packed, geom, fr, dimages, dparams, workspace, workspace_bytes, (hipStream_t)stream);

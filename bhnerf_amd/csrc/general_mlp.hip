@@ -903,9 +903,16 @@ int gen_forward(bool render, const bhn_model *m, int32_t mode, const void *packe
     if (render) {
         A.f.images = out;
         BHN_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)A.f.B * A.f.Sx * A.f.R, st));
-        // the training forward records the tape when the workspace holds ALL of it (what bhn_render_bwd_tape then asks for);
-        // with a smaller workspace it is the plain render and the gradient comes from bhn_render_bwd, chunk by chunk
-        if (workspace && workspace_bytes >= gen_slab_bytes(A) + gen_tape_bytes(A, A.ntiles)) {
+        // the training forward (workspace given) records the tape of ALL frames, which bhn_render_bwd_tape then reads; a workspace
+        // that cannot hold slabs + that tape is refused, as on the fused paths -- a plain render here would leave the tape pair
+        // nothing to read (callers check engine.fits_tape first; with less workspace the gradient comes from bhn_render_bwd)
+        if (workspace) {
+            const size_t need = gen_slab_bytes(A) + gen_tape_bytes(A, A.ntiles);
+            if (workspace_bytes < need) {
+                bhn_set_error("workspace too small for the training forward's tape: %zu bytes given, %zu needed (slabs %zu + tape %zu)",
+                              workspace_bytes, need, gen_slab_bytes(A), gen_tape_bytes(A, A.ntiles));
+                return BHN_EWORKSPACE;
+            }
             A.tape = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + gen_slab_bytes(A));
             A.tape16 = reinterpret_cast<char *>(A.tape);
             return gen_launch_mlp<GEN_RECORD>(A, grid, st);

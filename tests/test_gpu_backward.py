@@ -323,9 +323,12 @@ def test_general_path_emission_and_workspace_chunks(dev, mode):
     assert eng2.workspace(B, geom.P_eff).numel() == small < eng.workspace(B, geom.P_eff).numel() and not eng2.fits_tape(B, geom.P_eff)
     g_chunks = eng2.render_bwd(geom, tM0, dimg)
     assert torch.allclose(g_chunks, g_rec, rtol=1e-5, atol=1e-6 * float(g_rec.abs().max()))
-    # the recorded-tape pair refuses a workspace that cannot hold the whole tape (as the fused paths do)
+    # the recorded-tape pair refuses a workspace that cannot hold the whole tape (as the fused paths do): EACH call on its own --
+    # the training forward must not fall back to a plain render that records nothing (its tape pair would then read garbage)
     with pytest.raises(_hip.HipError, match='workspace'):
-        eng2.render_train(geom, tM0); eng2.render_bwd_tape(geom, tM0, dimg)
+        eng2.render_train(geom, tM0)
+    with pytest.raises(_hip.HipError, match='workspace'):
+        eng2.render_bwd_tape(geom, tM0, dimg)
     # run to run: images and gradients of the general path are bitwise reproducible (8-group tiles, combined ray sums, slabs)
     assert torch.equal(eng.render(geom, tM0), img) and torch.equal(eng.render_train(geom, tM0), img)
     assert torch.equal(eng.render_bwd_tape(geom, tM0, dimg), g_tape)
@@ -337,6 +340,16 @@ def test_general_path_emission_and_workspace_chunks(dev, mode):
     _hip.check(call(small))
     assert torch.allclose(out, g_rec, rtol=1e-5, atol=1e-6 * float(g_rec.abs().max()))
     assert call(small - 4096) == 4 and b'workspace' in lib.bhn_last_error()          # BHN_EWORKSPACE
+    # ... and the training forward through the C ABI: a workspace one KiB short of slabs + the whole tape is BHN_EWORKSPACE, the
+    # exact size records (the size is what bhn_render_bwd_workspace_bytes reports for all B frames)
+    need = int(lib.bhn_render_bwd_workspace_bytes(C.byref(eng.model), eng.mode, B, geom.P_eff, 0))
+    wbig = torch.empty((need,), dtype=torch.uint8, device=dev)
+    imgs = torch.empty((B, geom.Sx, geom.R), dtype=torch.float32, device=dev)
+    train = lambda nbytes: lib.bhn_render_fwd_train(C.byref(eng.model), eng.mode, _hip.ptr(eng.packed), C.byref(gs), C.byref(fs), _hip.ptr(imgs),
+                                                    _hip.ptr(wbig), nbytes, _hip.stream_ptr(dev))
+    assert train(need - 1024) == 4 and b'workspace' in lib.bhn_last_error()          # BHN_EWORKSPACE, nothing launched
+    _hip.check(train(need))
+    assert torch.equal(imgs, img)
 
 
 @pytest.mark.parametrize('rows', [48, 47])

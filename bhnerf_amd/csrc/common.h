@@ -77,7 +77,7 @@ struct MlpShape {
 
 int bhn_mlp_shape(const bhn_model *m, MlpShape *s);   // validates, returns BHN_* code
 
-// general_mlp.hip: the f32 layer-by-layer path of the shapes the fused kernels are not built for (MlpShape::general)
+// general_mlp.hip: the layer-by-layer path (f32 or bf16 by mode) of the shapes the fused kernels are not built for (MlpShape::general)
 #define BHN_GEN_DEG_MAX 10     // 3 + 6 deg <= 63 encoded features
 #define BHN_GEN_WIDTH_MAX 512
 size_t gen_packed_bytes(const MlpShape &s, int32_t mode);

@@ -12,12 +12,13 @@
 //                 share of the tape through LDS; bias gradients come from a constant ones B-fragment.
 //                 One slab flush per workgroup at the end: no float atomics, deterministic.
 //   reduce_kernel sums the slabs of each layer's workgroups into the flat dparams (flax tree order).
+#include <climits>
 #include <utility>
 #include <type_traits>
 #include "fused_common.h"
 #include "bwd_common.h"
 
-// dW job weights (bwd_run), in B tiles at width 256, scaled with the width
+// dW job weights (dw_job_split), in B tiles at width 256, scaled with the width
 static constexpr int JOB1_W = 13;        // the layer-1 job (measured optimum)
 static constexpr int JOBL_W = 7;         // extra weight of the layer depth-1 job when it rebuilds gA_{depth-1} and carries the output row
                                          // (round 5, re-swept without the layer-0 job, profiles/r5_dw_job_weights.txt: 6-7 beat 8 by 1.2 % of the dW kernel)
@@ -656,7 +657,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     frag &d0 = m == 0 ? act[KS - 2] : next[2 * (m > 0 ? m - 1 : 0)];
                     frag &d1 = m == 0 ? act[KS - 1] : next[2 * (m > 0 ? m - 1 : 0) + 1];
                     const int widx = (pl_layer * MW + (pm >> 1)) * 64 + lane;
-                    // h_depth: relu bits only (drop_hd: fused128, whose training forward keeps its weights resident -- bwd_run checks
+                    // h_depth: relu bits only (drop_hd: fused128, whose training forward keeps its weights resident -- bwd_launch checks
                     // that; a ring kernel would have to keep the emission's stores, which the waits of the weight ring count (YS above))
                     constexpr bool CAN_HD = W == 128 && Pol::ELEM_BYTES == 2 && !T8;
                     const bool no_hd = CAN_HD && A.t.drop_hd && pl_layer == a.depth - 1;
@@ -2041,12 +2042,6 @@ static void tape_layout(int depth, bool layer1_takes_enc, bool last_takes_enc, l
     t->total = off;
 }
 
-template <int W, class Pol>
-static long long bytes_per_group(int depth) {
-    using BG = BwdGeom<W, Pol>;
-    return (long long)(2 * depth * BG::MT + 1) * BG::TILE_BYTES + 128;
-}
-
 // bhn_tape_info: the bytes of tape each kernel of the training step moves per 32-point group, from the SAME flags the layout
 // and the job table are built from (bench.py's `tape_stream` figures; round 5 re-derived them in Python and got depths != 4 wrong)
 template <int W, class Pol>
@@ -2078,101 +2073,282 @@ static void tape_traffic(const MlpShape &s, const TapeLayout &t, int64_t *o) {
     o[4] = (t.drop_h1 ? 1 : 0) | (t.drop_ga ? 2 : 0) | (t.ga0_chain ? 4 : 0) | (t.fused128 ? 8 : 0) | (t.drop_hd ? 16 : 0) | (t.lbits ? 32 : 0);
 }
 
-enum { RUN_QUERY = 0, RUN_RECOMPUTE = 1, RUN_FWD_TRAIN = 2, RUN_BWD_TAPE = 3, RUN_INFO = 4 };
+// ---- the plan: what the backward of one network runs, from its shape and the ray set's size.  Arithmetic only, no HIP call:
+// the workspace query, bhn_tape_info, bhn_render_bwd_tape_kernel_name_for and the launch all read it.
+static constexpr size_t T8_STATE_BYTES = 256;    // the 8-bit tape's state block (BwdArgs::t8), between the slabs and the tape
 
 template <int W, class Pol>
-static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom,
-                   const bhn_frames *fr, const float *dimages, float *images, float *dparams, void *workspace,
-                   size_t workspace_bytes, hipStream_t st, size_t *query_bytes, int query_B, long long query_P,
-                   int device, void *const *events = nullptr, int n_events = 0) {
-    using BG = BwdGeom<W, Pol>;
-    using PK = Pack<W, Pol>;
-    BHN_CHECK_DEVICE(device);
-    const bool t8_cal = Pol::TAPE8 && (mode & BHN_T8_CALIBRATE);
-    mode = bhn_norm_mode(mode);
-    constexpr size_t t8_bytes = Pol::TAPE8 ? 256 : 0;                   // the 8-bit tape's state block, in front of the tape
-    const int ncu = bhn_num_cus(device);
-    const int grid_dw = ncu;                                            // one dW workgroup per CU
-    MlpShape s;
-    {
-        const int rcq = bhn_mlp_shape(m, &s);
-        if (rcq != BHN_OK) return rcq;
-    }
+struct BwdPlan {
+    using Kernel = void (*)(BwdArgs);
+    int depth;
+    bool skip1, skip_last;          // skip-concat into layer 1 / into layer depth-1 (tape_layout)
     // width 128, bf16, depth 4 (the reference's default network): delta chain and weight gradients fused in one kernel, the
     // gradient accumulated on chip, a tape of h_l / enc / e only (fused_bwd128.hip)
-    const bool f128 = bwd128_supported(Pol::MODE, W, s.depth);
-    // (ga0_chain: + one dW_0 slab of MT tiles per delta-chain workgroup, behind the dW kernel's slabs)
-    const bool ga0c = !f128 && ga0_chain_ok<W, Pol>(s.depth) && bhn_folds_wout(Pol::MODE, s.depth);
-    const size_t slab_dw_bytes = align_up(f128 ? bwd128_slab_bytes(ncu) : (size_t)grid_dw * BG::SLAB_FLOATS * 4, 256);
-    const size_t slab_bytes = slab_dw_bytes + (ga0c ? align_up((size_t)ncu * BG::MT * 4096, 256) : 0);
-    auto layout = [&](long long NQ, TapeLayout *t) {
-        if (f128) bwd128_tape_layout(s.depth, NQ, t);
-        else tape_layout<W, Pol>(s.depth, s.depth >= 2 && s.skip_in[1], s.depth >= 2 && s.skip_in[s.depth - 1], NQ, t);
-    };
-    // the fused 4x128 path's training forward runs on 12-wave workgroups (PolBF16X, fused_common.h): 12 groups per tile
+    bool f128;
+    bool ga0c;                      // TapeLayout::ga0_chain: + one dW_0 slab of MT tiles per delta-chain workgroup, behind the dW slabs
+    int nwf;                        // 32-point groups per tile of the training forward (bhn_fwd_tile_groups)
+    bool x12;                       // nwf == 12: the fused 4x128 path's training forward on 12-wave workgroups (PolBF16X)
+    size_t slab_dw_bytes, slab_bytes, tape_off;    // workspace: dW slabs | dW_0 slabs | 8-bit tape state | tape from tape_off on
+    int wg_begin[BHN_MAX_LAYERS + 2];              // dW jobs on one workgroup per CU (BwdArgs::wg_begin)
+    size_t lds_fixed, lds_taped, lds_fwd, lds_chn, lds_dw, res_fwd;
+    bool rf, rch;                   // the training forward / the delta chain keep their whole chunk sequence in LDS (ResidentRing)
+    Kernel k_fwd, k_chn, kdw;
+    void layout(long long NQ, TapeLayout *t) const {
+        if (f128) bwd128_tape_layout(depth, NQ, t);
+        else tape_layout<W, Pol>(depth, skip1, skip_last, NQ, t);
+    }
+};
+
+// dW jobs: every layer gets workgroups in proportion to the tiles it streams per 32-point group (A + B), with
+// measured corrections for the two jobs that compute more than they stream (layer 1: recompute of h_1; layer depth-1:
+// rebuild of gA, output row).  Balancing the jobs so that each takes the same time when it runs ALONE
+// (round 2) measured slower (5.0 vs 4.75 ms): run together they share the HBM stream, and the light
+// layer-0 job finishing early leaves its bandwidth to the others.
+template <int W, class Pol>
+static void dw_job_split(const MlpShape &s, const TapeLayout &t, int grid_dw, int *wg_begin) {
+    using BG = BwdGeom<W, Pol>;
+    const int depth = s.depth;
+    double work[BHN_MAX_LAYERS + 1], tot = 0;
+    const int last_job = t.drop_ga ? depth - 1 : depth;        // drop_ga: the output row rides on layer depth-1's job
+    for (int l = 0; l <= depth; ++l) {
+        const int mtA = (l == depth) ? 0 : BG::MT;
+        int nB = (l >= 1 ? BG::MT : 0) + ((l == 0 || s.skip_in[l]) ? 1 : 0);
+        if (l == 1 && t.drop_h1) nB = JOB1_W * BG::MT / 8;    // reads only the encoded inputs instead of h_1 but has the
+                                                              // same MFMA work + the recompute: not byte-bound any more
+        work[l] = (double)(mtA + nB) + 0.5;
+        // + the rebuild of gA and the output row (8-bit tape: the byte masks of that job are its long pole; 12 measured 2-3 % faster than 8)
+        if (l == depth - 1 && t.drop_ga) work[l] += (Pol::TAPE8 ? 12 : JOBL_W) * BG::MT / 8.0;
+        if constexpr (Pol::ELEM_BYTES == 4) {
+            // f32: the jobs are MFMA-bound (a 32x32x2 MFMA is 64 cycles; one 32x32 tile product over a 32-point
+            // group = 16 of them = 0.55 us at the observed 1.87 GHz) unless they stream more than ~34 GB/s per
+            // workgroup (one 68 KB group in flight per ~2 us round trip = 0.075 tile products per KiB: measured 26 GB/s for the layer-0 job alone)
+            const int a_tiles = (l == depth) ? 1 : BG::MT;           // the output job's A operand is the dout tile
+            const int wrr = (l == depth) ? 1 : BG::WRR, wcc = Pol::NWAVES / wrr;
+            const double tp = (double)((a_tiles + wrr - 1) / wrr) * ((nB + wcc - 1) / wcc);
+            const double kib = (double)(a_tiles + nB) * BG::TILE_BYTES / 1024.0;
+            work[l] = (tp > 0.075 * kib ? tp : 0.075 * kib) + 0.1;
+        }
+        if (l > last_job) work[l] = 0;
+        if (t.ga0_chain && l == 0) work[l] = 0;                // dW_0 comes out of the delta chain: no layer-0 job
+        tot += work[l];
+    }
+    int used = 0;
+    wg_begin[0] = 0;
+    for (int l = 0; l <= depth; ++l) {
+        int n = (int)(grid_dw * work[l] / tot);
+        if (n < 1) n = 1;
+        if (l == last_job) n = grid_dw - used;
+        if (n < 1) n = 1;
+        if (l > last_job || (t.ga0_chain && l == 0)) n = 0;
+        used += n;
+        wg_begin[l + 1] = used;
+    }
+}
+
+// ncu: workgroups of the dW kernel (one per CU), of which the slab sizes follow; Sx: Stokes planes (the ray-sum scratch in LDS)
+template <int W, class Pol>
+static void bwd_plan(const MlpShape &s, long long groups_per_frame, int ncu, int Sx, BwdPlan<W, Pol> *p) {
+    using BG = BwdGeom<W, Pol>;
+    using PK = Pack<W, Pol>;
+    constexpr bool CAN_RES = W <= 128;                                  // (width 256: no second instantiation)
     constexpr bool CAN_X = W == 128 && Pol::ELEM_BYTES == 2 && !Pol::TAPE8;
     using FPol = std::conditional_t<CAN_X, PolBF16X, Pol>;
-    const bool x12 = CAN_X && f128 && bhn_fwd_w12(Pol::MODE, W, s.depth, what == RUN_QUERY ? (query_P + 31) / 32 : bhn_groups_per_frame(geom));
-    const int nwf = x12 ? FPol::NWAVES : Pol::NWAVES;
-    if (what == RUN_QUERY) {
-        // (the caller's P may be the dense point count of a ray set that is walked compacted, or the other way round: room for either tile size)
-        size_t need = 0;
-        for (int nw : {(int)Pol::NWAVES, CAN_X && f128 ? (int)FPol::NWAVES : (int)Pol::NWAVES}) {
-            const long long tiles = (query_P + nw * 32 - 1) / (nw * 32) * query_B;
-            TapeLayout t;
-            layout(tiles * nw, &t);
-            if ((size_t)t.total > need) need = (size_t)t.total;
-        }
-        *query_bytes = slab_bytes + t8_bytes + need;
+    constexpr bool CAN_GA0C = ga0_chain_ok<W, Pol>(3);                // (compile-time part of the condition: which widths instantiate it)
+    const int depth = s.depth;
+    p->depth = depth;
+    p->skip1 = depth >= 2 && s.skip_in[1];
+    p->skip_last = depth >= 2 && s.skip_in[depth - 1];
+    p->f128 = bwd128_supported(Pol::MODE, W, depth);
+    p->ga0c = !p->f128 && ga0_chain_ok<W, Pol>(depth) && bhn_folds_wout(Pol::MODE, depth);
+    p->nwf = bhn_fwd_tile_groups(Pol::MODE, W, depth, groups_per_frame);
+    p->x12 = CAN_X && p->nwf == FPol::NWAVES;
+    p->slab_dw_bytes = align_up(p->f128 ? bwd128_slab_bytes(ncu) : (size_t)ncu * BG::SLAB_FLOATS * 4, 256);
+    p->slab_bytes = p->slab_dw_bytes + (p->ga0c ? align_up((size_t)ncu * BG::MT * 4096, 256) : 0);
+    p->tape_off = p->slab_bytes + (Pol::TAPE8 ? T8_STATE_BYTES : 0);
+    TapeLayout t;
+    p->layout(1, &t);                                                   // (its flags do not depend on the tape's length)
+    dw_job_split<W, Pol>(s, t, ncu, p->wg_begin);
+    // ring + bias rows + zero row + output weights + identity fragments
+    p->lds_fixed = ((size_t)depth * W + 32) * 4 + 128 + W * 4 + (Pol::ELEM_BYTES == 2 ? 0 : 2 * Pol::FRAG_BYTES) + RaySum<Pol::NWAVES>::bytes(Sx);
+    p->lds_taped = (size_t)(BG::RING_DIST_TAPED + 1) * PK::CHUNK_BYTES + p->lds_fixed;
+    // training forward with the resident encoded-input block (EncBlock): ring buffers of the KS hidden fragments + the block
+    const size_t lds_fwd_encr = (size_t)(BG::RING_DIST_TAPED + 1) * PK::KS * Pol::FRAG_BYTES + p->lds_fixed + EncBlock<W, Pol>::BYTES;
+    p->lds_dw = (size_t)BG::NBUF * BG::GROUP_BYTES + (t.drop_h1 ? (size_t)2 * BG::MT * Pol::FRAG_BYTES + W * 4 : 0);
+    if (t.drop_ga && (size_t)BG::NBUF * BG::GROUP_BYTES_LAST2 > p->lds_dw) p->lds_dw = (size_t)BG::NBUF * BG::GROUP_BYTES_LAST2;
+    if constexpr (Pol::TAPE8) {          // the 8-bit jobs other than layer 1's run a deeper ring of smaller group images (dw_body2: NB)
+        const size_t deep = (size_t)T8_NBUF * (2 * BG::MT * BG::TAPE_TILE + BG::TILE_BYTES + 1024);
+        if (deep > p->lds_dw) p->lds_dw = deep;
+    }
+    // small networks: the training forward / the delta chain keep their whole chunk sequence in LDS and run without the
+    // per-chunk barrier (ResidentRing), each when its own sequence fits
+    p->res_fwd = (size_t)PK::fwd_chunks(depth) * PK::CHUNK_BYTES + p->lds_fixed;
+    const size_t res_chn = (size_t)PK::bwd_chunks(depth) * PK::CHUNK_BYTES + p->lds_fixed;
+    p->rf = CAN_RES && p->res_fwd <= 160 * 1024;
+    p->rch = CAN_RES && res_chn <= 160 * 1024;
+    // (x12: the resident image + the ray-sum scratch of 12 groups: 154 KB at four Stokes planes)
+    const size_t res_fwd_x = p->res_fwd - RaySum<Pol::NWAVES>::bytes(Sx) + RaySum<FPol::NWAVES>::bytes(Sx);
+    p->lds_fwd = p->x12 ? res_fwd_x : p->rf ? p->res_fwd : (EncBlock<W, Pol>::ON ? lds_fwd_encr : p->lds_taped);
+    // ga0_chain: a ring of GA0C_DIST + 1 buffers of the KS fragments the chain streams, the fixed part, 4 staging images of one tile per wave
+    const size_t lds_ga0c = (size_t)(GA0C_DIST + 1) * PK::KS * Pol::FRAG_BYTES + p->lds_fixed + (size_t)4 * Pol::NWAVES * BG::TILE_BYTES;
+    p->lds_chn = p->ga0c ? lds_ga0c : p->rch ? res_chn : p->lds_taped;
+    p->k_fwd = p->x12 ? chain_kernel<W, FPol, 3, MODE_FWD_TRAIN, CAN_RES>
+             : p->rf  ? chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, CAN_RES> : chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, false>;
+    p->k_chn = p->ga0c ? chain_kernel<W, Pol, 3, MODE_CHAIN, false, CAN_GA0C>
+             : p->rch  ? chain_kernel<W, Pol, 3, MODE_CHAIN, CAN_RES> : chain_kernel<W, Pol, 3, MODE_CHAIN, false>;
+    p->kdw = dw_kernel<W, Pol>;
+}
+
+// ---- which backward runs
+enum BwdPath { BWD_GENERAL, BWD_F32, BWD_BF16, BWD_BF16_T8 };
+
+// The path of a mode (BHN_F32, BHN_BF16, BHN_BF16_T8 [| BHN_T8_CALIBRATE]) on a network, or an error: shapes outside the fused
+// kernels take the general path (general_mlp.hip) in either arithmetic mode; the 8-bit tape kernels exist for the networks the
+// reference's own drivers use at width 256 only.
+static int bwd_path(int32_t mode, const MlpShape &s, BwdPath *path) {
+    const bool t8 = (mode & 0xff) == BHN_BF16_T8 && bhn_norm_mode(mode) == BHN_BF16;
+    BHN_CHECK_ARG(mode == BHN_F32 || mode == BHN_BF16 || t8, "bad mode %d", mode);
+    if (t8 && (s.general || s.width_true != 256 || s.depth < 3 || s.skip_in[s.depth])) {
+        bhn_set_error("BHN_BF16_T8 (8-bit tape) is built for net_width 256, net_depth >= 3, posenc_deg <= 4 and no skip-concat "
+                      "into the output layer (got %d x %d, posenc_deg %d); use BHN_BF16", s.depth, s.width_true, s.deg);
+        return BHN_EUNSUPPORTED;
+    }
+    *path = s.general ? BWD_GENERAL : t8 ? BWD_BF16_T8 : mode == BHN_BF16 ? BWD_BF16 : BWD_F32;
+    return BHN_OK;
+}
+
+// f(std::integral_constant<int, W>, Pol) for the kernels of a fused path (the 8-bit tape: width 256 only)
+template <class F>
+static int with_bwd_kernels(BwdPath path, int width, F &&f) {
+    if (path == BWD_BF16_T8) return f(std::integral_constant<int, 256>(), PolBF16T8());
+    return path == BWD_BF16 ? bhn_with_width<PolBF16>(width, f) : bhn_with_width<PolF32>(width, f);
+}
+
+// ---- the 8-bit tape's host steps (PolBF16T8; no-ops for every other policy): with its state block (T8_STATE_BYTES), the t8_*
+// kernels and PolBF16T8's terms in the plan, all the host code holds of it
+// before the passes: this call's tape scales, the stored ratios times the size of THIS d(loss)/d(images)
+template <class Pol>
+static int t8_scales(const BwdArgs &A, bool calibrate, const float *dimages, int depth, hipStream_t st) {
+    if constexpr (Pol::TAPE8) {
+        const long long npx = (long long)A.f.B * A.f.Sx * A.f.R;
+        // a calibrating call starts from a clean state block: the workspace may never have been used, and t8_update keeps
+        // a layer's OLD ratio when the chain saw only zeros there -- all-zero ratios fall back to scale 1 (t8_prepare)
+        if (calibrate) BHN_HIP(hipMemsetAsync(A.t8, 0, T8_STATE_BYTES, st));
+        hipLaunchKernelGGL(t8_dmax_kernel, dim3((unsigned)(npx >= 65536 ? 64 : (npx + 1023) / 1024)), dim3(1024), 0, st, A.t8, dimages, npx);
+        hipLaunchKernelGGL(t8_prepare_kernel, dim3(1), dim3(64), 0, st, A.t8, depth, 1);
+        BHN_HIP(hipGetLastError());
+    }
+    return BHN_OK;
+}
+// BHN_T8_CALIBRATE, first pass, in front of its delta chain: the chain once with nothing limited (its tape output is overwritten
+// by the chain behind it); the ratios of its |gA_l| maxima to |dimages|max give this call's scales
+template <class Pol>
+static int t8_calibrate(const BwdArgs &A, void (*k_chn)(BwdArgs), long long grid, size_t lds_chn, int depth, hipStream_t st) {
+    if constexpr (Pol::TAPE8) {
+        hipLaunchKernelGGL(t8_open_kernel, dim3(1), dim3(64), 0, st, A.t8);
+        hipLaunchKernelGGL(k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), lds_chn, st, A);
+        hipLaunchKernelGGL(t8_update_kernel, dim3(1), dim3(64), 0, st, A.t8, depth);
+        hipLaunchKernelGGL(t8_prepare_kernel, dim3(1), dim3(64), 0, st, A.t8, depth, 0);
+        BHN_HIP(hipGetLastError());
+    }
+    return BHN_OK;
+}
+// behind the reduce: the next call's ratios
+template <class Pol>
+static void t8_update(const BwdArgs &A, int depth, hipStream_t st) {
+    if constexpr (Pol::TAPE8) hipLaunchKernelGGL(t8_update_kernel, dim3(1), dim3(64), 0, st, A.t8, depth);
+}
+
+// ---- launch
+enum { RUN_RECOMPUTE, RUN_FWD_TRAIN, RUN_BWD_TAPE };   // bhn_render_bwd, bhn_render_fwd_train, bhn_render_bwd_tape(_timed)
+
+// frames per pass so that the tape fits the workspace (the layout of the size query); the recorded-tape calls need all at once
+template <int W, class Pol>
+static int frames_per_pass(int what, const BwdPlan<W, Pol> &p, long long groups_per_frame, int B, size_t workspace_bytes, long long *fpp) {
+    TapeLayout t;
+    p.layout(groups_per_frame, &t);
+    if (workspace_bytes < p.tape_off + (size_t)t.total) {
+        bhn_set_error("render_bwd workspace too small: %zu bytes, need >= %zu (slabs %zu + one frame of tape %lld)",
+                      workspace_bytes, p.tape_off + (size_t)t.total, p.slab_bytes, t.total);
+        return BHN_EWORKSPACE;
+    }
+    *fpp = 1;
+    while (*fpp < B) {
+        p.layout(groups_per_frame * (*fpp + 1), &t);
+        if (p.tape_off + (size_t)t.total > workspace_bytes) break;
+        ++*fpp;
+    }
+    if (what != RUN_RECOMPUTE && *fpp < B) {
+        bhn_set_error("the recorded-tape path needs a workspace for all %d frames at once (%zu bytes given); "
+                      "use bhn_render_fwd + bhn_render_bwd, which iterate over frame groups", B, workspace_bytes);
+        return BHN_EWORKSPACE;
+    }
+    return BHN_OK;
+}
+
+// the kernels of one pass over a group of frames
+template <int W, class Pol>
+static int bwd_pass(int what, const BwdPlan<W, Pol> &p, const BwdArgs &A, int pass, long long grid, int ncu, bool t8_cal,
+                    int *nslabs128, hipStream_t st, void *const *events, int n_events) {
+    // bhn_render_bwd_tape_timed: event i is recorded behind kernel i - 1 (single-pass calls only)
+    auto mark = [&](int i) -> hipError_t {
+        return (events && i < n_events && events[i] && pass == 0) ? hipEventRecord((hipEvent_t)events[i], st) : hipSuccess;
+    };
+    if (what != RUN_FWD_TRAIN) BHN_HIP(mark(0));
+    if (what != RUN_BWD_TAPE) {              // the training forward, or (bhn_render_bwd) the forward again, tape only: A.f.images is null
+        hipLaunchKernelGGL(p.k_fwd, dim3((unsigned)grid), dim3((unsigned)p.nwf * 64u), p.lds_fwd, st, A);
+        BHN_HIP(hipGetLastError());
+        if (what == RUN_FWD_TRAIN) return BHN_OK;
+    }
+    if (p.f128) {                            // kernel slot 0 = the fused chain + dW kernel, slot 1 empty
+        // (later passes ACCUMULATE onto the slabs of the first: never more workgroups than the first pass had)
+        const long long g128 = bhn_balanced_grid(A.t.NQ / 4, (pass > 0 && *nslabs128 > 0 && *nslabs128 < ncu) ? *nslabs128 : ncu);
+        if ((int)g128 > *nslabs128) *nslabs128 = (int)g128;
+        const int rc = bwd128_launch(A, p.depth, (int)g128, st);
+        if (rc != BHN_OK) return rc;
+        BHN_HIP(mark(1));
+        BHN_HIP(mark(2));
         return BHN_OK;
     }
-    if (what == RUN_INFO) {        // query_bytes: int64_t out[8] (bhn_tape_info); query_P: 32-point groups per frame
-        TapeLayout t;
-        layout(query_P > 0 ? query_P : 1, &t);
-        int64_t *o = reinterpret_cast<int64_t *>(query_bytes);
-        tape_traffic<W, Pol>(s, t, o);
-        o[5] = bhn_fwd_w12(Pol::MODE, W, s.depth, query_P) && CAN_X && f128 ? (int)FPol::NWAVES : (int)Pol::NWAVES;
-        return BHN_OK;
+    if (t8_cal && pass == 0) {
+        const int rc = t8_calibrate<Pol>(A, p.k_chn, grid, p.lds_chn, p.depth, st);
+        if (rc != BHN_OK) return rc;
     }
+    hipLaunchKernelGGL(p.k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), p.lds_chn, st, A);
+    BHN_HIP(hipGetLastError());
+    BHN_HIP(mark(1));
+    hipLaunchKernelGGL(p.kdw, dim3((unsigned)A.wg_begin[p.depth + 1]), dim3(Pol::NTHREADS), p.lds_dw, st, A);
+    BHN_HIP(hipGetLastError());
+    BHN_HIP(mark(2));
+    return BHN_OK;
+}
+
+template <int W, class Pol>
+static int bwd_launch(int what, const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom, const bhn_frames *fr,
+                      const float *dimages, float *images, float *dparams, void *workspace, size_t workspace_bytes,
+                      hipStream_t st, int device, void *const *events, int n_events) {
+    BHN_CHECK_DEVICE(device);
+    const int ncu = bhn_num_cus(device);
+    const long long gpf = bhn_groups_per_frame(geom);
     BwdArgs A;
     memset(&A, 0, sizeof(A));
-    int rc = fused_fill_args(m, mode, packed, geom, fr, true, &A.f, &s, nwf);
-    A.fwd_nw = nwf;
+    MlpShape s;
+    int rc = fused_fill_args(m, bhn_norm_mode(mode), packed, geom, fr, true, &A.f, &s, bhn_fwd_tile_groups(Pol::MODE, W, m->net_depth, gpf));
     if (rc != BHN_OK) return rc;
+    BwdPlan<W, Pol> p;
+    bwd_plan(s, gpf, ncu, A.f.Sx, &p);
     BHN_CHECK_ARG(workspace, "null workspace");
     BHN_CHECK_ARG(what == RUN_FWD_TRAIN ? images != nullptr : (dimages && dparams), "null pointer");
-    const int depth = s.depth;
-    // frames per pass so that the tape fits the workspace (same layout function as the size query)
-    const long long groups_per_frame = (long long)A.f.tiles_per_frame * nwf;
-    TapeLayout t1;
-    layout(groups_per_frame, &t1);
-    if (workspace_bytes < slab_bytes + t8_bytes + (size_t)t1.total) {
-        bhn_set_error("render_bwd workspace too small: %zu bytes, need >= %zu (slabs %zu + one frame of tape %lld)",
-                      workspace_bytes, slab_bytes + t8_bytes + (size_t)t1.total, slab_bytes, t1.total);
-        return BHN_EWORKSPACE;
-    }
-    long long fpp = 1;
-    while (fpp < A.f.B) {
-        TapeLayout tn;
-        layout(groups_per_frame * (fpp + 1), &tn);
-        if (slab_bytes + t8_bytes + (size_t)tn.total > workspace_bytes) break;
-        ++fpp;
-    }
-    if (what != RUN_RECOMPUTE && fpp < A.f.B) {
-        bhn_set_error("the recorded-tape path needs a workspace for all %d frames at once (%zu bytes given); "
-                      "use bhn_render_fwd + bhn_render_bwd, which iterate over frame groups", A.f.B, workspace_bytes);
-        return BHN_EWORKSPACE;
-    }
-    A.f.slabs = reinterpret_cast<float *>(workspace);
-    A.slab0 = ga0c ? reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + slab_dw_bytes) : nullptr;
-    A.tape = reinterpret_cast<char *>(workspace) + slab_bytes + t8_bytes;
-    A.t8 = Pol::TAPE8 ? reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + slab_bytes) : nullptr;
-    if constexpr (Pol::TAPE8) {
-        // what the 8-bit kernels are built for (everything the reference's own drivers use at this width)
-        BHN_CHECK_ARG(t1.drop_h1 && t1.drop_ga && !s.skip_in[depth] && s.width_true == W,
-                      "BHN_BF16_T8: depth >= 3, no skip into layer 1 or into the output layer, net_width == %d", W);
-    }
-    A.f.slab_floats = BG::SLAB_FLOATS;
+    const int depth = s.depth, B_total = A.f.B;
+    long long fpp = 0;
+    rc = frames_per_pass(what, p, (long long)A.f.tiles_per_frame * p.nwf, B_total, workspace_bytes, &fpp);
+    if (rc != BHN_OK) return rc;
+    char *ws = reinterpret_cast<char *>(workspace);
+    A.f.slabs = reinterpret_cast<float *>(ws);
+    A.slab0 = p.ga0c ? reinterpret_cast<float *>(ws + p.slab_dw_bytes) : nullptr;
+    A.t8 = Pol::TAPE8 ? reinterpret_cast<float *>(ws + p.slab_bytes) : nullptr;
+    A.tape = ws + p.tape_off;
+    A.fwd_nw = p.nwf;
+    A.f.slab_floats = BwdGeom<W, Pol>::SLAB_FLOATS;
     A.f.dimages = dimages;
     A.f.images = images;
     A.dparams = dparams;
@@ -2181,281 +2357,144 @@ static int bwd_run(int what, const bhn_model *m, int32_t mode, const void *packe
     A.width_true = s.width_true;
     for (int l = 0; l <= depth; ++l) { A.kernel_off[l] = s.kernel_off[l]; A.bias_off[l] = s.bias_off[l]; A.in_dim[l] = s.in_dim[l]; }
     A.kernel_off[depth + 1] = s.nparams;
-    // dW jobs: every layer gets workgroups in proportion to the tiles it streams per 32-point group (A + B), with
-    // measured corrections for the two jobs that compute more than they stream (layer 1: recompute of h_1; layer depth-1:
-    // rebuild of gA, output row).  Balancing the jobs so that each takes the same time when it runs ALONE
-    // (round 2) measured slower (5.0 vs 4.75 ms): run together they share the HBM stream, and the light
-    // layer-0 job finishing early leaves its bandwidth to the others.
-    {
-        double work[BHN_MAX_LAYERS + 1], tot = 0;
-        const int last_job = t1.drop_ga ? depth - 1 : depth;       // drop_ga: the output row rides on layer depth-1's job
-        for (int l = 0; l <= depth; ++l) {
-            const int mtA = (l == depth) ? 0 : BG::MT;
-            int nB = (l >= 1 ? BG::MT : 0) + ((l == 0 || s.skip_in[l]) ? 1 : 0);
-            if (l == 1 && t1.drop_h1) nB = JOB1_W * BG::MT / 8;   // reads only the encoded inputs instead of h_1 but has the
-                                                                  // same MFMA work + the recompute: not byte-bound any more
-            work[l] = (double)(mtA + nB) + 0.5;
-            // + the rebuild of gA and the output row (8-bit tape: the byte masks of that job are its long pole; 12 measured 2-3 % faster than 8)
-            if (l == depth - 1 && t1.drop_ga) work[l] += (Pol::TAPE8 ? 12 : JOBL_W) * BG::MT / 8.0;
-            if constexpr (Pol::ELEM_BYTES == 4) {
-                // f32: the jobs are MFMA-bound (a 32x32x2 MFMA is 64 cycles; one 32x32 tile product over a 32-point
-                // group = 16 of them = 0.55 us at the observed 1.87 GHz) unless they stream more than ~34 GB/s per
-                // workgroup (one 68 KB group in flight per ~2 us round trip = 0.075 tile products per KiB: measured 26 GB/s for the layer-0 job alone)
-                const int a_tiles = (l == depth) ? 1 : BG::MT;           // the output job's A operand is the dout tile
-                const int wrr = (l == depth) ? 1 : BG::WRR, wcc = Pol::NWAVES / wrr;
-                const double tp = (double)((a_tiles + wrr - 1) / wrr) * ((nB + wcc - 1) / wcc);
-                const double kib = (double)(a_tiles + nB) * BG::TILE_BYTES / 1024.0;
-                work[l] = (tp > 0.075 * kib ? tp : 0.075 * kib) + 0.1;
-            }
-            if (l > last_job) work[l] = 0;
-            if (t1.ga0_chain && l == 0) work[l] = 0;               // dW_0 comes out of the delta chain: no layer-0 job
-            tot += work[l];
-        }
-        int used = 0;
-        A.wg_begin[0] = 0;
-        for (int l = 0; l <= depth; ++l) {
-            int n = (int)(grid_dw * work[l] / tot);
-            if (n < 1) n = 1;
-            if (l == last_job) n = grid_dw - used;
-            if (n < 1) n = 1;
-            if (l > last_job || (t1.ga0_chain && l == 0)) n = 0;
-            used += n;
-            A.wg_begin[l + 1] = used;
-        }
-        if (used > grid_dw) {
-            bhn_set_error("internal: dW job split overflow (%d > %d)", used, grid_dw);
-            return BHN_EINVAL;
-        }
-    }
-    // ring + bias rows + zero row + output weights + identity fragments
-    const size_t lds_fixed = ((size_t)depth * W + 32) * 4 + 128 + W * 4 + (Pol::ELEM_BYTES == 2 ? 0 : 2 * Pol::FRAG_BYTES) + RaySum<Pol::NWAVES>::bytes(A.f.Sx);
-    const size_t lds_taped = (size_t)(BG::RING_DIST_TAPED + 1) * PK::CHUNK_BYTES + lds_fixed;
-    // training forward with the resident encoded-input block (EncBlock): ring buffers of the KS hidden fragments + the block
-    const size_t lds_fwd_encr = (size_t)(BG::RING_DIST_TAPED + 1) * PK::KS * Pol::FRAG_BYTES + lds_fixed + EncBlock<W, Pol>::BYTES;
-    size_t lds_dw = (size_t)BG::NBUF * BG::GROUP_BYTES + (t1.drop_h1 ? (size_t)2 * BG::MT * Pol::FRAG_BYTES + W * 4 : 0);
-    if (t1.drop_ga && (size_t)BG::NBUF * BG::GROUP_BYTES_LAST2 > lds_dw) lds_dw = (size_t)BG::NBUF * BG::GROUP_BYTES_LAST2;
-    if constexpr (Pol::TAPE8) {          // the 8-bit jobs other than layer 1's run a deeper ring of smaller group images (dw_body2: NB)
-        const size_t deep = (size_t)T8_NBUF * (2 * BG::MT * BG::TAPE_TILE + BG::TILE_BYTES + 1024);
-        if (deep > lds_dw) lds_dw = deep;
-    }
-    // small networks: the training forward / the delta chain keep their whole chunk sequence in LDS and run without the
-    // per-chunk barrier (ResidentRing), each when its own sequence fits
-    const size_t res_fwd = (size_t)PK::fwd_chunks(depth) * PK::CHUNK_BYTES + lds_fixed, res_chn = (size_t)PK::bwd_chunks(depth) * PK::CHUNK_BYTES + lds_fixed;
-    constexpr bool CAN_RES = W <= 128;                                  // (width 256: no second instantiation)
-    const bool rf = CAN_RES && res_fwd <= 160 * 1024, rch = CAN_RES && res_chn <= 160 * 1024;
-    auto k_fwd = rf ? chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, CAN_RES> : chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, false>;
-    // (x12: the resident image + the ray-sum scratch of 12 groups: 154 KB at four Stokes planes)
-    const size_t res_fwd_x = res_fwd - RaySum<Pol::NWAVES>::bytes(A.f.Sx) + RaySum<FPol::NWAVES>::bytes(A.f.Sx);
-    if constexpr (CAN_X) {
-        if (x12) {
-            BHN_CHECK_ARG(CAN_RES && res_fwd_x <= 160 * 1024, "internal: the 12-wave training forward needs its weights resident (%zu bytes)", res_fwd_x);
-            k_fwd = chain_kernel<W, FPol, 3, MODE_FWD_TRAIN, CAN_RES>;
-        }
-    }
+    memcpy(A.wg_begin, p.wg_begin, sizeof(A.wg_begin));
+    BHN_CHECK_ARG(A.wg_begin[depth + 1] <= ncu, "internal: dW job split overflow (%d > %d)", A.wg_begin[depth + 1], ncu);
+    BHN_CHECK_ARG(!p.x12 || p.lds_fwd <= 160 * 1024, "internal: the 12-wave training forward needs its weights resident (%zu bytes)", p.lds_fwd);
     // (fused128: only the resident training forward records the relu bits of the last hidden layer in place of its h tiles, chain_kernel CAN_HD)
-    BHN_CHECK_ARG(!f128 || x12 || rf, "internal: the fused 4x128 training forward needs its weights resident (%zu bytes)", res_fwd);
-    const unsigned nthr_fwd = (unsigned)nwf * 64u;
-    constexpr bool CAN_GA0C = ga0_chain_ok<W, Pol>(3);                // (compile-time part of the condition: which widths instantiate it)
-    auto k_chn = rch ? chain_kernel<W, Pol, 3, MODE_CHAIN, CAN_RES> : chain_kernel<W, Pol, 3, MODE_CHAIN, false>;
-    if (ga0c) k_chn = chain_kernel<W, Pol, 3, MODE_CHAIN, false, CAN_GA0C>;
-    // ga0_chain: a ring of GA0C_DIST + 1 buffers of the KS fragments the chain streams, the fixed part, 4 staging images of one tile per wave
-    const size_t lds_ga0c = (size_t)(GA0C_DIST + 1) * PK::KS * Pol::FRAG_BYTES + lds_fixed + (size_t)4 * Pol::NWAVES * BG::TILE_BYTES;
-    const size_t lds_fwd = x12 ? res_fwd_x : rf ? res_fwd : (EncBlock<W, Pol>::ON ? lds_fwd_encr : lds_taped), lds_chn = ga0c ? lds_ga0c : rch ? res_chn : lds_taped;
-    auto kdw = dw_kernel<W, Pol>;
+    BHN_CHECK_ARG(!p.f128 || p.x12 || p.rf, "internal: the fused 4x128 training forward needs its weights resident (%zu bytes)", p.res_fwd);
+    constexpr bool CAN_RES = W <= 128, CAN_GA0C = ga0_chain_ok<W, Pol>(3);
+    using FPol = std::conditional_t<W == 128 && Pol::ELEM_BYTES == 2 && !Pol::TAPE8, PolBF16X, Pol>;
     static DeviceOnce once;                 // per template instantiation and device
     BHN_HIP(once.run(device, [&](int &) {
         for (const void *k : {(const void *)chain_kernel<W, FPol, 3, MODE_FWD_TRAIN, CAN_RES>, (const void *)chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, CAN_RES>, (const void *)chain_kernel<W, Pol, 3, MODE_FWD_TRAIN, false>,
                               (const void *)chain_kernel<W, Pol, 3, MODE_CHAIN, CAN_RES>, (const void *)chain_kernel<W, Pol, 3, MODE_CHAIN, false>,
-                              (const void *)chain_kernel<W, Pol, 3, MODE_CHAIN, false, CAN_GA0C>, (const void *)kdw}) {
+                              (const void *)chain_kernel<W, Pol, 3, MODE_CHAIN, false, CAN_GA0C>, (const void *)p.kdw}) {
             const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     }));
-    BHN_CHECK_ARG(lds_taped <= 160 * 1024 && lds_dw <= 160 * 1024 && lds_chn <= 160 * 1024, "LDS budget exceeded (chain %zu / %zu, dw %zu)", lds_taped, lds_chn, lds_dw);
-    const int B_total = A.f.B;
-    const double *tM0 = A.f.tM0;
-    int nslabs128 = 0;
-    if constexpr (Pol::TAPE8) {
-        if (what != RUN_FWD_TRAIN) {         // this call's tape scales: the stored ratios times the size of THIS d(loss)/d(images)
-            const long long npx = (long long)B_total * A.f.Sx * A.f.R;
-            // a calibrating call starts from a clean state block: the workspace may never have been used, and t8_update keeps
-            // a layer's OLD ratio when the chain saw only zeros there -- all-zero ratios fall back to scale 1 (t8_prepare)
-            if (t8_cal) BHN_HIP(hipMemsetAsync(A.t8, 0, t8_bytes, st));
-            hipLaunchKernelGGL(t8_dmax_kernel, dim3((unsigned)(npx >= 65536 ? 64 : (npx + 1023) / 1024)), dim3(1024), 0, st, A.t8, dimages, npx);
-            hipLaunchKernelGGL(t8_prepare_kernel, dim3(1), dim3(64), 0, st, A.t8, depth, 1);
-            BHN_HIP(hipGetLastError());
-        }
+    BHN_CHECK_ARG(p.lds_taped <= 160 * 1024 && p.lds_dw <= 160 * 1024 && p.lds_chn <= 160 * 1024, "LDS budget exceeded (chain %zu / %zu, dw %zu)", p.lds_taped, p.lds_chn, p.lds_dw);
+    const bool t8_cal = Pol::TAPE8 && (mode & BHN_T8_CALIBRATE);
+    if (what != RUN_FWD_TRAIN) {
+        rc = t8_scales<Pol>(A, t8_cal, dimages, depth, st);
+        if (rc != BHN_OK) return rc;
     }
     if (what == RUN_FWD_TRAIN)
         BHN_HIP(hipMemsetAsync(images, 0, sizeof(float) * (size_t)B_total * A.f.Sx * A.f.R, st));
+    const double *tM0 = A.f.tM0;
+    int nslabs128 = 0;
     for (int b0 = 0, pass = 0; b0 < B_total; b0 += (int)fpp, ++pass) {
         const int nb = (b0 + fpp <= B_total) ? (int)fpp : B_total - b0;
         A.f.B = nb;
         A.f.tM0 = tM0 + b0;
         A.f.dimages = dimages ? dimages + (long long)b0 * A.f.Sx * A.f.R : nullptr;
         A.f.total_tiles = (long long)A.f.tiles_per_frame * nb;
-        layout(A.f.total_tiles * nwf, &A.t);
+        p.layout(A.f.total_tiles * p.nwf, &A.t);
         A.accumulate = pass > 0;
         // (ga0_chain: later passes ACCUMULATE onto the dW_0 slabs of the first: never more workgroups than the first pass had)
         const long long grid = bhn_balanced_grid(A.f.total_tiles, (pass > 0 && A.n_chain_wg > 0 && A.n_chain_wg < ncu) ? A.n_chain_wg : ncu);
         if (pass == 0) A.n_chain_wg = (int)grid;
-        if (what == RUN_FWD_TRAIN) {
-            hipLaunchKernelGGL(k_fwd, dim3((unsigned)grid), dim3(nthr_fwd), lds_fwd, st, A);
-            BHN_HIP(hipGetLastError());
-            continue;
-        }
-        // bhn_render_bwd_tape_timed: event i is recorded behind kernel i - 1 (single-pass calls only)
-        auto mark = [&](int i) -> hipError_t {
-            return (events && i < n_events && events[i] && pass == 0) ? hipEventRecord((hipEvent_t)events[i], st) : hipSuccess;
-        };
-        BHN_HIP(mark(0));
-        if (f128) {                          // kernel slot 0 = the fused chain + dW kernel, slot 1 empty
-            if (what == RUN_RECOMPUTE) {
-                hipLaunchKernelGGL(k_fwd, dim3((unsigned)grid), dim3(nthr_fwd), lds_fwd, st, A);
-                BHN_HIP(hipGetLastError());
-            }
-            // (later passes ACCUMULATE onto the slabs of the first: never more workgroups than the first pass had)
-            const long long g128 = bhn_balanced_grid(A.t.NQ / 4, (pass > 0 && nslabs128 > 0 && nslabs128 < ncu) ? nslabs128 : ncu);
-            if ((int)g128 > nslabs128) nslabs128 = (int)g128;
-            const int rc128 = bwd128_launch(A, depth, (int)g128, st);
-            if (rc128 != BHN_OK) return rc128;
-            BHN_HIP(mark(1));
-            BHN_HIP(mark(2));
-            continue;
-        }
-        if (what == RUN_RECOMPUTE) {     // forward again (tape only: A.f.images is null), then the chain
-            hipLaunchKernelGGL(k_fwd, dim3((unsigned)grid), dim3(nthr_fwd), lds_fwd, st, A);
-            BHN_HIP(hipGetLastError());
-        }
-        if constexpr (Pol::TAPE8) {
-            if (t8_cal && pass == 0) {
-                // calibration: the delta chain once with nothing limited (its tape output is overwritten below); the
-                // ratios of its |gA_l| maxima to |dimages|max give this call's scales
-                hipLaunchKernelGGL(t8_open_kernel, dim3(1), dim3(64), 0, st, A.t8);
-                hipLaunchKernelGGL(k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), lds_chn, st, A);
-                hipLaunchKernelGGL(t8_update_kernel, dim3(1), dim3(64), 0, st, A.t8, depth);
-                hipLaunchKernelGGL(t8_prepare_kernel, dim3(1), dim3(64), 0, st, A.t8, depth, 0);
-                BHN_HIP(hipGetLastError());
-            }
-        }
-        hipLaunchKernelGGL(k_chn, dim3((unsigned)grid), dim3(Pol::NTHREADS), lds_chn, st, A);
-        BHN_HIP(hipGetLastError());
-        BHN_HIP(mark(1));
-        hipLaunchKernelGGL(kdw, dim3((unsigned)A.wg_begin[depth + 1]), dim3(Pol::NTHREADS), lds_dw, st, A);
-        BHN_HIP(hipGetLastError());
-        BHN_HIP(mark(2));
+        rc = bwd_pass(what, p, A, pass, grid, ncu, t8_cal, &nslabs128, st, events, n_events);
+        if (rc != BHN_OK) return rc;
     }
-    if (what != RUN_FWD_TRAIN && f128) {
-        const int rcr = reduce128_launch(A, depth, nslabs128, st);
-        if (rcr != BHN_OK) return rcr;
-    } else if (what != RUN_FWD_TRAIN) {
-        A.chain_step = 1;
-        if (ga0c && A.n_chain_wg > 16) {
-            const int parts = 16;
-            A.chain_step = (A.n_chain_wg + parts - 1) / parts;
-            hipLaunchKernelGGL(chain_slab_stage1, dim3(BG::MT, parts), dim3(256), 0, st, A, BG::MT, A.chain_step);
+    if (what != RUN_FWD_TRAIN) {
+        if (p.f128) {
+            rc = reduce128_launch(A, depth, nslabs128, st);
+            if (rc != BHN_OK) return rc;
+        } else {
+            using BG = BwdGeom<W, Pol>;
+            A.chain_step = 1;
+            if (p.ga0c && A.n_chain_wg > 16) {
+                const int parts = 16;
+                A.chain_step = (A.n_chain_wg + parts - 1) / parts;
+                hipLaunchKernelGGL(chain_slab_stage1, dim3(BG::MT, parts), dim3(256), 0, st, A, BG::MT, A.chain_step);
+            }
+            hipLaunchKernelGGL((reduce_kernel<W, Pol>), dim3((unsigned)ReduceGeom<W, Pol>::blocks(depth, (unsigned)A.f.skip_mask)), dim3(256), 0, st, A);
         }
-        hipLaunchKernelGGL((reduce_kernel<W, Pol>), dim3((unsigned)ReduceGeom<W, Pol>::blocks(depth, (unsigned)A.f.skip_mask)), dim3(256), 0, st, A);
-    }
-    if constexpr (Pol::TAPE8) {
-        if (what != RUN_FWD_TRAIN) hipLaunchKernelGGL(t8_update_kernel, dim3(1), dim3(64), 0, st, A.t8, depth);      // the next call's ratios
+        t8_update<Pol>(A, depth, st);
     }
     BHN_HIP(hipGetLastError());
     if (events && n_events > 3 && events[3]) BHN_HIP(hipEventRecord((hipEvent_t)events[3], st));
     return BHN_OK;
 }
 
-template <class Pol>
-static int bwd_dispatch(int what, int width, const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom,
-                        const bhn_frames *fr, const float *dimages, float *images, float *dparams, void *ws, size_t wsb,
-                        hipStream_t st, size_t *qb, int qB, long long qP, int device, void *const *ev = nullptr, int nev = 0) {
-    switch (width) {
-        case 32: return bwd_run<32, Pol>(what, m, mode, packed, geom, fr, dimages, images, dparams, ws, wsb, st, qb, qB, qP, device, ev, nev);
-        case 64: return bwd_run<64, Pol>(what, m, mode, packed, geom, fr, dimages, images, dparams, ws, wsb, st, qb, qB, qP, device, ev, nev);
-        case 128: return bwd_run<128, Pol>(what, m, mode, packed, geom, fr, dimages, images, dparams, ws, wsb, st, qb, qB, qP, device, ev, nev);
-        case 256: return bwd_run<256, Pol>(what, m, mode, packed, geom, fr, dimages, images, dparams, ws, wsb, st, qb, qB, qP, device, ev, nev);
-        default:
-            bhn_set_error("net_width %d: fused kernels are built for 32, 64, 128, 256", width);
-            return BHN_EUNSUPPORTED;
-    }
-}
-
+// ---- entry points
 static int bwd_entry(int what, const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom,
                      const bhn_frames *fr, const float *dimages, float *images, float *dparams, void *workspace,
                      size_t workspace_bytes, void *stream, void *const *ev = nullptr, int nev = 0) {
     BHN_CHECK_ARG(m, "null model");
-    const bool t8 = (mode & 0xff) == BHN_BF16_T8 && bhn_norm_mode(mode) == BHN_BF16;
-    BHN_CHECK_ARG(mode == BHN_F32 || mode == BHN_BF16 || t8, "bad mode %d", mode);
+    MlpShape s;
+    BwdPath path;
+    int rc = bhn_mlp_shape(m, &s);
+    if (rc == BHN_OK) rc = bwd_path(mode, s, &path);
+    if (rc != BHN_OK) return rc;
     int dev = 0;
     BHN_HIP(hipGetDevice(&dev));
-    MlpShape shape;
-    const int rcs = bhn_mlp_shape(m, &shape);
-    if (rcs != BHN_OK) return rcs;
-    const int kernel_width = shape.width;
-    if (shape.general) {
-        // shapes outside the fused kernels (general_mlp.hip, f32 in both modes): the training forward records the tape when the
-        // workspace holds it, bhn_render_bwd recomputes chunk by chunk
-        if (t8) { bhn_set_error("BHN_BF16_T8 (8-bit tape) is built for net_width 256, posenc_deg <= 4; use BHN_BF16"); return BHN_EUNSUPPORTED; }
+    const hipStream_t st = (hipStream_t)stream;
+    if (path == BWD_GENERAL) {
+        // shapes outside the fused kernels (general_mlp.hip): the training forward records the tape when the workspace holds
+        // it, bhn_render_bwd recomputes chunk by chunk
         BHN_CHECK_ARG(!ev, "per-kernel events are not available for posenc_deg > 4 / net_width > 256");
         if (what == RUN_FWD_TRAIN) {
             BHN_CHECK_ARG(images, "null pointer");
             BHN_CHECK_ARG(workspace, "null workspace");            // (gen_forward: no workspace = the plain render)
-            return gen_forward(true, m, mode, packed, geom, fr, images, (hipStream_t)stream, workspace, workspace_bytes);
+            return gen_forward(true, m, mode, packed, geom, fr, images, st, workspace, workspace_bytes);
         }
-        return gen_backward(what == RUN_BWD_TAPE, m, mode, packed, geom, fr, dimages, dparams, workspace, workspace_bytes, (hipStream_t)stream);
+        return gen_backward(what == RUN_BWD_TAPE, m, mode, packed, geom, fr, dimages, dparams, workspace, workspace_bytes, st);
     }
-    if (t8) {
-        if (kernel_width != 256 || shape.depth < 3) {
-            bhn_set_error("BHN_BF16_T8 (8-bit tape) is built for net_width 256 and net_depth >= 3 (got %d x %d); use BHN_BF16", shape.depth, shape.width_true);
-            return BHN_EUNSUPPORTED;
-        }
-        return bwd_run<256, PolBF16T8>(what, m, mode, packed, geom, fr, dimages, images, dparams, workspace, workspace_bytes,
-                                       (hipStream_t)stream, nullptr, 0, 0, dev, ev, nev);
-    }
-    return (mode == BHN_BF16)
-               ? bwd_dispatch<PolBF16>(what, kernel_width, m, mode, packed, geom, fr, dimages, images, dparams, workspace,
-                                       workspace_bytes, (hipStream_t)stream, nullptr, 0, 0, dev, ev, nev)
-               : bwd_dispatch<PolF32>(what, kernel_width, m, mode, packed, geom, fr, dimages, images, dparams, workspace,
-                                      workspace_bytes, (hipStream_t)stream, nullptr, 0, 0, dev, ev, nev);
+    return with_bwd_kernels(path, s.width, [&](auto w, auto pol) {
+        return bwd_launch<decltype(w)::value, decltype(pol)>(what, m, mode, packed, geom, fr, dimages, images, dparams, workspace,
+                                                             workspace_bytes, st, dev, ev, nev);
+    });
 }
 
 extern "C" size_t bhn_render_bwd_workspace_bytes(const bhn_model *m, int32_t mode, int32_t B, int64_t P, int32_t device) {
     MlpShape s;
-    if (bhn_mlp_shape(m, &s) != BHN_OK || B <= 0 || P <= 0) return 0;
-    size_t q = 0;
-    if (s.general && (mode & 0xff) != BHN_BF16_T8) return gen_bwd_workspace_bytes(s, mode, B, P);
-    if ((mode & 0xff) == BHN_BF16_T8 && bhn_norm_mode(mode) == BHN_BF16) {
-        if (s.general || s.width != 256 || s.depth < 3) {
-            bhn_set_error("BHN_BF16_T8 (8-bit tape) is built for net_width 256 and net_depth >= 3 (got %d x %d); use BHN_BF16", s.depth, s.width_true);
-            return 0;
+    BwdPath path;
+    if (bhn_mlp_shape(m, &s) != BHN_OK || B <= 0 || P <= 0 || bwd_path(mode, s, &path) != BHN_OK) return 0;
+    if (path == BWD_GENERAL) return gen_bwd_workspace_bytes(s, mode, B, P);
+    size_t bytes = 0;
+    with_bwd_kernels(path, s.width, [&](auto w, auto pol) {
+        constexpr int W = decltype(w)::value;
+        using Pol = decltype(pol);
+        BHN_CHECK_DEVICE(device);
+        BwdPlan<W, Pol> p;
+        bwd_plan(s, (P + 31) / 32, bhn_num_cus(device), 1, &p);
+        // (the caller's P may be the dense point count of a ray set that is walked compacted, or the other way round: room for either tile size)
+        long long need = 0;
+        for (int nw : {(int)Pol::NWAVES, bhn_fwd_tile_groups(Pol::MODE, W, s.depth, LLONG_MAX)}) {
+            TapeLayout t;
+            p.layout((P + nw * 32 - 1) / (nw * 32) * B * nw, &t);
+            if (t.total > need) need = t.total;
         }
-        return bwd_run<256, PolBF16T8>(RUN_QUERY, m, mode, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &q, B, P, device) == BHN_OK ? q : 0;
-    }
-    int rc = (mode == BHN_BF16)
-                 ? bwd_dispatch<PolBF16>(RUN_QUERY, s.width, m, mode, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &q, B, P, device)
-                 : bwd_dispatch<PolF32>(RUN_QUERY, s.width, m, mode, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &q, B, P, device);
-    return rc == BHN_OK ? q : 0;
+        bytes = p.tape_off + (size_t)need;
+        return BHN_OK;
+    });
+    return bytes;
 }
 
 extern "C" int bhn_tape_info(const bhn_model *m, int32_t mode, int64_t groups_per_frame, int64_t *info, int32_t n_info) {
     BHN_CHECK_ARG(m && info && n_info >= BHN_TAPE_INFO_N, "bhn_tape_info: info must hold %d entries", BHN_TAPE_INFO_N);
     MlpShape s;
-    const int rcs = bhn_mlp_shape(m, &s);
-    if (rcs != BHN_OK) return rcs;
+    BwdPath path;
+    int rc = bhn_mlp_shape(m, &s);
+    if (rc != BHN_OK) return rc;
     for (int i = 0; i < BHN_TAPE_INFO_N; ++i) info[i] = 0;
-    const bool t8 = (mode & 0xff) == BHN_BF16_T8 && bhn_norm_mode(mode) == BHN_BF16;
-    BHN_CHECK_ARG(mode == BHN_F32 || mode == BHN_BF16 || t8, "bad mode %d", mode);
-    if (s.general) { info[4] = 64; info[5] = 1; return BHN_OK; }       // (the general path: one 32-point group per workgroup, an f32 tape in chunks)
-    static_assert(sizeof(size_t) == sizeof(int64_t), "RUN_INFO passes the output array through the size query's pointer");
-    size_t *q = reinterpret_cast<size_t *>(info);
-    if (t8) {
-        if (s.width != 256 || s.depth < 3) { bhn_set_error("BHN_BF16_T8: net_width 256, net_depth >= 3"); return BHN_EUNSUPPORTED; }
-        return bwd_run<256, PolBF16T8>(RUN_INFO, m, mode, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, q, 1, groups_per_frame, 0);
-    }
-    return (mode == BHN_BF16)
-               ? bwd_dispatch<PolBF16>(RUN_INFO, s.width, m, mode, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, q, 1, groups_per_frame, 0)
-               : bwd_dispatch<PolF32>(RUN_INFO, s.width, m, mode, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, q, 1, groups_per_frame, 0);
+    rc = bwd_path(mode, s, &path);
+    if (rc != BHN_OK) return rc;
+    if (path == BWD_GENERAL) { info[4] = 64; info[5] = 1; return BHN_OK; }   // (the general path: its tape is not described here)
+    return with_bwd_kernels(path, s.width, [&](auto w, auto pol) {
+        constexpr int W = decltype(w)::value;
+        using Pol = decltype(pol);
+        BwdPlan<W, Pol> p;
+        bwd_plan(s, groups_per_frame, 0, 1, &p);                    // (no CU count: the slabs are not part of the tape)
+        TapeLayout t;
+        p.layout(groups_per_frame > 0 ? groups_per_frame : 1, &t);
+        tape_traffic<W, Pol>(s, t, info);
+        info[5] = p.nwf;
+        return BHN_OK;
+    });
 }
 
 extern "C" int bhn_render_bwd(const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom,
@@ -2484,22 +2523,25 @@ extern "C" int bhn_render_bwd_tape_timed(const bhn_model *m, int32_t mode, const
                      events, n_events);
 }
 
-extern "C" const char *bhn_render_bwd_tape_kernel_name(int32_t i);
-extern "C" const char *bhn_render_bwd_tape_kernel_name_for(const bhn_model *m, int32_t mode, int32_t i) {
-    MlpShape s;
-    if (!m || bhn_mlp_shape(m, &s) != BHN_OK) return nullptr;
-    if (s.general) {
-        static const char *const names[BHN_BWD_TAPE_KERNELS] = {"gen_mlp_kernel<GEN_CHAIN>", "gen_dw_kernel", "gen_reduce_kernel"};
-        return (i >= 0 && i < BHN_BWD_TAPE_KERNELS) ? names[i] : nullptr;
-    }
-    if (bwd128_supported(bhn_norm_mode(mode), s.width, s.depth)) {
-        static const char *const names[BHN_BWD_TAPE_KERNELS] = {"bwd128_kernel", "-", "reduce128_kernel"};
-        return (i >= 0 && i < BHN_BWD_TAPE_KERNELS) ? names[i] : nullptr;
-    }
-    return bhn_render_bwd_tape_kernel_name(i);
-}
-
 extern "C" const char *bhn_render_bwd_tape_kernel_name(int32_t i) {
     static const char *const names[BHN_BWD_TAPE_KERNELS] = {"chain_kernel<MODE_CHAIN>", "dw_kernel", "reduce_kernel"};
     return (i >= 0 && i < BHN_BWD_TAPE_KERNELS) ? names[i] : nullptr;
+}
+
+// the kernels of the path bwd_entry takes for this mode and network (null where it takes none)
+extern "C" const char *bhn_render_bwd_tape_kernel_name_for(const bhn_model *m, int32_t mode, int32_t i) {
+    static const char *const gen[BHN_BWD_TAPE_KERNELS] = {"gen_mlp_kernel<GEN_CHAIN>", "gen_dw_kernel", "gen_reduce_kernel"};
+    static const char *const f128[BHN_BWD_TAPE_KERNELS] = {"bwd128_kernel", "-", "reduce128_kernel"};
+    MlpShape s;
+    BwdPath path;
+    if (bhn_mlp_shape(m, &s) != BHN_OK || bwd_path(mode, s, &path) != BHN_OK || i < 0 || i >= BHN_BWD_TAPE_KERNELS) return nullptr;
+    if (path == BWD_GENERAL) return gen[i];
+    bool fused = false;
+    with_bwd_kernels(path, s.width, [&](auto w, auto pol) {
+        BwdPlan<decltype(w)::value, decltype(pol)> p;
+        bwd_plan(s, 0, 0, 1, &p);
+        fused = p.f128;
+        return BHN_OK;
+    });
+    return fused ? f128[i] : bhn_render_bwd_tape_kernel_name(i);
 }

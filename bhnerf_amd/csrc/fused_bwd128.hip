@@ -701,7 +701,7 @@ __global__ __launch_bounds__(256) void reduce128_kernel(BwdArgs A, int nslabs, i
 
 }   // namespace
 
-// ---- host side (called from bwd_run of fused_bwd.hip) --------------------------------------------------------------------
+// ---- host side (called from the plan and the launch of fused_bwd.hip) -----------------------------------------------------
 bool bwd128_supported(int mode, int kernel_width, int depth) {
 #ifdef BHN_NO_FUSED128
     return false;

@@ -11,6 +11,7 @@
 // Canonical register order of a 32-feature block: element j (0..7) of k-step s (0..1) of lane-half
 // h is feature 16*s + 8*(j>>2) + 4*h + (j&3).   (phi below)
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -158,17 +159,6 @@ struct PolBF16X : PolBF16 {
     static constexpr int NTHREADS = NWAVES * 64;
     static constexpr int WPE = 3;
 };
-// bf16, kernel width 128, depth 4 (= bwd128_supported) and at least one round of 12-group tiles per frame on a 256-CU device: the
-// problems whose forward kernels run on PolBF16X (a small ray set -- config 5: 1,460 groups per frame -- is better off with more,
-// smaller tiles: 0.253 against 0.256 ms per step).  A function of the MODEL and the RAY SET only, never of the batch: the
-// inference forward and the training forward of one problem always agree on the tile size.
-__host__ __device__ static inline bool bhn_fwd_w12(int mode, int kernel_width, int depth, long long groups_per_frame) {
-#ifdef BHN_NO_FUSED128
-    return false;
-#else
-    return BHN_W12 != 0 && mode == BHN_BF16 && kernel_width == 128 && depth == 4 && groups_per_frame >= 12 * 256;
-#endif
-}
 // 32-point groups per frame of a ray set as the fused kernels walk it (fused_fill_args: n_groups)
 static inline long long bhn_groups_per_frame(const bhn_geom *geom) {
     if (!geom) return 0;
@@ -228,6 +218,32 @@ struct PolF32 {
     static DEVI float fexp(float x) { return expf(x); }
     static constexpr bool FAST_TRIG = false;
 };
+
+// 32-point groups per workgroup tile of the forward kernels (fused_fill_args: nwaves): 12 (PolBF16X) for bf16, kernel width 128,
+// depth 4 (= bwd128_supported) and at least one round of 12-group tiles per frame on a 256-CU device (a small ray set -- config 5:
+// 1,460 groups per frame -- is better off with more, smaller tiles: 0.253 against 0.256 ms per step), else the waves of the mode's
+// policy.  A function of the MODEL and the RAY SET only, never of the batch: the inference forward, the training forward and the
+// backward's plan of one problem always agree on the tile size.
+static inline int bhn_fwd_tile_groups(int mode, int kernel_width, int depth, long long groups_per_frame) {
+#ifndef BHN_NO_FUSED128
+    if (BHN_W12 != 0 && mode == BHN_BF16 && kernel_width == 128 && depth == 4 && groups_per_frame >= 12 * 256) return PolBF16X::NWAVES;
+#endif
+    return mode == BHN_BF16 ? PolBF16::NWAVES : PolF32::NWAVES;
+}
+
+// f(std::integral_constant<int, W>(), Pol()) for the kernel width of a fused path: 32, 64, 128 or 256
+template <class Pol, class F>
+static int bhn_with_width(int width, F &&f) {
+    switch (width) {
+        case 32: return f(std::integral_constant<int, 32>(), Pol());
+        case 64: return f(std::integral_constant<int, 64>(), Pol());
+        case 128: return f(std::integral_constant<int, 128>(), Pol());
+        case 256: return f(std::integral_constant<int, 256>(), Pol());
+        default:
+            bhn_set_error("net_width %d: fused kernels are built for 32, 64, 128, 256", width);
+            return BHN_EUNSUPPORTED;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Division of a 32-bit unsigned by a run-time constant (Granlund & Montgomery): the divisor's multiplier and shifts

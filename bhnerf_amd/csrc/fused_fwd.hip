@@ -322,26 +322,22 @@ static int launch_fwd_w(FusedArgs &a, hipStream_t st) {
 // 32-point groups per workgroup tile of the forward kernels a model and ray set take (fused_fill_args: nwaves)
 static int fwd_tile_groups(const bhn_model *m, int mode, const bhn_geom *geom) {
     MlpShape s;
-    if (m && bhn_mlp_shape(m, &s) == BHN_OK && !s.general && bhn_fwd_w12(mode, s.width, s.depth, bhn_groups_per_frame(geom))) return PolBF16X::NWAVES;
-    return (mode == BHN_BF16) ? PolBF16::NWAVES : PolF32::NWAVES;
+    const bool fused = m && bhn_mlp_shape(m, &s) == BHN_OK && !s.general;
+    return bhn_fwd_tile_groups(mode, fused ? s.width : 0, fused ? s.depth : 0, bhn_groups_per_frame(geom));
 }
 
-template <class Pol, bool RENDER>
-static int launch_fwd(FusedArgs &a, int width, hipStream_t st) {
-    switch (width) {
-        case 32: return launch_fwd_w<32, Pol, RENDER>(a, st);
-        case 64: return launch_fwd_w<64, Pol, RENDER>(a, st);
-        case 128:
-            if constexpr (Pol::ELEM_BYTES == 2) {
-                if (bhn_fwd_w12(BHN_BF16, 128, a.depth, a.n_groups)) return launch_fwd_w<128, PolBF16X, RENDER>(a, st);
-            }
-            return launch_fwd_w<128, Pol, RENDER>(a, st);
-        case 256:
-            return launch_fwd_w<256, Pol, RENDER>(a, st);
-        default:
-            bhn_set_error("net_width %d: fused kernels are built for 32, 64, 128, 256", width);
-            return BHN_EUNSUPPORTED;
-    }
+// nw: fwd_tile_groups, the tile size fused_fill_args laid the problem out for
+template <bool RENDER>
+static int launch_fwd(FusedArgs &a, int mode, int width, int nw, hipStream_t st) {
+    auto go = [&](auto w, auto pol) {
+        constexpr int W = decltype(w)::value;
+        using Pol = decltype(pol);
+        if constexpr (W == 128 && Pol::ELEM_BYTES == 2) {
+            if (nw == PolBF16X::NWAVES) return launch_fwd_w<128, PolBF16X, RENDER>(a, st);
+        }
+        return launch_fwd_w<W, Pol, RENDER>(a, st);
+    };
+    return mode == BHN_BF16 ? bhn_with_width<PolBF16>(width, go) : bhn_with_width<PolF32>(width, go);
 }
 
 #ifdef BHN_DEBUG
@@ -381,8 +377,7 @@ extern "C" int bhn_predict_fwd(const bhn_model *m, int32_t mode, const void *pac
     a.emission = emission;
     if (geom->groups)   // points of skipped groups are outside the domain: emission 0
         BHN_HIP(hipMemsetAsync(emission, 0, sizeof(float) * (size_t)a.B * a.P, (hipStream_t)stream));
-    return mode == BHN_BF16 ? launch_fwd<PolBF16, false>(a, s.width, (hipStream_t)stream)
-                            : launch_fwd<PolF32, false>(a, s.width, (hipStream_t)stream);
+    return launch_fwd<false>(a, mode, s.width, nw, (hipStream_t)stream);
 }
 
 extern "C" int bhn_render_fwd(const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom,
@@ -406,6 +401,5 @@ extern "C" int bhn_render_fwd(const bhn_model *m, int32_t mode, const void *pack
                                       : launch_fwd_w<128, PolBF16, true, true, true>(a, (hipStream_t)stream);
     }
 #endif
-    return mode == BHN_BF16 ? launch_fwd<PolBF16, true>(a, s.width, (hipStream_t)stream)
-                            : launch_fwd<PolF32, true>(a, s.width, (hipStream_t)stream);
+    return launch_fwd<true>(a, mode, s.width, nw, (hipStream_t)stream);
 }

@@ -1,8 +1,8 @@
 // NeRF_Predictor shapes the fused kernels are not built for: posenc_deg 5..10 (network.py:98-122; 3 + 6 deg <= 63 encoded
 // features) and net_width 257..512 (network.py:154).  No reference driver sets either, so this path is written for
-// completeness, not for the roofline: f32 arithmetic in BOTH modes (v_mfma_f32_32x32x2_f32; BHN_BF16 is accepted and
-// computed in f32), activations of a 32-point group in LDS, weights streamed from L2 by every workgroup, and a backward
-// that goes through an HBM tape:
+// completeness, not for the roofline: BHN_F32 in f32 (v_mfma_f32_32x32x2_f32), BHN_BF16 on bf16 weight images and a bf16
+// tape with f32 accumulation (v_mfma_f32_32x32x16_bf16, "bf16 mode" below), activations of a 32-point group in LDS, weights
+// streamed from L2 by every workgroup, and a backward that goes through an HBM tape:
 //
 //   gen_mlp_kernel<PREDICT | RENDER>   one workgroup = a TILE of eight consecutive 32-point groups, one group at a time: warp +
 //                                      posenc (emission.py:200-210, network.py:118-122) -> LDS, layers as [feature][point] images
@@ -20,7 +20,7 @@
 //                                      (the bias is the job whose input tile is a row of ones);
 //   gen_reduce_kernel                  slabs summed in split order -> flat gradient (deterministic).
 //
-// Packed image (bhn_pack_weights, all f32): per layer K_l zero-padded to [hrows | erows][outp] (hrows = width padded to 32
+// Packed image (bhn_pack_weights; BHN_BF16 adds its bf16 fragment images behind it, Gen16): per layer K_l zero-padded to [hrows | erows][outp] (hrows = width padded to 32
 // for l > 0, erows = encoded inputs padded to 32 for layer 0 and the skip layers, network.py:59-61; outp = padded width, 32
 // for the output layer whose column 0 is real), its transposed hidden part [outp][hrows] for the delta chain, its bias.
 #include <algorithm>

@@ -267,3 +267,85 @@ def image_plane_dynamics(volume, fov, coords, Omega, t_frames, t_injection, t_ge
         em = np.asarray(J, dtype=np.float64)[None] * em[:, None]                     # (nt, S, *spatial)
     return radiative_trasfer(em, g, dtau, Sigma)
 
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Kernel-shaped restatements of the voxel renderer and the grid predictor: flat geometry (P = R*G points, ray-major),
+# frame offsets t_M0 = (t_frame - t_start_obs)/GM_c3 - t_injection, a grid per frame, a grid with three sizes and three
+# extents, Stokes weights.  Pinned to map_coordinates_linear / scipy, image_plane_dynamics, grid_predictor_apply and
+# oracle_torch.grid_loss_and_grad in tests/test_standalone_refs_cpu.py.
+# ---------------------------------------------------------------------------------------------------------------
+def warp_points(x, y, z, Omega, t_geo, tM0):
+    """emission.py:143-211 for rot_axis z on flat points: (ux, uy, uz, valid), each (B, P); valid = not before the injection."""
+    x, y, z, Omega, t_geo = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (x, y, z, Omega, t_geo))
+    tM = np.asarray(tM0, dtype=np.float64).reshape(-1, 1) + t_geo[None]
+    valid = ~(tM < 0.0)
+    th = tM * Omega[None]
+    c, s = np.cos(th), np.sin(th)
+    return c * x + s * y, c * y - s * x, np.broadcast_to(z, th.shape), valid
+
+
+def world_to_index(u, extent, n):
+    """utils.py:160-166: index = (c + fov/2) / fov * (n - 1)."""
+    return (np.asarray(u, dtype=np.float64) + 0.5 * extent) / extent * (n - 1.0)
+
+
+def trilinear_world(grid, extents, ux, uy, uz):
+    """interpolate_coords (emission.py:213-233) with one extent per axis.  `grid` is (nx, ny, nz), or (B, nx, ny, nz) with
+    one grid per leading entry of ux/uy/uz (emission.py:289-293).  0 outside the grid or where a coordinate is NaN."""
+    grid = np.asarray(grid, dtype=np.float64)
+    if grid.ndim == 4:
+        return np.stack([trilinear_world(grid[b], extents, ux[b], uy[b], uz[b]) for b in range(grid.shape[0])])
+    index = [world_to_index(u, float(f), n) for u, f, n in zip((ux, uy, uz), extents, grid.shape)]
+    return map_coordinates_linear(grid, index)
+
+
+def voxel_render(grid, extents, x, y, z, Omega, t_geo, tM0, w, R, G):
+    """image_plane_dynamics (emission.py:235-303) on flat geometry: (images (B, Sx, R), emission (B, P)).  `w` is
+    (Sx, P) = J_s g^2 dtau Sigma."""
+    ux, uy, uz, valid = warp_points(x, y, z, Omega, t_geo, tM0)
+    e = np.where(valid, trilinear_world(grid, extents, ux, uy, uz), 0.0)
+    return render_weighted(e, w, R, G), e
+
+
+def render_weighted(e, w, R, G):
+    """kgeo.py:621 ray sum of emission (B, P) against Stokes weights (Sx, P) -> (B, Sx, R)."""
+    w = np.asarray(w, dtype=np.float64).reshape(-1, R, G)
+    return (e.reshape(e.shape[0], 1, R, G) * w[None]).sum(-1)
+
+
+def grid_emission(grid, scale, x, y, z, Omega, t_geo, tM0, dom):
+    """GRID_Predictor.__call__ (network.py:306-353) on flat geometry with a given domain mask: emission (B, P), and the
+    pieces its gradient needs."""
+    grid = np.asarray(grid, dtype=np.float64)
+    ux, uy, uz, valid = warp_points(x, y, z, Omega, t_geo, tM0)
+    ext = (2.0 * scale,) * 3
+    val = trilinear_world(grid, ext, ux, uy, uz)
+    live = valid & (np.asarray(dom).reshape(-1) != 0)[None]
+    return np.where(live, sigmoid(val - 10.0), 0.0), (ux, uy, uz, live)
+
+
+def grid_render_grad(grid, scale, x, y, z, Omega, t_geo, tM0, dom, w, dimages, R, G):
+    """d loss / d grid given d loss / d images (B, Sx, R) for images = render_weighted(grid_emission(...), w): the chain
+    rule written out (dE = sum_s dI_s w_s; d val = dE e (1 - e); the eight trilinear weights scattered into the grid)."""
+    grid = np.asarray(grid, dtype=np.float64)
+    n = grid.shape[0]
+    e, (ux, uy, uz, live) = grid_emission(grid, scale, x, y, z, Omega, t_geo, tM0, dom)
+    w = np.asarray(w, dtype=np.float64).reshape(-1, R, G)
+    dI = np.asarray(dimages, dtype=np.float64).reshape(e.shape[0], -1, R, 1)
+    dE = (dI * w[None]).sum(1).reshape(e.shape)
+    ix, iy, iz = (world_to_index(u, 2.0 * scale, n) for u in (ux, uy, uz))
+    inside = live & (ix >= 0) & (ix <= n - 1) & (iy >= 0) & (iy <= n - 1) & (iz >= 0) & (iz <= n - 1)
+    d = np.where(inside, dE * e * (1.0 - e), 0.0)
+    out = np.zeros_like(grid)
+    lo, fr = [], []
+    for i in (ix, iy, iz):
+        ic = np.where(inside, i, 0.0)
+        i0 = np.minimum(np.floor(ic).astype(np.int64), max(n - 2, 0))
+        lo.append(i0); fr.append(ic - i0)
+    for a in (0, 1):
+        for b in (0, 1):
+            for c in (0, 1):
+                wt = (fr[0] if a else 1 - fr[0]) * (fr[1] if b else 1 - fr[1]) * (fr[2] if c else 1 - fr[2])
+                np.add.at(out, (np.minimum(lo[0] + a, n - 1), np.minimum(lo[1] + b, n - 1), np.minimum(lo[2] + c, n - 1)), d * wt)
+    return out

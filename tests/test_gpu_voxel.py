@@ -47,10 +47,13 @@ def test_image_plane_dynamics_golden(golden):
     fast = emission.image_plane_dynamics((g['volume'], float(g['axis'][-1] - g['axis'][0])), geos, g['Omega'], t,
                                          float(g['t_injection']), J=1.0, slow_light=False, doppler=False, t_start_obs=0.1 * units.hr)
     assert relerr(fast, g['images_fast']) < 1e-5
-    movie4d = np.stack([g['volume']] * 3)            # one grid per frame (emission.py:289-293)
+    # one grid per frame (emission.py:289-293), each frame's a different volume: frame b scaled by 1 + b scales image b by the
+    # same factor (trilinear sampling is linear in the grid), so a frame read from another frame's grid shows
+    factor = 1.0 + np.arange(3.0)
+    movie4d = g['volume'][None] * factor[:, None, None, None]
     img4 = emission.image_plane_dynamics((movie4d, float(g['axis'][-1] - g['axis'][0])), geos, g['Omega'], t,
                                          float(g['t_injection']), J=1.0, doppler=False)
-    assert relerr(img4, g['images']) < 1e-5
+    assert img4.shape == g['images'].shape and relerr(img4, g['images'] * factor[:, None, None]) < 1e-5
     with pytest.raises(AttributeError):
         emission.image_plane_dynamics(Vol(), geos, g['Omega'], t, 0.0, doppler=True)       # needs geos.g
     with pytest.raises(AttributeError):

@@ -10,7 +10,6 @@ import numpy as np
 import torch
 
 from . import _hip
-from .constants import GM_c3_hr
 
 COMPACT_POINTS = True          # point-level compaction of the domain mask for the fused kernels (RayGeometry.compact)
 COMPACT_BELOW = 0.9            # ... when less than this fraction of the samples is inside the domain
@@ -157,11 +156,24 @@ def ray_span(ray):
     return int((torch.div(ends, 32, rounding_mode='floor') - torch.div(starts, 32, rounding_mode='floor')).max().item()) + 1
 
 
-def frame_offsets(t_frames, t_start_obs, t_injection, GM_c3, device):
-    """tM0[b] = (t_frames[b]-t_start_obs)/GM_c3 - t_injection in float64 (emission.py:200-201)."""
+def _tM0_host(t_frames, t_start_obs, t_injection, GM_c3):
+    """tM0[b] = (t_frames[b]-t_start_obs)/GM_c3 - t_injection in float64 on the host (emission.py:200-201): the one place
+    that computes it, for the eager step (frame_offsets) and for the staging buffer of a captured one."""
     t = np.atleast_1d(np.asarray(t_frames, dtype=np.float64))
-    tM0 = (t - float(t_start_obs)) / float(GM_c3) - float(t_injection)
-    return _hip.h2d_small(np.asarray(tM0, dtype=np.float64), device)      # (pinned staging: no host stall, _hip._PinnedRing)
+    return (t - float(t_start_obs)) / float(GM_c3) - float(t_injection)
+
+
+def frame_offsets(t_frames, t_start_obs, t_injection, GM_c3, device):
+    """_tM0_host as a device tensor (pinned staging: no host stall, _hip._PinnedRing)."""
+    return _hip.h2d_small(_tM0_host(t_frames, t_start_obs, t_injection, GM_c3), device)
+
+
+def _frames(tM0, clock_probe=None):
+    """bhn_frames of a float64 device vector of frame offsets (and bench.py's clock-probe buffer)."""
+    assert tM0.dtype == torch.float64 and tM0.is_cuda and tM0.is_contiguous()
+    cp = clock_probe
+    assert cp is None or (cp.dtype == torch.int64 and cp.is_cuda and cp.numel() >= 4 * _hip.BHN_CLK_SLOTS)
+    return _hip.bhn_frames(int(tM0.numel()), tM0.data_ptr(), None if cp is None else cp.data_ptr())
 
 
 class FusedPredictor:
@@ -184,6 +196,8 @@ class FusedPredictor:
         self.packed = torch.empty((int(lib.bhn_packed_bytes(C.byref(self.model), self.mode)),), dtype=torch.uint8,
                                   device=self.device)
         self._ws = None
+        self.max_workspace_bytes = None     # cap of the backward workspace; None: a quarter of the device memory
+        self._t8_calibrated = False         # 8-bit tape: the scales in the workspace come from a backward call on it
         # posenc_deg > 4 or net_width > 256: the general layer-by-layer path (csrc/general_mlp.hip)
         self.general = posenc_deg > 4 or net_width > 256
         # queried once, here: torch's device-property query is not safe to call from two host threads at the same time
@@ -220,10 +234,7 @@ class FusedPredictor:
     clock_probe = None      # measurement aid (bench.py): an int64 device tensor of 4 * BHN_CLK_SLOTS entries -> bhn_frames.clock_probe
 
     def _frames(self, tM0):
-        assert tM0.dtype == torch.float64 and tM0.is_cuda and tM0.is_contiguous()
-        cp = self.clock_probe
-        assert cp is None or (cp.dtype == torch.int64 and cp.is_cuda and cp.numel() >= 4 * _hip.BHN_CLK_SLOTS)
-        return _hip.bhn_frames(int(tM0.numel()), tM0.data_ptr(), None if cp is None else cp.data_ptr())
+        return _frames(tM0, self.clock_probe)
 
     def tape_info(self, groups_per_frame):
         """bhn_tape_info: bytes of tape per 32-point group each kernel of the training step moves, and the layout flags."""
@@ -248,31 +259,50 @@ class FusedPredictor:
         full[:, k['idx']] = out[:, :k['n']]
         return full
 
-    @_on_device
-    def render(self, geom, tM0, out=None):
-        """image_plane_prediction (network.py:373-420) -> images (B, Sx, R) float32."""
+    def _forward(self, train, geom, tM0, out):
+        """The launch behind render (train False) and render_train (True: the tape goes to the workspace)."""
         B = int(tM0.numel())
         if out is None:
             out = torch.empty((B, geom.Sx, geom.R), dtype=torch.float32, device=self.device)
+        ws = self.workspace(B, geom.P_eff) if train else None
         gs, fs = geom.c_struct_fused(), self._frames(tM0)
-        _hip.check(_hip.lib().bhn_render_fwd(C.byref(self.model), self.mode, _hip.ptr(self.packed), C.byref(gs),
-                                             C.byref(fs), _hip.ptr(out), _hip.stream_ptr(self.device)))
+        lib = _hip.lib()
+        entry, tape = (lib.bhn_render_fwd_train, (_hip.ptr(ws), ws.numel())) if train else (lib.bhn_render_fwd, ())
+        timer = self.step_timer if train else None
+        if timer is not None:
+            timer.fwd_mark(0)
+        _hip.check(entry(C.byref(self.model), self.mode, _hip.ptr(self.packed), C.byref(gs), C.byref(fs), _hip.ptr(out), *tape,
+                         _hip.stream_ptr(self.device)))
+        if timer is not None:
+            timer.fwd_mark(1)
         return out
+
+    @_on_device
+    def render(self, geom, tM0, out=None):
+        """image_plane_prediction (network.py:373-420) -> images (B, Sx, R) float32."""
+        return self._forward(False, geom, tM0, out)
+
+    @_on_device
+    def render_train(self, geom, tM0, out=None):
+        """Training forward: images (B,Sx,R) + tape recorded in the workspace (see render_bwd_tape)."""
+        return self._forward(True, geom, tM0, out)
+
+    def _ws_bytes(self, B, P):
+        """bhn_render_bwd_workspace_bytes: what the backward of B frames of P points needs (0: error)."""
+        return int(_hip.lib().bhn_render_bwd_workspace_bytes(C.byref(self.model), self.mode, B, P, self.device.index or 0))
+
+    def _ws_cap(self):
+        cap = self.max_workspace_bytes
+        return self._total_memory // 4 if cap is None else cap
 
     @_on_device
     def workspace(self, B, P):
         """Backward workspace (slabs + tape).  Sized for all B frames when that fits under
         ``max_workspace_bytes`` (default 1/4 of the device memory), else for as many frames as fit;
         ``bhn_render_bwd`` then iterates over frame groups."""
-        lib = _hip.lib()
-        dev = self.device.index or 0
-        full = int(lib.bhn_render_bwd_workspace_bytes(C.byref(self.model), self.mode, B, P, dev))
-        one = int(lib.bhn_render_bwd_workspace_bytes(C.byref(self.model), self.mode, 1, P, dev))
+        full, one, cap = self._ws_bytes(B, P), self._ws_bytes(1, P), self._ws_cap()
         if full == 0 or one == 0:
-            raise _hip.HipError(lib.bhn_last_error().decode() or 'render_bwd workspace query failed')
-        cap = getattr(self, 'max_workspace_bytes', None)
-        if cap is None:
-            cap = self._total_memory // 4
+            raise _hip.HipError(_hip.lib().bhn_last_error().decode() or 'render_bwd workspace query failed')
         # fused paths: at least one frame of tape (what bhn_render_bwd needs).  General path: bhn_render_bwd walks the groups in
         # chunks of any size, so the cap is the cap -- one frame of an 8x512 network on 256 x 256 x 128 rays would be 277 GB
         want = min(full, cap) if self.general else min(full, max(one, cap))
@@ -288,7 +318,7 @@ class FusedPredictor:
         self._t8_calibrated = False
 
     def _bwd_mode(self):
-        if self.mode != _hip.BHN_BF16_T8 or getattr(self, '_t8_calibrated', False):
+        if self.mode != _hip.BHN_BF16_T8 or self._t8_calibrated:
             return self.mode
         return self.mode | _hip.BHN_T8_CALIBRATE
 
@@ -297,82 +327,47 @@ class FusedPredictor:
         if mode & _hip.BHN_T8_CALIBRATE:
             self._t8_calibrated = True
 
-    @_on_device
-    def render_bwd(self, geom, tM0, dimages, out=None):
-        """d loss / d params given d loss / d images (B,Sx,R): the reverse of ``render``."""
+    def _backward(self, entry, geom, tM0, dimages, out, timer=None):
+        """The launch behind render_bwd / render_bwd_tape; with bench.py's step timer the entry point that also takes the
+        caller's HIP events (bhn_render_bwd_tape_timed records them between the kernels of the call)."""
         assert dimages.dtype == torch.float32 and dimages.is_contiguous() and dimages.is_cuda
         if out is None:
             out = torch.empty((self.nparams,), dtype=torch.float32, device=self.device)
         ws = self.workspace(int(tM0.numel()), geom.P_eff)
         gs, fs = geom.c_struct_fused(), self._frames(tM0)
         mode = self._bwd_mode()
-        _hip.check(_hip.lib().bhn_render_bwd(C.byref(self.model), mode, _hip.ptr(self.packed), C.byref(gs),
-                                             C.byref(fs), _hip.ptr(dimages), _hip.ptr(out), _hip.ptr(ws), ws.numel(),
-                                             _hip.stream_ptr(self.device)))
+        events = () if timer is None else timer.bwd_events()
+        _hip.check(entry(C.byref(self.model), mode, _hip.ptr(self.packed), C.byref(gs), C.byref(fs), _hip.ptr(dimages),
+                         _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(self.device), *events))
         self._bwd_done(mode)
         return out
 
+    @_on_device
+    def render_bwd(self, geom, tM0, dimages, out=None):
+        """d loss / d params given d loss / d images (B,Sx,R): the reverse of ``render``."""
+        return self._backward(_hip.lib().bhn_render_bwd, geom, tM0, dimages, out)
+
+    @_on_device
+    def render_bwd_tape(self, geom, tM0, dimages, out=None):
+        """Gradient from the tape recorded by ``render_train`` (same geom / frames / packed weights)."""
+        timer = self.step_timer
+        if timer is not None:
+            return self._backward(_hip.lib().bhn_render_bwd_tape_timed, geom, tM0, dimages, out, timer)
+        return self._backward(_hip.lib().bhn_render_bwd_tape, geom, tM0, dimages, out)
 
     def fits_tape(self, B, P):
         """True when the workspace can hold the tape of all B frames (the recorded-tape fast path)."""
-        lib = _hip.lib()
-        full = int(lib.bhn_render_bwd_workspace_bytes(C.byref(self.model), self.mode, B, P, self.device.index or 0))
-        return 0 < full <= self.workspace(B, P).numel()
+        return 0 < self._ws_bytes(B, P) <= self.workspace(B, P).numel()
 
     def tape_group(self, B, P):
         """Largest number of frames (<= B) whose tape fits the workspace cap, 0 if not even one does: a training
         step whose loss is a sum of per-frame terms then runs frame group by frame group on the recorded-tape
         path instead of recomputing the forward (`bhn_render_bwd`)."""
-        lib = _hip.lib()
-        dev = self.device.index or 0
-        cap = getattr(self, 'max_workspace_bytes', None)
-        if cap is None:
-            cap = self._total_memory // 4
+        cap = self._ws_cap()
         for nb in range(int(B), 0, -1):
-            need = int(lib.bhn_render_bwd_workspace_bytes(C.byref(self.model), self.mode, nb, P, dev))
-            if 0 < need <= cap:
+            if 0 < self._ws_bytes(nb, P) <= cap:
                 return nb
         return 0
-
-    @_on_device
-    def render_train(self, geom, tM0, out=None):
-        """Training forward: images (B,Sx,R) + tape recorded in the workspace (see render_bwd_tape)."""
-        B = int(tM0.numel())
-        if out is None:
-            out = torch.empty((B, geom.Sx, geom.R), dtype=torch.float32, device=self.device)
-        ws = self.workspace(B, geom.P_eff)
-        gs, fs = geom.c_struct_fused(), self._frames(tM0)
-        timer = self.step_timer
-        if timer is not None:
-            timer.fwd_mark(0)
-        _hip.check(_hip.lib().bhn_render_fwd_train(C.byref(self.model), self.mode, _hip.ptr(self.packed), C.byref(gs),
-                                                   C.byref(fs), _hip.ptr(out), _hip.ptr(ws), ws.numel(),
-                                                   _hip.stream_ptr(self.device)))
-        if timer is not None:
-            timer.fwd_mark(1)
-        return out
-
-    @_on_device
-    def render_bwd_tape(self, geom, tM0, dimages, out=None):
-        """Gradient from the tape recorded by ``render_train`` (same geom / frames / packed weights)."""
-        assert dimages.dtype == torch.float32 and dimages.is_contiguous() and dimages.is_cuda
-        if out is None:
-            out = torch.empty((self.nparams,), dtype=torch.float32, device=self.device)
-        ws = self.workspace(int(tM0.numel()), geom.P_eff)
-        gs, fs = geom.c_struct_fused(), self._frames(tM0)
-        mode = self._bwd_mode()
-        timer = self.step_timer
-        if timer is not None:       # bench.py: the caller's HIP events between the kernels of this call (bhn_render_bwd_tape_timed)
-            ev, n_ev = timer.bwd_events()
-            _hip.check(_hip.lib().bhn_render_bwd_tape_timed(C.byref(self.model), mode, _hip.ptr(self.packed), C.byref(gs),
-                                                            C.byref(fs), _hip.ptr(dimages), _hip.ptr(out), _hip.ptr(ws), ws.numel(),
-                                                            _hip.stream_ptr(self.device), ev, n_ev))
-        else:
-            _hip.check(_hip.lib().bhn_render_bwd_tape(C.byref(self.model), mode, _hip.ptr(self.packed), C.byref(gs),
-                                                      C.byref(fs), _hip.ptr(dimages), _hip.ptr(out), _hip.ptr(ws), ws.numel(),
-                                                      _hip.stream_ptr(self.device)))
-        self._bwd_done(mode)
-        return out
 
 
 class RenderFunction(torch.autograd.Function):
@@ -415,9 +410,7 @@ class GridEngine:
         assert flat.dtype == torch.float32 and flat.numel() == self.nparams and flat.is_contiguous()
         self.grid = flat
 
-    def _frames(self, tM0):
-        assert tM0.dtype == torch.float64 and tM0.is_cuda and tM0.is_contiguous()
-        return _hip.bhn_frames(int(tM0.numel()), tM0.data_ptr())
+    _frames = staticmethod(_frames)
 
     @_on_device
     def predict(self, geom, tM0):

@@ -10,8 +10,6 @@ Data-parallel semantics (network.py:620): each process (one per GPU) c
 chi^2 over its own frames, gradients are AVERAGED over processes with one RCCL all-reduce of the
 flat gradient buffer, then every rank applies the identical Adam update.
 """
-import glob
-import os
 from collections import OrderedDict
 from pathlib import Path
 
@@ -122,8 +120,7 @@ class TrainState:
         vector of the completed step (first step: this rank's own loss in every slot; no update yet)."""
         import torch.distributed as dist
         prev = self._pending
-        buf[n:].zero_()
-        buf[n + rank] = loss.reshape(-1)[0]
+        _fill_loss_slots(buf, n, loss, rank)
         self._pending = (dist.all_reduce(buf, async_op=True), buf)
         if prev is None:                        # no completed step yet: this rank's own loss in every slot (a NaN filler
             return loss.reshape(-1)[:1].expand(world).clone()      # would reach Optimizer.loss, the log functions and every mean)
@@ -184,12 +181,6 @@ class TrainState:
         self.step = int(np.asarray(sd.get('step', adam.get('count', 0))))
         return self
 
-    def state_dict(self):
-        return self.to_state_dict()
-
-    def load_state_dict(self, sd):
-        return self.from_state_dict(sd)
-
 
 def _fingerprint(v):
     """Cache key of one ray-tracing argument (NeRF_Predictor.geometry): identity + what an in-place edit would change.
@@ -241,6 +232,7 @@ class NeRF_Predictor:
         self.out_channel, self.do_skip = out_channel, do_skip
         self.mode, self.device = mode, device
         self._engine, self._engine_key, self._geoms = None, None, OrderedDict()
+        self._graph_epoch = 0               # bumped by clear_geometry_cache: captured training steps are dropped with it
 
     # -- engine / geometry caches ----------------------------------------------------------------
     def engine(self):
@@ -276,7 +268,7 @@ class NeRF_Predictor:
 
     def clear_geometry_cache(self):
         self._geoms.clear()
-        self._graph_epoch = getattr(self, '_graph_epoch', 0) + 1      # captured training steps (optimization.GraphedImageStep) are dropped too
+        self._graph_epoch += 1              # captured training steps (optimization.GraphedImageStep) are dropped too
 
     # -- reference API -----------------------------------------------------------------------------
     def init_params(self, raytracing_args=None, seed=1):
@@ -316,18 +308,20 @@ class NeRF_Predictor:
 
     __call__ = apply
 
-    def save_params(self, directory, filename='NeRF_Predictor_params.yml'):
+    # what save_params writes and from_yml hands back to the constructor (network.py:242), and the file's default name
+    _yml_keys = ('scale', 'rmin', 'rmax', 'z_width', 'posenc_deg', 'posenc_var', 'net_depth', 'net_width', 'out_channel', 'do_skip')
+    _yml_name = 'NeRF_Predictor_params.yml'
+
+    def save_params(self, directory, filename=None):
         directory = Path(directory)
         directory.mkdir(parents=True, exist_ok=True)
-        keys = ['scale', 'rmin', 'rmax', 'z_width', 'posenc_deg', 'posenc_var', 'net_depth', 'net_width',
-                'out_channel', 'do_skip']                                       # network.py:242
-        with open(directory.joinpath(filename), 'w') as f:
+        with open(directory.joinpath(filename or self._yml_name), 'w') as f:
             yaml.dump({k: (float(getattr(self, k)) if isinstance(getattr(self, k), (float, np.floating))
-                           else getattr(self, k)) for k in keys}, f)
+                           else getattr(self, k)) for k in self._yml_keys}, f)
 
     @classmethod
-    def from_yml(cls, directory, filename='NeRF_Predictor_params.yml', **kw):
-        params = yaml.safe_load(Path(directory).joinpath(filename).read_text())
+    def from_yml(cls, directory, filename=None, **kw):
+        params = yaml.safe_load(Path(directory).joinpath(filename or cls._yml_name).read_text())
         return cls(**params, **kw)
 
 
@@ -336,10 +330,14 @@ class GRID_Predictor(NeRF_Predictor):
     parameters ``{'grid': (res,res,res)}`` initialised to -10 (network.py:334).  Same driver interface as
     NeRF_Predictor (``init_params / init_state / apply / save_params / from_yml``); kernels ``bhn_grid_*``."""
 
+    # (the reference's key list is the NeRF one, network.py:359, and so writes only the first four; grid_res is added so that
+    #  from_yml can rebuild the predictor)
+    _yml_keys = ('scale', 'rmin', 'rmax', 'z_width', 'grid_res')
+    _yml_name = 'GRID_Predictor_params.yml'
+
     def __init__(self, scale=1.0, rmin=0.0, rmax=np.inf, z_width=np.inf, grid_res=64, *, device=None, mode='f32'):
-        self.scale, self.rmin, self.rmax, self.z_width, self.grid_res = scale, rmin, rmax, z_width, int(grid_res)
-        self.device, self.mode = device, 'f32'
-        self._engine, self._engine_key, self._geoms = None, None, OrderedDict()
+        super().__init__(scale, rmin, rmax, z_width, mode='f32', device=device)
+        self.grid_res = int(grid_res)
 
     def engine(self):
         key = (self.scale, self.grid_res)
@@ -357,23 +355,17 @@ class GRID_Predictor(NeRF_Predictor):
         tree.flat = flat
         return tree
 
-    def save_params(self, directory, filename='GRID_Predictor_params.yml'):
-        directory = Path(directory)
-        directory.mkdir(parents=True, exist_ok=True)
-        # (the reference's key list is the NeRF one, network.py:359, and so writes only these four; grid_res is added so
-        #  that from_yml can rebuild the predictor)
-        with open(directory.joinpath(filename), 'w') as f:
-            yaml.dump({k: (float(getattr(self, k)) if isinstance(getattr(self, k), (float, np.floating)) else getattr(self, k))
-                       for k in ('scale', 'rmin', 'rmax', 'z_width', 'grid_res')}, f)
-
-    @classmethod
-    def from_yml(cls, directory, filename='GRID_Predictor_params.yml', **kw):
-        params = yaml.safe_load(Path(directory).joinpath(filename).read_text())
-        return cls(**params, **kw)
-
 
 def latest_checkpoint(checkpoint_dir):
     return checkpoints.latest_checkpoint(checkpoint_dir) if checkpoint_dir else None
+
+
+def _time_origin(t_start_obs, t_units):
+    """(t_start_obs as a float, GM/c^3 in the unit of time): a unit-carrying t_start_obs sets the unit, else `t_units` does
+    (emission.py:176-185)."""
+    if units.is_quantity(t_start_obs):
+        t_units, t_start_obs = t_start_obs.unit, t_start_obs.value
+    return float(t_start_obs), constants.GM_c3(t_units)
 
 
 def _frame_offsets(t_frames, t_units, t_start_obs, t_injection, device):
@@ -381,12 +373,9 @@ def _frame_offsets(t_frames, t_units, t_start_obs, t_injection, device):
     if isinstance(t_frames, torch.Tensor) and t_frames.dtype == torch.float64 and t_frames.is_cuda \
             and getattr(t_frames, '_bhn_is_tM0', False):
         return t_frames, False
-    if units.is_quantity(t_start_obs):
-        t_units = t_start_obs.unit
-        t_start_obs = float(t_start_obs.value)
-    GM_c3 = constants.GM_c3(t_units) if t_units is not None else 1.0
     if units.is_quantity(t_frames):
-        t_frames = t_frames.to(t_units).value
+        t_frames = t_frames.to(getattr(t_start_obs, 'unit', t_units)).value
+    t_start_obs, GM_c3 = _time_origin(t_start_obs, t_units)
     if isinstance(t_frames, torch.Tensor):
         t_frames = t_frames.detach().cpu().numpy()
     tf = np.asarray(t_frames, dtype=np.float64)
@@ -468,6 +457,12 @@ def loss_fn_eht(params, predictor_fn, target, sigma, A, t_frames, coords, Omega,
     return loss, [images]
 
 
+def _fill_loss_slots(buf, n, loss, rank):
+    """The loss slots behind the gradient in the all-reduce message: this rank's loss in its own slot, zero in the others."""
+    buf[n:].zero_()
+    buf[n + rank] = loss.reshape(-1)[0]
+
+
 def dp_allreduce(buf, n, loss, rank, world):
     """The one collective of a training step (network.py:620): ``buf[:n]`` holds this rank's gradient
     of its per-device chi^2 SUM; slots ``buf[n:n+world]`` carry the per-rank losses so that a single
@@ -476,31 +471,51 @@ def dp_allreduce(buf, n, loss, rank, world):
     if world == 1 and not _dist_on():
         return loss
     import torch.distributed as dist        # (an initialised process group of ONE rank still runs the collective: the RCCL
-    buf[n:].zero_()                         #  path of a single-GPU box, tests/test_gpu_ddp.py)
-    buf[n + rank] = loss.reshape(-1)[0]
+    _fill_loss_slots(buf, n, loss, rank)    #  path of a single-GPU box, tests/test_gpu_ddp.py)
     dist.all_reduce(buf)                                  # RCCL over xGMI on GPUs; gloo in the CPU tests
     return buf[n:].clone()
 
 
 def _exchange_and_apply(state, buf, n, loss, rank, world):
     """jax.lax.pmean(grads) + apply_gradients (network.py:620-621): one all-reduce, Adam with grad / world."""
-    if (world > 1 or _dist_on()) and getattr(state, 'overlap_allreduce', False):
+    if (world > 1 or _dist_on()) and state.overlap_allreduce:
         return state.exchange_overlapped(buf, n, loss, rank, world)
     loss_vec = dp_allreduce(buf, n, loss, rank, world)
     state.apply_gradients(buf[:n], grad_scale=1.0 / world)
     return loss_vec
 
 
+def _image_operands(geom, B, dtype, operands, device):
+    """target / sigma / offset of B frames as float32 device tensors in the layout of bhn_chi2_image: per pixel ('full') or
+    per Stokes plane ('lc')."""
+    tshape = (B, geom.Sx, geom.R) if dtype == 'full' else (B, geom.Sx)
+    return [_hip.as_f32(v, device).reshape(tshape) for v in operands]
+
+
+def _pass(eng, geom, tM0, images, chi2, grad, taped):
+    """The launches of one pass over the frames `tM0` -- THE body of the eager step, of every slice of the frame-grouped step
+    and of the captured step (optimization.GraphedImageStep): forward into `images` (None: a new tensor), chi2(images) ->
+    (loss, d loss / d images) and, given a gradient buffer, the backward into it: from the tape the forward recorded
+    (`taped`) or re-running the forward.  Returns (loss, images)."""
+    images = (eng.render_train if taped else eng.render)(geom, tM0, out=images)
+    loss, dimg = chi2(images)
+    if grad is not None:
+        (eng.render_bwd_tape if taped else eng.render_bwd)(geom, tM0, dimg, out=grad)
+    return loss, images
+
+
+def _slot_images(images, geom):
+    """(B,Sx,R) -> (1, B, [S], *spatial): the leading axis is this process's "device" slot of the reference's pmap output."""
+    return images.reshape((1, images.shape[0]) + ((geom.S,) if geom.S else ()) + geom.spatial)
+
+
 def _step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, Omega, J, g, dtau, Sigma,
                 t_start_obs, t_geos, t_injection, scale, train, eht=False):
     """Per-process body of gradient_step_image/_eht and test_image/_eht with no torch.autograd in the
-    loop: pack -> fused render -> chi^2 kernel -> fused backward -> all-reduce -> Adam.  For the EHT
+    loop: pack -> `_pass` (fused render -> chi^2 kernel -> fused backward) -> all-reduce -> Adam.  For the EHT
     losses ``offset`` carries the DFT matrices A."""
-    if eht:
-        if dtype not in engine.EHT_DTYPES:
-            raise AttributeError('eht dtype ({}) not supported'.format(dtype))
-    elif dtype not in ('full', 'lc'):
-        raise AttributeError('image dtype ({}) not supported'.format(dtype))
+    if dtype not in (engine.EHT_DTYPES if eht else ('full', 'lc')):
+        raise AttributeError('{} dtype ({}) not supported'.format('eht' if eht else 'image', dtype))
     pred = state.predictor
     eng = pred.engine()
     dev = eng.device
@@ -510,54 +525,40 @@ def _step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, 
     eng.pack(state.flat)
     taped = train and eng.fits_tape(B, geom.P_eff)      # record the tape while rendering: no recompute later
     group = eng.tape_group(B, geom.P_eff) if (train and not taped and not eht) else 0
-    if group:
-        # the tape of all B frames does not fit, but chi^2 is a sum of per-frame terms: frame groups on the taped path
-        tshape = (B, geom.Sx, geom.R) if dtype == 'full' else (B, geom.Sx)
-        tgt, sig, off = (_hip.as_f32(v, dev).reshape(tshape) for v in (target, sigma, offset))
+    staged = lambda: _image_operands(geom, B, dtype, (target, sigma, offset), dev)
+    if eht:
+        chi2 = lambda im: engine.chi2_eht(im, offset, target, sigma, scale, dtype, want_grad=train)
+    else:       # (host arrays are staged after the forward has been enqueued: the copy runs under it)
+        chi2 = lambda im: engine.chi2_image(im, *staged(), scale, dtype, want_grad=train)
+    n = eng.nparams
+    buf = state.grad_buffer() if train else None
+    if not group:
+        loss, images = _pass(eng, geom, tM0, None, chi2, buf[:n] if train else None, taped)
+    else:
+        # the tape of all B frames does not fit, but chi^2 is a sum of per-frame terms: frame groups on the taped path.  The
+        # first group's gradient goes straight to the buffer, the later ones are added to it; the loss is summed from zero
+        ops = staged()
         images = torch.empty((B, geom.Sx, geom.R), dtype=torch.float32, device=dev)
-        n = eng.nparams
-        buf = state.grad_buffer()
         part = torch.empty((n,), dtype=torch.float32, device=dev)
         loss = torch.zeros((1,), dtype=torch.float32, device=dev)
         for b0 in range(0, B, group):
             sl = slice(b0, min(b0 + group, B))
-            eng.render_train(geom, tM0[sl], out=images[sl])
-            lg, dimg = engine.chi2_image(images[sl], tgt[sl].contiguous(), sig[sl].contiguous(), off[sl].contiguous(), scale, dtype)
-            loss += lg
-            if b0 == 0:
-                eng.render_bwd_tape(geom, tM0[sl], dimg, out=buf[:n])
-            else:
-                eng.render_bwd_tape(geom, tM0[sl], dimg, out=part)
+            loss += _pass(eng, geom, tM0[sl], images[sl],
+                          lambda im: engine.chi2_image(im, *(v[sl].contiguous() for v in ops), scale, dtype),
+                          part if b0 else buf[:n], True)[0]
+            if b0:
                 buf[:n] += part
-        rank, world = _world()
-        loss_vec = _exchange_and_apply(state, buf, n, loss, rank, world)
-        out = images.reshape((1, B) + ((geom.S,) if geom.S else ()) + geom.spatial)
-        return loss_vec, state, out
-    images = eng.render_train(geom, tM0) if taped else eng.render(geom, tM0)
-    if eht:
-        loss, dimg = engine.chi2_eht(images if geom.S else images[:, 0], offset, target, sigma, scale, dtype, want_grad=train)
-        dimg = dimg.reshape(images.shape) if train else None
-    else:
-        tshape = (B, geom.Sx, geom.R) if dtype == 'full' else (B, geom.Sx)
-        tgt, sig, off = (_hip.as_f32(v, dev).reshape(tshape) for v in (target, sigma, offset))
-        loss, dimg = engine.chi2_image(images, tgt, sig, off, scale, dtype, want_grad=train)
     rank, world = _world()
     if train:
-        n = eng.nparams
-        buf = state.grad_buffer()
-        (eng.render_bwd_tape if taped else eng.render_bwd)(geom, tM0, dimg, out=buf[:n])
         loss_vec = _exchange_and_apply(state, buf, n, loss, rank, world)
+    elif world > 1:
+        import torch.distributed as dist
+        parts = [torch.empty_like(loss) for _ in range(world)]
+        dist.all_gather(parts, loss)
+        loss_vec = torch.cat(parts)
     else:
-        if world > 1:
-            import torch.distributed as dist
-            parts = [torch.empty_like(loss) for _ in range(world)]
-            dist.all_gather(parts, loss)
-            loss_vec = torch.cat(parts)
-        else:
-            loss_vec = loss
-    # leading axis = this process's "device" slot of the reference's pmap output
-    out = images.reshape((1, B) + ((geom.S,) if geom.S else ()) + geom.spatial)
-    return loss_vec, state, out
+        loss_vec = loss
+    return loss_vec, state, _slot_images(images, geom)
 
 
 def gradient_step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, Omega, J, g, dtau, Sigma,

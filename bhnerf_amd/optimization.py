@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import checkpoints, network, units
+from . import _hip, checkpoints, engine, network, units
 
 try:  # progress bar is optional
     from tqdm.auto import tqdm
@@ -174,7 +174,8 @@ class GraphedImageStep:
     which is what a GPU needs when its share of a step is a single small frame (the reference's b = 8 on 8 devices,
     optimization.py:289-291).  With an RCCL process group the all-reduce and Adam are captured too (`collective_in_graph`);
     when the backend cannot be captured (gloo) the graph ends at the gradient and the exchange + Adam follow eagerly.
-    The arithmetic is the un-captured step's, kernel for kernel: parameters are bitwise equal (tests/test_gpu_api.py).
+    What is captured is the eager step's own body (`network._pass`, called by `_body` on the graph's buffers), so the
+    arithmetic is the un-captured step's, kernel for kernel: parameters are bitwise equal (tests/test_gpu_api.py).
 
     A HIP graph bakes raw device addresses in.  The step therefore keeps a reference to everything it captured (ray-tracing
     dict, geometry, workspace, parameters, Adam moments, gradient buffer) and `stale()` compares them with what an eager step
@@ -184,30 +185,22 @@ class GraphedImageStep:
     the next step on this ray set overwrites (the reference's training loop discards it: optimization.py:132)."""
 
     def __init__(self, state, args, dtype, scale, rt, n_local):
-        from . import engine, _hip
         pred = state.predictor
         eng = pred.engine()
         self.state, self.eng, self.args, self.dtype, self.scale = state, eng, args, dtype, float(scale)
         self.rt, self.pred = rt, pred                                          # (kept alive: the cache key holds their ids)
-        self.epoch = getattr(pred, '_graph_epoch', 0)
+        self.epoch = pred._graph_epoch
         dev = eng.device
         self.geom = geom = self._geometry()
         B = self.B = int(n_local)
         if not eng.fits_tape(B, geom.P_eff):
             raise ValueError('the tape of %d frames does not fit the workspace: no graph for this step' % B)
-        t_start, t_units = rt['t_start_obs'], args.t_units
-        if units.is_quantity(t_start):
-            t_units, t_start = t_start.unit, float(t_start.value)
-        from . import constants
-        self.GM = constants.GM_c3(t_units) if t_units is not None else 1.0
-        self.t_start, self.t_inj = float(t_start), float(rt['t_injection'])
-        args[np.arange(min(args.num_frames, network._world()[1]))]            # (makes the device-resident copies of the per-frame arrays)
+        (self.t_start, self.GM), self.t_inj = network._time_origin(rt['t_start_obs'], args.t_units), float(rt['t_injection'])
         # whole-movie target, sigma, offset as ONE tensor (the batch is gathered by a single index_select): the stack
         # TemporalBatchedArgs keeps for its own gathers -- no third device copy of the movie
-        if args._stack is None or args._stack.shape[0] != 3 or args._stack.dtype != torch.float32:
+        self.full = args.device_stack()
+        if self.full is None or self.full.shape[0] != 3 or self.full.dtype != torch.float32:
             raise ValueError('target / sigma / offset of one shape and dtype expected: no graph for this step')
-        self.full = args._stack
-        self.tshape = (B, geom.Sx, geom.R) if dtype == 'full' else (B, geom.Sx)
         # per-step inputs: a ring of pinned staging slots (the host runs ahead of the GPU: a slot is rewritten only after the
         # copies issued from it have executed), three device buffers the graph reads
         # (one buffer [idx: B int64 | tM0: B float64 | lr, 1-b1^t, 1-b2^t, pad: 4 float32] = ONE copy per step; the host writes
@@ -255,7 +248,7 @@ class GraphedImageStep:
     def stale(self):
         """True when an eager step would no longer use what this graph captured (see the class docstring)."""
         st, eng = self.state, self.eng
-        if self.pred.engine() is not eng or getattr(self.pred, '_graph_epoch', 0) != self.epoch:
+        if self.pred.engine() is not eng or self.pred._graph_epoch != self.epoch:
             return True
         if self._geometry() is not self.geom:                  # edited ray set / evicted and rebuilt geometry
             return True
@@ -269,15 +262,13 @@ class GraphedImageStep:
         return not (eng._ws is ws and st.flat is flat and st.m is m and st.v is v and st.grad_buffer() is grad)
 
     def _body(self):
-        from . import engine
+        """What the graph holds: the eager step's own pass (network._pass) on the graph's buffers, then Adam from device scalars."""
         st, eng, geom = self.state, self.eng, self.geom
         eng.pack(st.flat)
-        tgt, sig, off = (a.reshape(self.tshape) for a in self.full.index_select(1, self.d_idx))
-        images = eng.render_train(geom, self.d_tM0, out=self.images)
-        loss, dimg = engine.chi2_image(images, tgt, sig, off, self.scale, self.dtype)
+        ops = network._image_operands(geom, self.B, self.dtype, self.full.index_select(1, self.d_idx), eng.device)
         buf = st.grad_buffer()
-        eng.render_bwd_tape(geom, self.d_tM0, dimg, out=buf[:self.n])
-        lossv = loss
+        loss = lossv = network._pass(eng, geom, self.d_tM0, self.images, lambda im: engine.chi2_image(im, *ops, self.scale, self.dtype),
+                                     buf[:self.n], True)[0]
         if self.collective_in_graph:
             rank, world = network._world()
             lossv = network.dp_allreduce(buf, self.n, loss, rank, world)            # (the reference's pmean, network.py:620)
@@ -287,7 +278,6 @@ class GraphedImageStep:
         return loss, lossv, buf
 
     def _stage(self, key):
-        from . import engine
         st = self.state
         sl = self.slots[self.slot_i]
         self.slot_i = (self.slot_i + 1) % len(self.slots)
@@ -295,7 +285,7 @@ class GraphedImageStep:
             sl['done'].synchronize()                       # (waits only when the GPU is a whole ring behind the host)
         self.slot_used += 1
         sl['idx'][:] = key
-        sl['tM0'][:] = (self.args.t_values[key] - self.t_start) / self.GM - self.t_inj          # engine.frame_offsets, float64
+        sl['tM0'][:] = engine._tM0_host(self.args.t_values[key], self.t_start, self.t_inj, self.GM)
         sl['hyp'][:] = engine.adam_hyper(st.step + 1, st.learning_rate())
         self.d_buf.copy_(sl['buf'], non_blocking=True)
         sl['done'].record()
@@ -352,7 +342,7 @@ class GraphedImageStep:
 
     def __call__(self, key):
         """key: this rank's frame indices of the step (length B).  Returns (loss vector, state, images (1, B, [S], H, W))."""
-        st, geom = self.state, self.geom
+        st = self.state
         assert len(key) == self.B
         self._stage(key)
         if self.graph is None:
@@ -364,8 +354,18 @@ class GraphedImageStep:
             loss_vec = self.lossv.clone()
         else:
             loss_vec = network._exchange_and_apply(st, self.buf, self.n, self.loss, rank, world)
-        out = self.images.reshape((1, self.B) + ((geom.S,) if geom.S else ()) + geom.spatial)
-        return loss_vec, st, out
+        return loss_vec, st, network._slot_images(self.images, self.geom)
+
+
+class _NoGraph:
+    """Falsy entry of TrainStep._graphs for a step that cannot be captured.  It keeps (state, rt) alive, as a captured step
+    does: the ids in its cache key cannot be recycled while it stands, so it never needs the `matches` check."""
+
+    def __init__(self, *refs):
+        self.refs = refs
+
+    def __bool__(self):
+        return False
 
 
 class TrainStep(object):
@@ -399,27 +399,19 @@ class TrainStep(object):
     def _graphed(self, state, rt, indices):
         key = shard(np.atleast_1d(np.asarray(indices)))
         gkey = (id(rt), len(key), id(state))
-        g = self._graphs.get(gkey)
-        if g is not None and g is not False and (not g.matches(state, rt) or g.stale()):
+        g = self._graphs.pop(gkey, None)
+        if g and (not g.matches(state, rt) or g.stale()):
             # another object at a recycled id, or the step would no longer run on what was captured (re-allocated workspace,
             # replaced state tensors, edited ray set, cleared geometry cache): never replay it
-            del self._graphs[gkey]
             g = None
         if g is None:
             try:
                 g = GraphedImageStep(state, self.args[0], str(self.dtype[0]), float(self.scale[0]), rt, len(key))
             except ValueError:
-                g = False                                  # (tape does not fit / arguments of mixed shapes: this step stays eager)
-            self._graphs[gkey] = g if g else False
-            if g is False:
-                self._nograph_refs = getattr(self, '_nograph_refs', {})
-                self._nograph_refs[gkey] = (rt, state)     # (keeps the ids of a "no graph" entry from being recycled)
-            while len(self._graphs) > self.MAX_GRAPHS:
-                old = next(iter(self._graphs))
-                self._graphs.pop(old)
-                getattr(self, '_nograph_refs', {}).pop(old, None)
-        else:
-            self._graphs[gkey] = self._graphs.pop(gkey)    # LRU order
+                g = _NoGraph(state, rt)                    # (tape does not fit / arguments of mixed shapes: this step stays eager)
+        self._graphs[gkey] = g                             # (re-inserted at the end: LRU order)
+        while len(self._graphs) > self.MAX_GRAPHS:
+            self._graphs.pop(next(iter(self._graphs)))
         return g(key) if g else None
 
     def __call__(self, state, raytracing_args, indices, update_state=True):
@@ -430,7 +422,7 @@ class TrainStep(object):
             ray_sets = [ray_sets[int(self._rng.integers(len(ray_sets)))]]
         fns = self.grad_pmap if update_state else self.test_pmap
         if (update_state and self.use_graph and self.num_losses == 1 and fns[0] is network.gradient_step_image
-                and torch.cuda.is_available() and not getattr(state, 'overlap_allreduce', False)
+                and torch.cuda.is_available() and not state.overlap_allreduce
                 and type(state.predictor) is network.NeRF_Predictor):
             res = self._graphed(state, ray_sets[0], indices)
             if res is not None:
@@ -519,19 +511,24 @@ class TemporalBatchedArgs(object):
         """Random frame batch; identical on every rank (same seed, same call sequence)."""
         return self._rng.choice(self.num_frames, batchsize, replace=replace)
 
+    def device_stack(self):
+        """The per-frame arrays on the current device, copied there on first use, as ONE (nargs, nt, ...) tensor when they
+        have one shape and dtype (target / sigma / offset of an image-plane loss: a batch is then gathered by one kernel),
+        else None."""
+        if self._dev is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+            self._dev = [torch.as_tensor(a, device=dev) for a in self.host_args]
+            same = len(self._dev) > 1 and len({(tuple(a.shape), a.dtype) for a in self._dev}) == 1
+            self._stack = torch.stack(self._dev) if same else None
+        return self._stack
+
     def __getitem__(self, key):
         key = shard(np.atleast_1d(np.asarray(key)))
         if torch.cuda.is_available():
-            if self._dev is None:
-                dev = torch.device('cuda', torch.cuda.current_device())
-                self._dev = [torch.as_tensor(a, device=dev) for a in self.host_args]
-                # arguments of one shape and dtype (target / sigma / offset of an image-plane loss) are gathered by ONE kernel
-                same = len(self._dev) > 1 and len({(tuple(a.shape), a.dtype) for a in self._dev}) == 1
-                self._stack = torch.stack(self._dev) if same else None
-            from . import _hip
+            stack = self.device_stack()
             idx = _hip.h2d_small(np.asarray(key, dtype=np.int64), self._dev[0].device if self._dev else 'cuda')
-            if self._stack is not None:
-                out = list(self._stack.index_select(1, idx))
+            if stack is not None:
+                out = list(stack.index_select(1, idx))
             else:
                 out = [a.index_select(0, idx) for a in self._dev]
         else:

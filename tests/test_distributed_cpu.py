@@ -92,6 +92,7 @@ class _StubEngine:
         self.nl = len(trainer.k)
         self.nparams = sum(p.numel() for p in trainer.k + trainer.b)
         self.calls = []
+        self.fits, self.group = True, 0        # what fits_tape / tape_group report (a capped workspace: False, frames per group)
 
     def _params_flax_order(self):
         return [p for i in range(self.nl) for p in (self.tr.k[i], self.tr.b[i])]
@@ -108,13 +109,17 @@ class _StubEngine:
                 off += p.numel()
 
     def fits_tape(self, B, P):
-        return True
+        return self.fits
+
+    def tape_group(self, B, P):
+        return min(self.group, B)
 
     def render_train(self, geom, tM0, out=None):
         self.calls.append('render')
         t_frames = (tM0.double() + self.tinj) * self.GM + self.t0
         self._images = self.tr.forward(t_frames)
-        return self._images.detach().float().reshape(tM0.numel(), 1, -1)
+        images = self._images.detach().float().reshape(tM0.numel(), 1, -1)
+        return images if out is None else out.copy_(images)
 
     render = render_train
 
@@ -280,3 +285,67 @@ def test_two_rank_overlapped_allreduce_is_the_one_step_stale_update():
     assert np.abs(res[0][1] - ref).max() < 2e-3 * moved
     # the loss vectors returned by steps 2 and 3 are those of the completed steps 1 and 2
     assert res[0][2].shape == (2, 2) and np.allclose(res[0][2].sum(axis=1), ref_losses[:2], rtol=2e-5)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The same driver in one process without a process group: the three routes of network._step_image (single taped pass,
+# frame groups under a capped workspace, test mode) issue the calls they are documented to issue.
+# ---------------------------------------------------------------------------------------------------------------
+def _single_process_step(monkeypatch, train=True, fits=True, group=0):
+    import sys
+    import types
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, 'tests'))
+    from bhnerf_amd import network, units
+    from oracle import oracle_np as onp
+    import test_oracle_golden as tg
+    g = dict(np.load(os.path.join(root, 'tests', 'golden', 'g5_predict_e.npz')))      # 4 frames, 4x128
+    tr, t = tg._torch_trainer(g)
+    eng = _StubEngine(tr, g['t_start_obs'], g['t_injection'], onp.GM_C3_SGRA_HR)
+    eng.fits, eng.group = fits, group
+    H, W = g['coords'].shape[1:3]
+    pred = types.SimpleNamespace(engine=lambda: eng, geometry=lambda *a, **k: types.SimpleNamespace(P_eff=H * W, S=0, Sx=1, R=H * W, spatial=(H, W)))
+    slice_losses = []
+
+    def chi2_image(images, target, sigma, offset, scale, dtype, want_grad=True):       # engine.chi2_image ('full')
+        d = (images - target - offset) / sigma
+        slice_losses.append((scale * (d * d).sum()).reshape(1))
+        return slice_losses[-1], (2.0 * scale * d / sigma if want_grad else None)
+
+    def adam_step(params, grads, m, v, tcount, lr, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0):
+        eng.calls.append('adam(grad_scale=%g)' % grad_scale)
+
+    monkeypatch.setattr(network.engine, 'chi2_image', chi2_image)
+    monkeypatch.setattr(network.engine, 'adam_step', adam_step)
+    state = network.TrainState(None, eng.flatten(), pred, 3, 1e-3, 1e-4)
+    tgt, sig, off = (g[k + '_full'].reshape(4, H, W).astype(np.float32) for k in ('target', 'sigma', 'offset'))
+    fn = network.gradient_step_image if train else network.test_image
+    loss, state, images = fn(state, units.hr, 'full', tgt, sig, off, g['t_frames'], g['coords'], g['Omega'], 1.0, g['g'], g['dtau'],
+                             g['Sigma'], float(g['t_start_obs']), g['t_geos'], float(g['t_injection']), 1.0)
+    return eng, state, loss, images, slice_losses, (H, W)
+
+
+def test_frame_grouped_step_runs_slice_by_slice_and_sums_the_loss_in_slice_order(monkeypatch):
+    """fits_tape False, tape_group 2, four frames: two taped passes, ONE Adam step; the loss is the float32 sum of the slice
+    losses added in slice order onto zero; the images of all four frames come back."""
+    eng, state, loss, images, slice_losses, (H, W) = _single_process_step(monkeypatch, fits=False, group=2)
+    assert eng.calls == ['pack', 'render', 'bwd', 'render', 'bwd', 'adam(grad_scale=1)'], eng.calls
+    assert len(slice_losses) == 2
+    want = torch.zeros((1,), dtype=torch.float32)
+    want += slice_losses[0]
+    want += slice_losses[1]
+    assert loss.dtype == torch.float32 and torch.equal(loss, want)
+    assert images.shape == (1, 4, H, W) and state.step == 1
+
+
+def test_single_pass_step_is_one_render_and_one_backward(monkeypatch):
+    eng, state, loss, images, slice_losses, (H, W) = _single_process_step(monkeypatch)
+    assert eng.calls == ['pack', 'render', 'bwd', 'adam(grad_scale=1)'], eng.calls
+    assert len(slice_losses) == 1 and torch.equal(loss, slice_losses[0])
+    assert images.shape == (1, 4, H, W) and state.step == 1
+
+
+def test_test_mode_step_renders_only_and_leaves_the_state_alone(monkeypatch):
+    eng, state, loss, images, slice_losses, (H, W) = _single_process_step(monkeypatch, train=False)
+    assert eng.calls == ['pack', 'render'], eng.calls
+    assert state.step == 0 and images.shape == (1, 4, H, W) and loss.shape == (1,)

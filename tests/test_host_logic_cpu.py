@@ -289,3 +289,49 @@ def test_bench_dump_outputs_dtypes_cap_and_fixed_sample(tmp_path):
     for f in files:
         a, b = np.load(tmp_path / 'b' / f), np.load(tmp_path / 'c' / f)
         assert a.size < big[f[0]].size and np.array_equal(a, b) and np.isin(a, big[f[0]]).all()
+
+
+def test_host_frame_offsets_keep_the_float64_formula_of_frame_offsets(golden):
+    """engine._tM0_host is the one computation of tM0 (engine.frame_offsets copies it to the device, a captured step writes it
+    to its staging buffer): exactly tM0[b] = (t_frames[b] - t_start_obs) / GM_c3 - t_injection in float64, and
+    network._time_origin takes origin and unit from a unit-carrying t_start_obs."""
+    from bhnerf_amd import engine
+    g = golden('g5_predict_e')
+    t = np.asarray(g['t_frames'], dtype=np.float64)
+    t0, t_inj, GM = 0.25, float(g['t_injection']), constants.GM_c3('hr')
+    want = (t - float(t0)) / float(GM) - float(t_inj)
+    got = engine._tM0_host(g['t_frames'], t0, t_inj, GM)
+    assert got.dtype == np.float64 and got.shape == t.shape and np.array_equal(got, want)
+    assert np.array_equal(engine._tM0_host(t[[2, 0]], t0, t_inj, GM), want[[2, 0]])           # (a captured step's batch of frame times)
+    assert np.array_equal(engine._tM0_host(float(t[1]), t0, t_inj, GM), want[1:2])           # a scalar frame time: one frame
+    dev = engine.frame_offsets(g['t_frames'], t0, t_inj, GM, 'cpu')
+    assert dev.dtype == torch.float64 and np.array_equal(dev.numpy(), want)
+    # a unit-carrying t_start_obs decides the unit (here minutes although t_units says hours), a plain one leaves it to t_units
+    start, GM_min = network._time_origin(15.0 * units.min, units.hr)
+    assert start == 15.0 and GM_min == constants.GM_c3('min')
+    assert network._time_origin(np.float32(0.25), units.hr) == (0.25, GM) and network._time_origin(0.25, None) == (0.25, 1.0)
+    tM0, scalar_t = network._frame_offsets(t * 60.0 * units.min, units.hr, 15.0 * units.min, t_inj, 'cpu')
+    assert not scalar_t and np.array_equal(tM0.numpy(), (t * 60.0 - 15.0) / GM_min - t_inj)
+    tM0, scalar_t = network._frame_offsets(t[1], units.hr, t0, torch.tensor(t_inj), 'cpu')
+    assert scalar_t and np.array_equal(tM0.numpy(), want[1:2])
+
+
+def test_save_params_writes_the_same_yaml_for_both_predictors(tmp_path):
+    """save_params / from_yml exist once (NeRF_Predictor), driven by each class's key list and file name: the files are
+    byte for byte what each predictor's own copy wrote before, and from_yml rebuilds the predictor from them."""
+    nerf = network.NeRF_Predictor(8.0, 2.0, np.float32(20.0), np.inf, posenc_deg=3, net_depth=4, net_width=128)
+    grid = network.GRID_Predictor(8.0, 2.0, np.float64(20.0), np.inf, 32)
+    nerf.save_params(tmp_path)
+    grid.save_params(tmp_path)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ['GRID_Predictor_params.yml', 'NeRF_Predictor_params.yml']
+    assert (tmp_path / 'NeRF_Predictor_params.yml').read_text() == (
+        'do_skip: true\nnet_depth: 4\nnet_width: 128\nout_channel: 1\nposenc_deg: 3\nposenc_var: 2.0e-05\nrmax: 20.0\nrmin: 2.0\n'
+        'scale: 8.0\nz_width: .inf\n')
+    assert (tmp_path / 'GRID_Predictor_params.yml').read_text() == 'grid_res: 32\nrmax: 20.0\nrmin: 2.0\nscale: 8.0\nz_width: .inf\n'
+    back = network.NeRF_Predictor.from_yml(tmp_path, mode='f32')
+    assert type(back) is network.NeRF_Predictor and (back.net_width, back.rmax, back.z_width, back.mode) == (128, 20.0, np.inf, 'f32')
+    back = network.GRID_Predictor.from_yml(tmp_path)
+    assert type(back) is network.GRID_Predictor and (back.grid_res, back.scale, back.rmin, back.mode) == (32, 8.0, 2.0, 'f32')
+    grid.save_params(tmp_path, 'other.yml')
+    assert network.GRID_Predictor.from_yml(tmp_path, 'other.yml').grid_res == 32
+    assert grid._graph_epoch == 0 and grid._engine is None                       # (initialised through the base class)

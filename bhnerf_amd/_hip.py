@@ -13,12 +13,8 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
-# BHNERF_HIP_LIB: an alternative build of the library, e.g. the debug build (make debug) for the tools/ scripts
+# BHNERF_HIP_LIB: an alternative build of the library, e.g. another commit's, to compare against
 LIB_PATH = os.environ.get('BHNERF_HIP_LIB') or os.path.join(CSRC, 'libbhnerf_hip.so')
-DEBUG_SIGNATURES = {        # include/bhnerf_hip_debug.h: only libbhnerf_hip_dbg.so exports these
-    'bhn_debug_set_fwd_variant': (C.c_int, [C.c_int32]),
-    'bhn_debug_read': (C.c_int, [C.c_void_p, C.c_size_t]),
-}
 
 ABI_VERSION = 5              # BHN_ABI_VERSION of include/bhnerf_hip.h this binding was written against
 BHN_F32, BHN_BF16, BHN_BF16_T8 = 0, 1, 2
@@ -126,10 +122,6 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
-        for name, (res, args) in DEBUG_SIGNATURES.items():
-            if hasattr(handle, name):
-                fn = getattr(handle, name)
-                fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
 

@@ -8,9 +8,6 @@
 #include <string.h>
 
 #include "../../include/bhnerf_hip.h"
-#ifdef BHN_DEBUG
-#include "../../include/bhnerf_hip_debug.h"
-#endif
 
 #define BHN_MAX_LAYERS 9   // net_depth <= 8 hidden layers + the output layer
 #define BHN_DEG_MAX 4      // posenc degrees 0..4 share ONE kernel-side slot layout of the 32-feature block

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     constexpr int NFR = ((MODE == MODE_CHAIN && KS >= 8) || ENCR) ? KS : KS + 2;
     using RG = DmaRing<RES ? CB : NFR * Pol::FRAG_BYTES, Pol::NWAVES, GA0C>;     // (GA0C: transposed LDS reads in the kernel -> asm DMA)
     constexpr int DIST = GA0C ? GA0C_DIST : BG::RING_DIST_TAPED;
-    using RS = std::conditional_t<RES, ResidentRing<RG, CB, MT>, RingState<RG, CB, DIST, false, MT>>;
+    using RS = std::conditional_t<RES, ResidentRing<RG, CB, MT>, RingState<RG, CB, DIST, MT>>;
     // stores guaranteed younger than chunk c+2 at the end of step c (RingState::step_end): every interval between
     // two DMA issues holds the >= ES stores of one pending-tile emission; with >= 16 k-steps the running step's
     // own emission (k-step 12) also follows its DMA issue (k-step 9).  The DMA pieces of the DIST-2 younger chunks
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     APipe<Pol> ap;
     if (have_ring) {
         // (the transposed images are stored layer-major from layer 1 on: the ring starts at layer LEND's)
-        rs.start(ring, a.packed + a.fwd_off, NCF, a.packed + a.bwd_off + (size_t)(LEND - 1) * MT * CB, NLB, sdbg ? 1 : 0, 0);
+        rs.start(ring, a.packed + a.fwd_off, NCF, a.packed + a.bwd_off + (size_t)(LEND - 1) * MT * CB, NLB, sdbg ? 1 : 0);
         ap.prime(rs.ch(), first_bias);
     } else {
         __syncthreads();

@@ -57,6 +57,7 @@ constexpr int LDS_BYTES = OFF_B0 + 512;
 constexpr int CB = (KS + 2) * 1024;                                 // chunk bytes of the packed weight images (fused_common.h Pack<128>)
 constexpr int SLAB_TILES = 65;                                      // 60 hidden tiles + 4 layer-0 tiles + the output layer's row / biases
 constexpr int SLAB_FLOATS128 = SLAB_TILES * 1024;
+constexpr int CPF = 3;                                             // chain B fragments in flight
 
 typedef PolBF16 Pol;
 typedef Pol::frag frag;
@@ -83,9 +84,6 @@ DEVI u32x4 make_rsrc(const char *p) {
 #pragma clang diagnostic ignored "-Winline-asm"      // (only: "inline asm clobber list contains reserved registers: M0")
 // one wave copies 1 KiB global -> LDS: lane i's 16 bytes come from rs.base + soff + voff(i) and land at lds + 16 i
 DEVI void dma_piece(const u32x4 &rs, unsigned soff, unsigned lds, unsigned voff) {
-#ifdef BHN_B128_ABL
-    if (BHN_B128_ABL & 8) return;
-#endif
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds" ::"s"(lds), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
 }
 #pragma clang diagnostic pop
@@ -206,25 +204,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int ks = 0; ks < KS; ks += 4) asm volatile("" : "+v"(wf[mi][ks]), "+v"(wf[mi][ks + 1]), "+v"(wf[mi][ks + 2]), "+v"(wf[mi][ks + 3]));
     };
-#ifndef BHN_B128_ABL
-#define BHN_B128_ABL 0              // measurement builds (results wrong): 1 no dW MFMAs, 2 dW fragments read once per phase, 4 no chain MFMAs, 8 no tape DMA, 16 no chain epilogue, 32 no front, 64 no barriers
-#endif
-#ifndef BHN_B128_STAMPS
-#define BHN_B128_STAMPS 0           // 1 (measurement build): s_memtime stamps of one iteration of workgroup 0 -> slab tile 64 (tools/dbg_bwd128_stamps.py)
-#endif
-    long long *ts = nullptr;
-    int ts_i = 0;
-    auto stamp = [&]() {
-        if constexpr (BHN_B128_STAMPS != 0) {
-            if (ts) { const long long t = __builtin_readcyclecounter(); if (lane == 0) ts[ts_i] = t; ++ts_i; }
-        }
-    };
     auto drain_and_barrier = [&]() {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        stamp();
-        if (!(BHN_B128_ABL & 64)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        stamp();
     };
 
     // ---- accumulators: hidden layer l = 1..DEPTH-1: (m0,n0) (m0,n1) (m1,n0) (m1,n1); the skip layer's (m_e, enc) tile;
@@ -246,10 +229,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // `side(ks)`: work of other phases issued in the shadow of this step's MFMAs (one wave per SIMD: nothing else hides it)
     auto chain_mma = [&](const frag (&wf)[2][KS], unsigned ga_in, int pi, f32x16 (&c)[2], auto &&side) {
         { const f32x16 z = {}; c[0] = z; c[1] = z; }
-#ifndef BHN_B128_CPF
-#define BHN_B128_CPF 3              // chain B fragments in flight
-#endif
-        constexpr int CPF = BHN_B128_CPF;
         frag bq[CPF + 1];
 #pragma unroll
         for (int i = 0; i < CPF; ++i) bq[i] = lds_row(smem, ga_in + (rowb[pi] ^ (32u * i)));
@@ -257,11 +236,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int ks = 0; ks < KS; ++ks) {
             if (ks + CPF < KS) bq[(ks + CPF) % (CPF + 1)] = lds_row(smem, ga_in + (rowb[pi] ^ (32u * (ks + CPF))));
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (BHN_B128_ABL & 4) { asm volatile("" :: "v"(bq[ks % (CPF + 1)])); }
-            else {
             c[0] = Pol::mma(wf[0][ks], bq[ks % (CPF + 1)], c[0]);
             c[1] = Pol::mma(wf[1][ks], bq[ks % (CPF + 1)], c[1]);
-            }
             side(ks);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -303,29 +279,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             else f.be = f.b0;
             return f;
         };
-#ifndef BHN_B128_DWDB
-#define BHN_B128_DWDB 0             // 1: the next k-step's fragments are fetched BEFORE this step's MFMAs (a second fragment set: 24 registers)
-#endif
         KF cur = fetch(0);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            KF nx = cur;
-            if constexpr (BHN_B128_DWDB != 0) { if (k + 1 < 8) nx = fetch(k + 1); }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (BHN_B128_ABL & 1) { asm volatile("" :: "v"(cur.a0), "v"(cur.a1), "v"(cur.b0), "v"(cur.b1), "v"(cur.be), "v"(cur.ae)); }
-            else {
             t[0] = Pol::mma(cur.a0, cur.b0, t[0]);
             t[1] = Pol::mma(cur.a0, cur.b1, t[1]);
             t[2] = Pol::mma(cur.a1, cur.b0, t[2]);
             t[3] = Pol::mma(cur.a1, cur.b1, t[3]);
-            }
-            if constexpr (BHN_B128_ABL & 1) {}
-            else if constexpr (ENC) te = Pol::mma(cur.ae, cur.be, te);
+            if constexpr (ENC) te = Pol::mma(cur.ae, cur.be, te);
             else bs = Pol::sum8(cur.ae, bs);
             // the next k-step's fragments are fetched BEHIND this step's MFMAs (160 cycles of matrix work cover the LDS
             // latency; a second fragment set in flight costs 40 registers this kernel does not have)
-            if constexpr (BHN_B128_DWDB != 0) cur = nx;
-            else if (k + 1 < 8 && !(BHN_B128_ABL & 2)) cur = fetch(k + 1);
+            if (k + 1 < 8) cur = fetch(k + 1);
             side(k);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -436,11 +402,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         asm volatile("" : "+a"(acc_e), "+a"(acc0));
         const bool has_next = Q + gridDim.x < nquads;
         const long long Qn = has_next ? Q + gridDim.x : Q;     // the last iteration re-loads its own quad (with dout = 0: no contribution)
-        if constexpr (BHN_B128_STAMPS != 0) {
-            ts = (blockIdx.x == 0 && Q == blockIdx.x + 100ll * gridDim.x) ? reinterpret_cast<long long *>(a.slabs + 64 * 1024 + 256) + 64 * wv : nullptr;
-            ts_i = 0;
-            stamp();
-        }
         const unsigned e_img = OFF_E + eb * ENC_IMG;
         // (the top phase of THIS quad -- gA_{D-1} -> GA0, dW_out -- ran at the end of the previous iteration, beside layer 0's dW)
         // Layers D-1 .. 1.  Buffers alternate: gA_l in GA[(D-1-l) & 1], h_l in H[(D-l) & 1]; the h image that the mask of
@@ -455,21 +416,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const u32x4 rs_h = h_rsrc(l - 1 >= 2 ? l - 1 : 2, Q);
             if (l == 2) make_h1(e_img, OFF_H + (hi ^ 1) * IMG);          // (the image h_3 has left; published by this layer's barrier)
             if (l == 1) { dnext = point_dout(Qn); load_maskd(Qn, mnext); }   // loads issued here, consumed behind this layer's dW phase / in the next top phase
-            stamp();
             f32x16 c0[2], c1[2];
             chain_mma(wf, ga_in, 0, c0, [&](int ks) { if (l - 1 >= 2) dma_h_piece(rs_h, hi ^ 1, ks); });
-            stamp();
-            if constexpr (BHN_B128_ABL & 16) {
-                chain_mma(wf, ga_in, 1, c1, [&](int) {});
-            } else {
-                post_begin(0, h_img);
-                chain_mma(wf, ga_in, 1, c1, [&](int ks) { post_slice(c0, 0, h_img, ga_out, ks); });
-                post_begin(1, h_img);
-            }
-            stamp();
+            post_begin(0, h_img);
+            chain_mma(wf, ga_in, 1, c1, [&](int ks) { post_slice(c0, 0, h_img, ga_out, ks); });
+            post_begin(1, h_img);
             const int ln = (l - 1 >= 1) ? l - 1 : DEPTH - 1;  // next layer's weights (this layer's are dead behind the chain MFMAs)
             auto side_dw = [&](int k) {
-                if constexpr (!(BHN_B128_ABL & 16)) post_slice(c1, 1, h_img, ga_out, k);
+                post_slice(c1, 1, h_img, ga_out, k);
                 if (k < 4) {                                  // (all sixteen issued in the first half: the last ones have four k-steps to land)
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi) { wf[mi][2 * k] = load_w1(ln, mi, 2 * k); wf[mi][2 * k + 1] = load_w1(ln, mi, 2 * k + 1); }
@@ -477,7 +431,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             };
             if (l == SKIPL) dw_phase(std::true_type{}, ga_in, h_img, e_img, acc[l - 1], acc_e, bsum[l - 1], side_dw);
             else dw_phase(std::false_type{}, ga_in, h_img, e_img, acc[l - 1], acc_e, bsum[l - 1], side_dw);
-            stamp();
             use_w(wf);
             if (l == 1) {
                 asm volatile("" : "+v"(dnext));                // (the compiler's wait for this load belongs here, at a drain point)
@@ -485,7 +438,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 if (lane < 32) bout += d;
                 put_dout(d);
             }
-            stamp();
             drain_and_barrier();                               // gA_{l-1} complete; the h image issued above has landed
         }
         // ---- layer 0: dW_0 = gA_0^T enc; the images of the next quad fly under it ----
@@ -493,13 +445,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int gi0 = (DEPTH - 1) & 1, hfree = (DEPTH - 1) & 1;          // gA_0 image; H image that held h_1
             const u32x4 rs_h = h_rsrc(DEPTH - 1, Qn);
             dma_enc(Qn, eb ^ 1);
-            stamp();
             dw0_phase(OFF_GA + gi0 * IMG, e_img, [&](int k) { dma_h_piece(rs_h, hfree, k); });
-            stamp();
             // ... and the NEXT quad's top phase beside it (its h_D landed behind layer 1's barrier; GA0 was last read by layer 1):
             // one barrier and one drain fewer per iteration than a top phase of its own
-            if (!(BHN_B128_ABL & 32)) front(mnext, OFF_GA + 0 * IMG);
-            stamp();
+            front(mnext, OFF_GA + 0 * IMG);
             drain_and_barrier();                               // GA0 complete; h_{D-1} (H1) and enc of the next quad landed
         }
         eb ^= 1;
@@ -703,11 +652,7 @@ __global__ __launch_bounds__(256) void reduce128_kernel(BwdArgs A, int nslabs, i
 
 // ---- host side (called from the plan and the launch of fused_bwd.hip) -----------------------------------------------------
 bool bwd128_supported(int mode, int kernel_width, int depth) {
-#ifdef BHN_NO_FUSED128
-    return false;
-#else
     return mode == BHN_BF16 && kernel_width == 128 && depth == 4;
-#endif
 }
 
 size_t bwd128_slab_bytes(int grid) { return (size_t)grid * SLAB_FLOATS128 * 4; }
@@ -716,10 +661,7 @@ void bwd128_tape_layout(int depth, long long NQ, TapeLayout *t) {
     memset(t, 0, sizeof(*t));
     t->NQ = NQ;
     t->fused128 = 1;
-#ifndef BHN_F128_PAD
-#define BHN_F128_PAD 0             // (measurement builds: bytes between the h tensors of the tape beyond their size)
-#endif
-    const long long per_tensor = NQ * (long long)MT * TB + BHN_F128_PAD;
+    const long long per_tensor = NQ * (long long)MT * TB;
     long long off = 0;
     t->drop_h1 = 1;                                              // h_1 = relu(W_0^T enc + b_0) is recomputed by the backward (2 MFMAs per tile)
     t->h_off[1] = -1;

@@ -40,7 +40,6 @@ struct PolBF16 {
     static constexpr int FRAG_BYTES = 1024;     // 64 lanes x 8 bf16
     static constexpr bool TAPE8 = false;        // (PolBF16T8: the h / gA tape tiles in 8 bits)
     static constexpr int LDS_PREFETCH = 4;      // A fragments in flight + 1 (ring_step); 6 / 8 measured no faster
-    static constexpr bool PHASE_LAG = false;    // RingState LAG: measured 5 % slower in the render kernel, off
     using frag = bf16x8;
     static DEVI frag zero() { frag f; for (int j = 0; j < 8; ++j) f[j] = (__bf16)0.f; return f; }
     static DEVI frag lds_frag(const char *chunk, int f, int lane) {
@@ -151,9 +150,6 @@ struct PolBF16T8 : PolBF16 {
 // hides more of them (one box, profiles/r5_ab_twelve_waves_width128.txt: inference forward 0.92 -> 0.85 ms, -7 %; training forward
 // 1.43 -> 1.25 ms, -12 %; 146 / 167 of the 170 registers a wave may have at that occupancy).
 // The training forward and the inference forward share the tile size: `render` and `render_train` give bit-identical images.
-#ifndef BHN_W12
-#define BHN_W12 1
-#endif
 struct PolBF16X : PolBF16 {
     static constexpr int NWAVES = 12;
     static constexpr int NTHREADS = NWAVES * 64;
@@ -177,7 +173,6 @@ struct PolF32 {
     static constexpr int FRAG_BYTES = 2048;     // 2 halves x 64 lanes x 4 f32
     static constexpr bool TAPE8 = false;
     static constexpr int LDS_PREFETCH = 2;
-    static constexpr bool PHASE_LAG = false;    // one wave per SIMD
     using frag = f32x8;
     static DEVI frag zero() { frag f; for (int j = 0; j < 8; ++j) f[j] = 0.f; return f; }
     static DEVI frag lds_frag(const char *chunk, int f, int lane) {
@@ -225,9 +220,7 @@ struct PolF32 {
 // policy.  A function of the MODEL and the RAY SET only, never of the batch: the inference forward, the training forward and the
 // backward's plan of one problem always agree on the tile size.
 static inline int bhn_fwd_tile_groups(int mode, int kernel_width, int depth, long long groups_per_frame) {
-#ifndef BHN_NO_FUSED128
-    if (BHN_W12 != 0 && mode == BHN_BF16 && kernel_width == 128 && depth == 4 && groups_per_frame >= 12 * 256) return PolBF16X::NWAVES;
-#endif
+    if (mode == BHN_BF16 && kernel_width == 128 && depth == 4 && groups_per_frame >= 12 * 256) return PolBF16X::NWAVES;
     return mode == BHN_BF16 ? PolBF16::NWAVES : PolF32::NWAVES;
 }
 
@@ -303,7 +296,7 @@ struct FusedArgs {
     FastDiv fd_tpf, fd_G;
     int ray_direct;                 // every ray touches at most two 32-point wave tiles (dense: from G; compacted: bhn_geom.ray_span): one atomic per (tile, ray) is already
                                     // order-independent (RaySum::direct), no combine through LDS needed
-    int debug;            // measurement builds only
+    int debug;            // unused, always 0 (kept: without it hipcc merges the scalar argument loads differently, tools/README.md)
     int deg;              // posenc degree 0..BHN_DEG_MAX (run time: only the prologue and the weight packing depend on it)
     long long *clk;       // bhn_frames.clock_probe (NULL: off): clock stamps of workgroup 0, four per kernel slot (clock_stamp)
 };
@@ -616,6 +609,7 @@ struct PackPost {
 // ZB: every tile of the sequence starts from a ZERO accumulator (the delta chain): no bias rows are read and ap.bias -- sixteen
 // registers that would hold zeros across the step boundary -- is not used
 template <int W, class Pol, class RG, class Post, int NFR = W / 16 + 2, bool ZB = false>
+// `dbg`: always 0 (bits 1 / 2 skipped the MFMAs / the post work in measurement builds; kept, see RingState::dbg)
 // `encw` (NFR == KS with an encoded-input block, i.e. the forward kernels whose ring copies only the hidden fragments of a chunk):
 // the tile's two encoded-input weight fragments in the RESIDENT block the kernel filled at its start (EncBlock below)
 DEVI f32x16 ring_step(const char *ch, const char *chn, APipe<Pol> &ap, const typename Pol::frag (&src)[W / 16],
@@ -790,7 +784,7 @@ DEVI void lds_barrier() {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Ring bookkeeping of the pipelined steps: chunk c is consumed from buffer `cur` while chunks c+1 .. c+DIST-1
+// Ring bookkeeping of the pipelined steps: chunk c is consumed from buffer `o_cur` while chunks c+1 .. c+DIST-1
 // are resident or in flight; step_end() waits for this wave's pieces of chunk c+2 (NOT c+1: the A-fragment
 // prefetch of the next step reads chunk c+2 before that step's barrier) and synchronises the workgroup.
 // ---------------------------------------------------------------------------------------------
@@ -798,14 +792,12 @@ DEVI void lds_barrier() {
 // the ring buffers are RG::NPIECE KiB apart -- normally the whole chunk; the delta chain leaves out the two encoded-input
 // fragments its transposed image never uses (16 instead of 18 pieces at width 256: two instead of three DMA issues per wave
 // and step).
-template <class RG, int CB, int DIST, bool LAG, int MT = 1, bool STAMPS = false>
+template <class RG, int CB, int DIST, int MT = 1>
 struct RingState {
     static constexpr int CBL = RG::NPIECE * 1024;          // bytes copied per chunk = stride of the ring buffers in LDS
     static_assert(CBL <= CB, "the ring copies at most a whole chunk");
-    // LAG (measured, not used): the second wave of every SIMD (waves NWAVES/2..) consumes the ring ONE STEP BEHIND
-    // the first, so that the two waves of a SIMD are never in their per-tile VALU phases at the same time.  Costs one
-    // more resident chunk and one idle step per wave; 5 % slower in the render kernel.
-    static constexpr int NB = DIST + (LAG ? 2 : 1);
+    // (Letting the second wave of every SIMD consume the ring one step behind the first measured 5 % slower in the render kernel.)
+    static constexpr int NB = DIST + 1;
     static_assert(DIST >= 2, "ring geometry");
     __host__ __device__ static constexpr size_t lds_bytes(int) { return (size_t)NB * CBL; }
     char *ring;
@@ -815,20 +807,20 @@ struct RingState {
     unsigned off_b;         // byte offset of the transposed image from img_a (both live in the packed-weight buffer)
     __amdgpu_buffer_rsrc_t rs;
     u32x4 rsa;
-    int NC, NCA, nlb, cur, issue_c, dbg, lag;
-    long long *ts;          // STAMPS (measurement builds): per-step time stamps (compute done, barrier passed)
-    static DEVI int wrap(int i) { return i < 0 ? i + NB : (i >= NB ? i - NB : i); }
+    int NC, NCA, nlb, issue_c;
+    int dbg, lag;           // always 0: what is left of the removed measurement switches, kept because the kernels' generated code
+                            // changes without the (never taken) branches on them (tools/README.md)
     // The buffer offset is made opaque to the compiler: when the number of ring buffers divides the steps of a layer it
     // proves the ring position of every unrolled step, folds it into the LDS address of each fragment read and, LDS being
     // larger than the 16-bit offset field of ds_read, pays one v_add per read (16 per step, round-2 ISA census).  From
     // an SGPR base it is one v_add per step and immediate offsets.
     static DEVI int opaque(int v) { asm volatile("" : "+s"(v)); return v; }
-    // Without LAG the three buffer offsets a step needs (consumed, next, the one just freed) are carried as byte offsets
-    // and rotated at the step end (3 SALU) instead of being derived from `cur` each time (three wrap()s and multiplies:
+    // The three buffer offsets a step needs (consumed, next, the one just freed) are carried as byte offsets and rotated
+    // at the step end (3 SALU) instead of being derived from a buffer index each time (three wraps and multiplies:
     // ~25 of the 140-190 instructions of a ring step, round-2 ISA census).
     int o_cur, o_nxt, o_prv, wvu;
-    DEVI const char *ch() const { return ring + opaque(LAG ? wrap(cur - lag) * CBL : o_cur); }
-    DEVI const char *chn() const { return ring + opaque(LAG ? wrap(cur - lag + 1) * CBL : o_nxt); }
+    DEVI const char *ch() const { return ring + opaque(o_cur); }
+    DEVI const char *chn() const { return ring + opaque(o_nxt); }
     DEVI unsigned next_src() {
         unsigned src;
         if (issue_c < NCA) src = (unsigned)issue_c * CB;
@@ -841,40 +833,30 @@ struct RingState {
     }
     DEVI DmaJob job() {
         if (dbg & 4) return DmaJob{false, 0u, nullptr, rs, wvu, rsa};
-        return DmaJob{true, next_src(), ring + (LAG ? wrap(cur - 2) * CBL : o_prv), rs, wvu, rsa};
+        return DmaJob{true, next_src(), ring + o_prv, rs, wvu, rsa};
     }
     // STORES: global stores this wave is GUARANTEED to have issued after the DMA pieces of chunk c+2 (issued in the
     // middle of step c-2) other than the two younger chunks: vmcnt retires in order and counts stores, so they may
     // stay in flight across the wait.  0 is always safe (it only waits for more).
     template <int STORES = 0>
     DEVI void step_end() {
-        long long t1 = 0;
-        if (STAMPS && ts) t1 = __builtin_readcyclecounter();
         if (!(dbg & 4)) RG::template wait_younger<RG::PPW * (DIST - 2) + STORES>();
         if (!(dbg & 8)) lds_barrier();
-        if (STAMPS && ts) {
-            const long long t3 = __builtin_readcyclecounter();
-            if ((threadIdx.x & 63) == 0) { ts[0] = t1; ts[1] = t3; }
-            ts += 2;
-        }
-        if constexpr (LAG) cur = (cur == NB - 1) ? 0 : cur + 1;
-        else {
-            o_prv = o_cur;
-            o_cur = o_nxt;
-            o_nxt = (o_nxt == (NB - 1) * CBL) ? 0 : o_nxt + CBL;
-        }
+        o_prv = o_cur;
+        o_cur = o_nxt;
+        o_nxt = (o_nxt == (NB - 1) * CBL) ? 0 : o_nxt + CBL;
     }
-    DEVI void idle_step() {      // a step in which this wave consumes nothing (lagging waves: first; the others: last)
+    DEVI void idle_step() {      // a step in which this wave consumes nothing (the forward's last)
         const DmaJob j = job();
         if (j.on) RG::issue(j);
         step_end();
     }
-    DEVI void start(char *ring_, const char *a_, int nca, const char *b_, int nlb_, int dbg_, int lag_) {
+    DEVI void start(char *ring_, const char *a_, int nca, const char *b_, int nlb_, int dbg_) {
         ring = ring_; img_a = a_; NCA = nca; nlb = nlb_; NC = nca + nlb_ * MT;
         off_b = b_ ? (unsigned)(b_ - a_) : 0u;                  // (the transposed image follows the forward image)
         rs = RG::resource(a_);
         rsa = RG::resource_raw(a_);
-        dbg = dbg_; cur = 0; issue_c = 0; lag = LAG ? lag_ : 0; ts = nullptr;
+        dbg = dbg_; issue_c = 0; lag = 0;
         o_cur = 0; o_nxt = CBL; o_prv = (NB - 1) * CBL;
         wvu = opaque(__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
 #pragma unroll
@@ -895,7 +877,6 @@ struct ResidentRing {
     static constexpr int NB = 0;                 // (no ring buffers: lds_bytes(nc) is the footprint)
     char *ring;
     int NC, dbg, lag, o_cur, o_nxt, wvu;
-    long long *ts;
     static DEVI int opaque(int v) { asm volatile("" : "+s"(v)); return v; }
     __host__ __device__ static constexpr size_t lds_bytes(int nc) { return (size_t)nc * CB; }
     DEVI const char *ch() const { return ring + opaque(o_cur); }
@@ -909,8 +890,8 @@ struct ResidentRing {
     DEVI void idle_step() {}
     // chunk j of the consumption order: forward chunks 0..nca-1 of img_a, then the transposed chunks of hidden layers
     // nlb .. 1 (stored layer-major ascending in img_b), MT each -- RingState::next_src's order
-    DEVI void start(char *ring_, const char *a_, int nca, const char *b_, int nlb_, int dbg_, int) {
-        ring = ring_; NC = nca + nlb_ * MT; dbg = dbg_; lag = 0; ts = nullptr;
+    DEVI void start(char *ring_, const char *a_, int nca, const char *b_, int nlb_, int dbg_) {
+        ring = ring_; NC = nca + nlb_ * MT; dbg = dbg_; lag = 0;
         o_cur = 0; o_nxt = NC > 1 ? CB : 0;
         wvu = opaque(__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
         // the whole sequence by LDS-DMA, every piece in flight at once (round 5: through registers -- 12 dependent load / store

@@ -140,13 +140,9 @@ extern "C" int bhn_pack_weights(const bhn_model *m, int32_t mode, const float *p
 // ---------------------------------------------------------------------------------------------
 // forward kernel
 // ---------------------------------------------------------------------------------------------
-// DBG: measurement build of the width-128 kernels (bit 128: per-wave time stamps [compute done, barrier passed] of the ring steps of one
-// tile); (tools/dbg_fwd128_ablate.py): a.debug bits knock out one cost at a time -- 1 hidden/output MFMAs, 2 relu+pack, 4 weight DMA +
-// its waits, 8 barriers, 16 posenc trig, 32 epilogue.  Results are then meaningless.
 // RES: the whole weight image resident in LDS (ResidentRing: no DMA, no per-chunk barrier), when it fits
-template <int W, class Pol, int DEG, bool RENDER, bool DBG = false, bool RES = false>
+template <int W, class Pol, int DEG, bool RENDER, bool RES = false>
 __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(Pol::WPE, Pol::WPE))) void fused_fwd_kernel(FusedArgs a) {
-    const int dbg = DBG ? a.debug : 0;
     clock_stamp(a.clk, BHN_CLK_FWD, 0);
     using PK = Pack<W, Pol>;
     using frag = typename Pol::frag;
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
     constexpr int NFR = ENCR ? KS : KS + 2;
     using RG = DmaRing<ENCR ? KS * Pol::FRAG_BYTES : CB, Pol::NWAVES>;
     constexpr int DIST = Pol::FWD_DIST;                                                // LDS-DMA weight ring: chunks in flight
-    using RS = std::conditional_t<RES, ResidentRing<RG, CB, MT>, RingState<RG, CB, DIST, Pol::PHASE_LAG, MT, DBG>>;
+    using RS = std::conditional_t<RES, ResidentRing<RG, CB, MT>, RingState<RG, CB, DIST, MT>>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *ring = smem;                                              // NB x (bytes copied per chunk) (resident: all chunks)
     float *bias_lds = reinterpret_cast<float *>(smem + RS::lds_bytes(PK::fwd_chunks(a.depth)));     // (depth+1) x W
@@ -170,7 +166,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
 
     // weight ring (LDS-DMA), software-pipelined steps: fused_common.h "Software-pipelined ring steps"
     RS rs;
-    rs.start(ring, a.packed + a.fwd_off, PK::fwd_chunks(a.depth), nullptr, 0, dbg, wv >= Pol::NWAVES / 2 ? 1 : 0);
+    rs.start(ring, a.packed + a.fwd_off, PK::fwd_chunks(a.depth), nullptr, 0, 0);
     if (rs.lag) rs.idle_step();
     APipe<Pol> ap;
     ap.prime(rs.ch(), bias_lds);
@@ -183,18 +179,12 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
         const bool inb = in.inb;
         frag enc[2];
         bool live;
-        if (!(dbg & 16)) point_prologue<Pol, DEG>(a, in, enc, live);
-        else { live = in.dom; for (int j = 0; j < 8; ++j) { Pol::set(enc[0], j, in.x); Pol::set(enc[1], j, in.tg); } }
+        point_prologue<Pol, DEG>(a, in, enc, live);
         nxt = load_point<Pol::NWAVES>(a, tile + gridDim.x, wv, pl);      // next tile's inputs fly during this tile
         float w0 = 0.f;                                                  // quadrature weight of s = 0, needed at the very end
         if (RENDER && h == 0 && inb) w0 = a.w[p];
 
         frag act[KS], next[KS];
-        if (DBG) for (int ks = 0; ks < KS; ++ks) next[ks] = act[ks] = Pol::zero();
-        if (DBG) {      // bit 128: stamp the ring steps of this workgroup's 4th tile, waves 0 and NWAVES/2 -> a.emission
-            const bool on = (dbg & 128) && blockIdx.x == 0 && tile == blockIdx.x + 3 * (long long)gridDim.x;
-            rs.ts = on ? reinterpret_cast<long long *>(a.emission) + wv * 64 : nullptr;
-        }
         f32x16 pend;
         PackTile0<Pol> l0;
         layer0_step<W, Pol, RG, 0, RS, PackTile0<Pol>, NFR>(rs, ap, enc, act, bias_lds, h, pend, l0);
@@ -213,7 +203,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
             const char *ch = rs.ch(), *chn = rs.chn();
             const DmaJob dj = rs.job();
             PackPost<Pol> post(pend, act[KS - 2], act[KS - 1]);
-            const f32x16 acc = ring_step<W, Pol, RG, PackPost<Pol>, NFR>(ch, chn, ap, act, enc, (a.skip_mask >> a.depth) & 1, bias_lds /* next tile, layer 0 */, post, dj, dbg,
+            const f32x16 acc = ring_step<W, Pol, RG, PackPost<Pol>, NFR>(ch, chn, ap, act, enc, (a.skip_mask >> a.depth) & 1, bias_lds /* next tile, layer 0 */, post, dj, 0,
                                                                          encblk + 2 * MT * Pol::FRAG_BYTES);
             outv = acc[0];
             rs.step_end();
@@ -221,9 +211,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
         // ---- epilogue: sigmoid(out - 10), masks (network.py:230-232) ----------------------
         float e = 0.f;
         if (h == 0 && live) e = 1.f / (1.f + Pol::fexp(10.f - outv));
-        if (dbg & 32) {
-            if (e == 12345.f) a.images[0] = e;
-        } else if (!RENDER) {
+        if (!RENDER) {
             if (h == 0 && inb) a.emission[(long long)b * a.P + p] = e;
         } else {
             // x J g^2 dtau Sigma and the sum over the ray: segment sums per wave, combined per workgroup tile (RaySum)
@@ -288,19 +276,19 @@ int fused_fill_args(const bhn_model *m, int32_t mode, const void *packed, const 
 }
 
 
-template <int W, class Pol, bool RENDER, bool DBG = false, bool RES = false>
+template <int W, class Pol, bool RENDER, bool RES = false>
 static int launch_fwd_w(FusedArgs &a, hipStream_t st) {
     using PK = Pack<W, Pol>;
     const size_t lds_fixed = (size_t)(a.depth + 1) * W * 4 + RaySum<Pol::NWAVES>::bytes(a.Sx);
-    if constexpr (!RES && !DBG && W <= 128 && Pol::ELEM_BYTES == 2) {     // (f32, one wave per SIMD: measured 11 % slower resident)
+    if constexpr (!RES && W <= 128 && Pol::ELEM_BYTES == 2) {     // (f32, one wave per SIMD: measured 11 % slower resident)
         // small networks: all chunks of the forward image resident in LDS, waves run without the per-chunk barrier
-        if ((size_t)PK::fwd_chunks(a.depth) * PK::CHUNK_BYTES + lds_fixed <= 160 * 1024) return launch_fwd_w<W, Pol, RENDER, DBG, true>(a, st);
+        if ((size_t)PK::fwd_chunks(a.depth) * PK::CHUNK_BYTES + lds_fixed <= 160 * 1024) return launch_fwd_w<W, Pol, RENDER, true>(a, st);
     }
     constexpr bool ENCR = EncBlock<W, Pol>::ON && !RES;             // (the kernel's own condition)
     const size_t lds = RES ? (size_t)PK::fwd_chunks(a.depth) * PK::CHUNK_BYTES + lds_fixed
-                           : (size_t)(Pol::FWD_DIST + (Pol::PHASE_LAG ? 2 : 1)) * (ENCR ? (size_t)PK::KS * Pol::FRAG_BYTES : (size_t)PK::CHUNK_BYTES) + lds_fixed +
+                           : (size_t)(Pol::FWD_DIST + 1) * (ENCR ? (size_t)PK::KS * Pol::FRAG_BYTES : (size_t)PK::CHUNK_BYTES) + lds_fixed +
                              (ENCR ? (size_t)EncBlock<W, Pol>::BYTES : 0);
-    auto kern = fused_fwd_kernel<W, Pol, 3, RENDER, DBG, RES>;
+    auto kern = fused_fwd_kernel<W, Pol, 3, RENDER, RES>;
     int dev = 0;
     BHN_HIP(hipGetDevice(&dev));
     BHN_CHECK_DEVICE(dev);
@@ -340,30 +328,6 @@ static int launch_fwd(FusedArgs &a, int mode, int width, int nw, hipStream_t st)
     return mode == BHN_BF16 ? bhn_with_width<PolBF16>(width, go) : bhn_with_width<PolF32>(width, go);
 }
 
-#ifdef BHN_DEBUG
-// Measurement build only (make debug -> libbhnerf_hip_dbg.so, include/bhnerf_hip_debug.h): low 4 bits 1 = production
-// kernel (default), 3 = ablation build of the width-128 render kernel with the flags of fused_fwd_kernel<DBG> in bits 4.. .
-static thread_local int g_fwd_variant = 1;
-extern "C" int bhn_debug_set_fwd_variant(int32_t v) {
-    g_fwd_variant = v;
-    return BHN_OK;
-}
-static void *g_dbg_buf = nullptr;
-static void *bhn_debug_buffer() {        // 4 KiB device scratch of the measurement builds (time stamps)
-    if (!g_dbg_buf) {
-        if (hipMalloc(&g_dbg_buf, 4096) != hipSuccess) return nullptr;
-        (void)hipMemset(g_dbg_buf, 0, 4096);
-    }
-    return g_dbg_buf;
-}
-extern "C" int bhn_debug_read(void *dst_host, size_t bytes) {
-    BHN_CHECK_ARG(dst_host && bytes <= 4096, "bad debug read");
-    BHN_CHECK_ARG(g_dbg_buf, "no ablation launch has run");
-    BHN_HIP(hipMemcpy(dst_host, g_dbg_buf, bytes, hipMemcpyDeviceToHost));
-    return BHN_OK;
-}
-#endif
-
 extern "C" int bhn_predict_fwd(const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom,
                                const bhn_frames *fr, float *emission, void *stream) {
     FusedArgs a;
@@ -392,14 +356,5 @@ extern "C" int bhn_render_fwd(const bhn_model *m, int32_t mode, const void *pack
     if (rc != BHN_OK) return rc;
     a.images = images;
     BHN_HIP(hipMemsetAsync(images, 0, sizeof(float) * (size_t)a.B * a.Sx * a.R, (hipStream_t)stream));
-#ifdef BHN_DEBUG
-    if (mode == BHN_BF16 && s.width == 128 && (g_fwd_variant & 15) == 3) {     // ablation build of the resident-weights kernel, see fused_fwd_kernel
-        a.debug = g_fwd_variant >> 4;
-        a.emission = reinterpret_cast<float *>(bhn_debug_buffer());
-        BHN_CHECK_ARG(a.emission, "no debug buffer");
-        return nw == PolBF16X::NWAVES ? launch_fwd_w<128, PolBF16X, true, true, true>(a, (hipStream_t)stream)
-                                      : launch_fwd_w<128, PolBF16, true, true, true>(a, (hipStream_t)stream);
-    }
-#endif
     return launch_fwd<true>(a, mode, s.width, nw, (hipStream_t)stream);
 }

@@ -83,8 +83,8 @@ def test_tape_info_reports_the_layout_the_kernels_use(lib):
 
 def test_release_library_has_no_hidden_allocation_or_environment_reads(lib):
     """include/bhnerf_hip.h conventions: the caller owns every buffer and the library keeps no hidden state.  The
-    release build must not even REFERENCE an allocator or getenv (the measurement switches live in the debug build,
-    include/bhnerf_hip_debug.h), and must not export a debug entry point."""
+    library must not even REFERENCE an allocator or getenv (there is no debug build any more: the measurement switches
+    and their entry points are removed, tools/README.md), and must not export a debug entry point."""
     import shutil
     import subprocess
     from bhnerf_amd import _hip

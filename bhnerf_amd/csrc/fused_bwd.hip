@@ -435,7 +435,6 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     constexpr bool T8 = Pol::TAPE8;
     const FusedArgs &a = A.f;
     clock_stamp(a.clk, MODE == MODE_CHAIN ? BHN_CLK_CHAIN : BHN_CLK_FWD_TRAIN, 0);
-    constexpr int sdbg = 0;                        // (a run-time MFMA-skip flag put every MFMA in its own basic block)
     // the delta chain's transposed image never uses the two encoded-input fragments of a chunk: its ring copies (and its steps
     // stream) only the KS hidden fragments; the training forward (bf16) keeps them in a resident block of their own (EncBlock)
     // (KS >= 8: the A-fragment prefetch of a step runs LDS_PREFETCH - 1 fragments into the NEXT chunk, which must have that many)
@@ -456,9 +455,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     constexpr int YS_L1r = (KS >= 16) ? YS - ES : 0;                   // first steps of layer 1 when h_1 is not emitted
     constexpr int YS_L1 = YS_L1r > 0 ? YS_L1r : 0;
     const int NCF = (MODE == MODE_CHAIN) ? 0 : PK::fwd_chunks(A.f.depth);
-    // delta chain: hidden layers depth-1 .. LEND = 1 produce gA_{l-1}
-    constexpr int LEND = 1;
-    const int NLB = (MODE == MODE_FWD_TRAIN) ? 0 : A.f.depth - LEND;
+    const int NLB = (MODE == MODE_FWD_TRAIN) ? 0 : A.f.depth - 1;      // delta chain: hidden layers depth-1 .. 1 produce gA_{l-1}
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *ring = smem;
     float *bias_lds = reinterpret_cast<float *>(smem + RS::lds_bytes(NCF + NLB * MT));  // depth x W + the 32 rows of the output tile, then one zero row
@@ -516,8 +513,8 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     RS rs;
     APipe<Pol> ap;
     if (have_ring) {
-        // (the transposed images are stored layer-major from layer 1 on: the ring starts at layer LEND's)
-        rs.start(ring, a.packed + a.fwd_off, NCF, a.packed + a.bwd_off + (size_t)(LEND - 1) * MT * CB, NLB, sdbg ? 1 : 0);
+        // (the transposed images are stored layer-major from layer 1 on)
+        rs.start(ring, a.packed + a.fwd_off, NCF, a.packed + a.bwd_off, NLB, 0);
         ap.prime(rs.ch(), first_bias);
     } else {
         __syncthreads();
@@ -536,7 +533,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     // the delta chain stalled for 500-1500 cycles (ring-step stamps: 50.4 k ticks per tile against 39.1 k with the stores switched
     // off, the training forward -- no loads in its loop -- 49.3 k against 45.8 k; profiles/r5_chain_stamps.txt).
     constexpr int MWL = MT >= 4 ? 2 : (MT == 2 ? 3 : 5);              // layers in the FIFO
-    const int NL = a.depth - LEND;                                     // chain layers per tile
+    const int NL = a.depth - 1;                                        // chain layers per tile
     auto layer_words = [&](long long tile0, int pos, unsigned (&w)[MW]) {
         long long t = tile0;
         int j = pos;
@@ -654,8 +651,8 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     const char *ch = rs.ch(), *chn = rs.chn();
                     const DmaJob dj = rs.job();
                     const int pm = m == 0 ? MT - 1 : m - 1;           // pending tile (layer pl_layer)
-                    frag &d0 = m == 0 ? act[KS - 2] : next[2 * (m > 0 ? m - 1 : 0)];
-                    frag &d1 = m == 0 ? act[KS - 1] : next[2 * (m > 0 ? m - 1 : 0) + 1];
+                    frag &d0 = m == 0 ? act[KS - 2] : next[2 * (m - 1)];
+                    frag &d1 = m == 0 ? act[KS - 1] : next[2 * (m - 1) + 1];
                     const int widx = (pl_layer * MW + (pm >> 1)) * 64 + lane;
                     // h_depth: relu bits only (drop_hd: fused128, whose training forward keeps its weights resident -- bwd_launch checks
                     // that; a ring kernel would have to keep the emission's stores, which the waits of the weight ring count (YS above))
@@ -669,7 +666,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     // bias rows of the next tile: (l, m+1), or the first tile of the next sequence part
                     const float *bn = (out || (m == MT - 1 && l + 1 > a.depth)) ? nullptr : bl + 32 * (m + 1);
                     if (out) bn = bias_lds;                           // next tile, layer 0
-                    const f32x16 acc = ring_step<W, Pol, RG, TapePost<Pol, true>, NFR>(ch, chn, ap, act, enc, sk, bn, post, dj, sdbg,
+                    const f32x16 acc = ring_step<W, Pol, RG, TapePost<Pol, true>, NFR>(ch, chn, ap, act, enc, sk, bn, post, dj, 0,
                                                                                        encblk + 2 * (out ? MT : m) * Pol::FRAG_BYTES);
                     // without the h_1 emission the interval after this layer's first DMA issue holds no store: the
                     // three step ends that count it allow one emission less in flight (small widths: none)
@@ -677,8 +674,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     else if (drop_h1 && l == 1) rs.template step_end<(KS >= 16 ? YS : 0)>();
                     else rs.template step_end<YS>();
                     pend = acc;
-                    pl_layer = l;
-                    if (m == 0) pl_layer = l;                         // from here on the pending tiles are layer l's
+                    pl_layer = l;                                     // from here on the pending tiles are layer l's
                 }
                 if (!out) {
 #pragma unroll
@@ -794,14 +790,14 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
             unsigned t8_amax = T8 ? (unsigned)__builtin_bit_cast(unsigned short, (__bf16)__builtin_fabsf(dout)) : 0u;     // 8-bit tape: scale of the pending tile's layer, |gA|max of that layer so far
             if constexpr (T8) t8_sc = 0x1p60f;        // (gA_{depth-1} is not recorded -- TapeLayout::drop_ga -- and must not be limited either)
 #pragma nounroll
-            for (int l = a.depth - 1; l >= LEND; --l) {
+            for (int l = a.depth - 1; l >= 1; --l) {
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     const char *ch = rs.ch(), *chn = rs.chn();
                     const DmaJob dj = rs.job();
                     const int pm = m == 0 ? MT - 1 : m - 1;
-                    frag &d0 = m == 0 ? dl[KS - 2] : next[2 * (m > 0 ? m - 1 : 0)];
-                    frag &d1 = m == 0 ? dl[KS - 1] : next[2 * (m > 0 ? m - 1 : 0) + 1];
+                    frag &d0 = m == 0 ? dl[KS - 2] : next[2 * (m - 1)];
+                    frag &d1 = m == 0 ? dl[KS - 1] : next[2 * (m - 1) + 1];
                     const bool no_ga = (A.t.drop_ga && pnd_layer == a.depth - 1) || (GA0C && pnd_layer == 0);     // gA_{depth-1}'s last tile: not recorded; GA0C: gA_0 is staged
                     // GA0C: a finished gA_0 tile goes to the LDS staging image gaS[tile & 1] instead of the tape
                     const bool staged = GA0C && pnd_layer == 0;
@@ -817,12 +813,12 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                             else if (l == a.depth - 1 && m <= 1 && have_prev) { cons_on = true; cons.ga = gaS + m * STG; cons.enc = encS + (tpar ^ 1) * STG; }
                         }
                     }
-                    const float *bias_nx = (l == LEND && m == MT - 1) ? first_bias : zero_lds;
+                    const float *bias_nx = (l == 1 && m == MT - 1) ? first_bias : zero_lds;
                     char *tdst = A.tape + ga_lin + pnd_layer * lin_stride + (q * MT + pm) * TT;
                     TapePost<Pol, false, GA0C> post(pend, d0, d1, pnd_mask, em, tdst, nullptr, nullptr, no_acc, T8 && (pm & 1), false,
                                                     no_ga ? EMIT_OFF : 0, t8_sc, t8_amax);
                     post.stage = stage; post.stage_off = stage_off;
-                    const f32x16 acc = ring_step<W, Pol, RG, TapePost<Pol, false, GA0C>, NFR, GA0C>(ch, chn, ap, dl, enc, false, bias_nx, post, dj, sdbg);
+                    const f32x16 acc = ring_step<W, Pol, RG, TapePost<Pol, false, GA0C>, NFR, GA0C>(ch, chn, ap, dl, enc, false, bias_nx, post, dj, 0);
                     if constexpr (GA0C) {
                         if (cons_on) { if (ctile / NCW) cons.run(cacc1, 2 * MT); else cons.run(cacc0, 2 * MT); }      // (m is unrolled: folded)
                     }
@@ -872,13 +868,13 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     for (int i = 0; i < MW; ++i) mwf[k][i] = mwf[k + 1][i];
                 layer_words(tile, (a.depth - 1 - l) + MWL, mwf[MWL - 1]);
             }
-            if (a.depth > 1) {           // flush the last tile of gA_{LEND-1} (no further step to hide it behind)
+            if (a.depth > 1) {           // flush the last tile of gA_0 (no further step to hide it behind)
                 TapePost<Pol, false, GA0C> post(pend, dl[KS - 2], dl[KS - 1], pnd_mask, em,
-                                              A.tape + ga_lin + (LEND - 1) * lin_stride + (q * MT + MT - 1) * TT, nullptr, nullptr, no_acc, T8 && ((MT - 1) & 1), false, GA0C ? EMIT_OFF : 0,
+                                              A.tape + ga_lin + (q * MT + MT - 1) * TT, nullptr, nullptr, no_acc, T8 && ((MT - 1) & 1), false, GA0C ? EMIT_OFF : 0,
                                               t8_sc, t8_amax);
                 if constexpr (GA0C) { post.stage = gaS + ((MT - 1) & 1) * STG + wvu * TB; post.stage_off = stage_off; }     // consumed in the second step of the next tile
                 post.all();
-                if constexpr (T8) t8_flush(LEND - 1, t8_amax);
+                if constexpr (T8) t8_flush(0, t8_amax);
             }
             if constexpr (GA0C) { tpar ^= 1; have_prev = true; }
         }   // MODE_CHAIN

@@ -117,6 +117,13 @@ class CpuTrainer:
         loss.backward()
         return loss.detach(), images.detach(), [p.grad for p in self.k + self.b]
 
+    def grad_linear(self, t_frames, dimages):
+        """Gradient of sum(images * dimages), `dimages` shaped like forward()'s images: what bhn_render_bwd computes from the
+        upstream gradient of the images (the signature of oracle_bf16.Bf16Trainer.grad_linear) -> [dK_0..dK_D, db_0..db_D]."""
+        images = self.forward(t_frames)
+        assert tuple(dimages.shape) == tuple(images.shape), (tuple(dimages.shape), tuple(images.shape))
+        return list(torch.autograd.grad((images * dimages.detach()).sum(), self.k + self.b))
+
     def step(self, t_frames, target, sigma, offset, scale=1.0, dtype='full', grad_div=1.0):
         loss, images, grads = self.loss_and_grad(t_frames, target, sigma, offset, scale, dtype)
         self.apply(grads, grad_div)
@@ -135,6 +142,12 @@ class CpuTrainer:
                 mhat = m / (1.0 - 0.9 ** t)
                 vhat = v / (1.0 - 0.999 ** t)
                 p.sub_(lr * mhat / (vhat.sqrt() + 1e-8))
+
+
+def grad_linear(kernels, biases, geom, hp, t_frames, dimages):
+    """d(sum(dimages * images)) / d(params) of predictor + render in the precision of `kernels` (float64 in the tests), by
+    autograd: CpuTrainer's inputs and an upstream image gradient -> [dK_0..dK_D, db_0..db_D]."""
+    return CpuTrainer(kernels, biases, geom, hp).grad_linear(t_frames, dimages)
 
 
 def grid_loss_and_grad(grid, t_frames, geom, hp, target, sigma):

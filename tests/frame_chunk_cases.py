@@ -1,0 +1,69 @@
+"""The problems of the frame-chunk tests (test_gpu_frame_chunks, and the bf16 cases of
+test_gpu_backward.test_frame_group_taped_step_equals_full_step): the case tables, the ray sets and the builder.  No test here."""
+import numpy as np
+import torch
+
+from conftest import mask_tie_points
+from oracle import oracle_np as onp
+
+DENSE, SHELL = (8.0, 0.0, np.inf, np.inf), (8.0, 2.5, 8.0, 4.0)            # scale, rmin, rmax, z_width
+RAY_SETS = {'dense 144': (12, 12, 32, DENSE), 'dense 96': (12, 8, 32, DENSE), 'compacted': (18, 15, 50, SHELL)}   # rays H x W, samples
+T_FRAMES = (0.004, 0.021, 0.047)          # hours: t_M = t / GM_c3 + s + 5.6, so frame 0 is pre-injection for s < -6.3, frame 1 for s < -9.3
+T_INJ = -(1000.0 - 4.0)
+
+# name: (depth, width, mode, S, ray set, frames B, frames per pass)
+CASES = {
+    '4x128 S0 dense 144':        (4, 128, 'bf16', 0, 'dense 144', 3, (1, 2)),       # fused128; 2: uneven, passes of 2 + 1
+    '4x128 S3 compacted':        (4, 128, 'bf16', 3, 'compacted', 3, (2,)),
+    '4x100 S2 dense 96':         (4, 100, 'bf16', 2, 'dense 96', 2, (1,)),          # fused128, zero-padded
+    '4x256 S0 dense 144':        (4, 256, 'bf16', 0, 'dense 144', 3, (1, 2)),       # ga0_chain, chain_slab_stage1
+    '4x256 S3 dense 96':         (4, 256, 'bf16', 3, 'dense 96', 2, (1,)),          # ga0_chain, <= 16 chain workgroups
+    '6x256 S1 compacted':        (6, 256, 'bf16', 1, 'compacted', 3, (2,)),         # ga0_chain, skip into layer 3
+    '2x256 S0 dense 96':         (2, 256, 'bf16', 0, 'dense 96', 2, (1,)),          # generic, no W_out fold
+    '6x64 S2 dense 144':         (6, 64, 'bf16', 2, 'dense 144', 3, (2,)),          # fold, resident chain
+    '6x128 S0 dense 96':         (6, 128, 'bf16', 0, 'dense 96', 3, (1,)),          # fold, not fused128
+    '4x256 f32 S3 dense 144':    (4, 256, 'f32', 3, 'dense 144', 3, (2,)),
+    '4x64 f32 S0 dense 96':      (4, 64, 'f32', 0, 'dense 96', 3, (1,)),
+    '8x32 f32 S0 dense 96':      (8, 32, 'f32', 0, 'dense 96', 3, (1,)),
+}
+# the problems of test_gpu_backward.test_frame_group_taped_step_equals_full_step's bf16 cases (three frames, groups of 2 + 1)
+STEP_CASES = {'4x128 S0 dense 96': (4, 128, 'bf16', 0, 'dense 96', 3, ()), '4x256 S0 dense 96': (4, 256, 'bf16', 0, 'dense 96', 3, ())}
+
+_PROBLEMS = {}
+
+
+def problem(name):
+    """The problem of a case in the layout of a g5_* fixture (float64 arrays of f32-rounded values; geometry in the style of
+    test_gpu_backward.random_problem) + the upstream image gradient `dimg` (B, Sx, R), rand - 0.4."""
+    if name in _PROBLEMS:
+        return _PROBLEMS[name]
+    depth, width, mode, S, rays, B, _ = CASES[name] if name in CASES else STEP_CASES[name]
+    H, Wd, G, dom = RAY_SETS[rays]
+    rng = np.random.default_rng(1000 + 7 * width + depth + 31 * S)
+    alpha, beta = np.meshgrid(np.linspace(-8, 8, H), np.linspace(-8, 8, Wd), indexing='ij')
+    s = np.linspace(-9.6, 9.6, G)
+    inc = np.deg2rad(60.0)
+    coords = np.stack([alpha[..., None] * np.ones(G), beta[..., None] * np.cos(inc) + s * np.sin(inc),
+                       -beta[..., None] * np.sin(inc) + s * np.cos(inc)])
+    r = np.sqrt((coords ** 2).sum(0)) + 0.3
+    f32r = lambda v: np.asarray(v, dtype=np.float32).astype(np.float64)
+    g = dict(coords=f32r(coords), Omega=f32r(1.0 / (r ** 1.5 + 0.1)), t_geos=f32r(-(1000.0 - (s + 9.6)) * np.ones_like(r)),
+             g=f32r(rng.uniform(0.6, 1.4, r.shape)), Sigma=f32r(r ** 2), dtau=f32r((s[1] - s[0]) / r ** 2), J=np.array(1.0))
+    if S:
+        I = rng.uniform(0.5, 1.5, r.shape); chi = rng.uniform(0, np.pi, r.shape)
+        g['J'] = f32r(np.stack([I, 0.85 * I * np.cos(2 * chi), 0.85 * I * np.sin(2 * chi)])[:S])
+    tree = onp.he_uniform_params(rng, depth, width, 21, dtype=np.float32)
+    for i in range(depth + 1):
+        g['kernel%d' % i] = tree['MLP_0']['Dense_%d' % i]['kernel'].astype(np.float64)
+        g['bias%d' % i] = f32r(rng.uniform(-0.1, 0.1, tree['MLP_0']['Dense_%d' % i]['bias'].shape))
+    g['bias%d' % depth] = g['bias%d' % depth] + 9.0              # (sigmoid(out - 10) off its flat tail)
+    g.update(t_frames=np.array(T_FRAMES[:B]), t_start_obs=0.0, t_injection=T_INJ, hparams=np.array(list(dom) + [3, depth, width, 1.0]))
+    # no domain or injection mask decided within f32 rounding; pre-injection samples in frame 0, fewer of them in the last frame
+    assert not mask_tie_points(g).any()
+    tM = g['t_frames'].reshape(-1, 1, 1, 1) / onp.GM_C3_SGRA_HR + g['t_geos'] - T_INJ
+    pre = (tM < 0).sum(axis=(1, 2, 3))
+    assert len(set(T_FRAMES[:B])) == B and 0 < pre[0] < tM[0].size and pre[-1] < pre[0]
+    gen = torch.Generator().manual_seed(width + depth + S)
+    dimg = (torch.rand((B, max(S, 1), H * Wd), generator=gen, dtype=torch.float64) - 0.4).float().double()
+    _PROBLEMS[name] = dict(g=g, dimg=dimg, dom=dom, depth=depth, width=width, S=S, B=B, spatial=(H, Wd))
+    return _PROBLEMS[name]

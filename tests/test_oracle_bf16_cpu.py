@@ -240,3 +240,27 @@ def test_accumulation_noise_explains_the_largest_errors():
         print('accum32 %-14s %.2e (GPU %.1e)  per-layer dK %s' % (name, dist, OBSERVED[name][3], ' '.join('%.0e' % v for v in prof)))
         assert dist >= OBSERVED[name][3] / 8 and dist >= 10 * quiet, (name, dist, quiet)
         assert prof[0] > prof[-1], (name, prof)
+
+
+@pytest.mark.parametrize('S', [0, 3])
+def test_f64_linear_gradient_oracle_is_the_chi2_gradient(S):
+    """oracle_torch.grad_linear (the float64 reference of bhn_render_bwd: d sum(dimages images) / d params) with dimages =
+    d chi^2 / d images is CpuTrainer.loss_and_grad's gradient to float64 rounding (the chain rule through the images), without and
+    with Stokes planes; the emulator with its rounding off gives the same through its hand-written backward."""
+    ks, bs, geom, hp, tf, tg = small_problem(4, 48, S, True)
+    target, sigma, offset = tg
+    scale = 0.7
+    tr = ot.CpuTrainer(ks, bs, geom, hp)
+    _, images, g0 = tr.loss_and_grad(tf, target, sigma, offset, scale, 'full')
+    dimages = 2.0 * scale * (images - target - offset) / sigma ** 2
+    assert dimages.shape == ((2, 3, 6, 5) if S else (2, 6, 5))
+    g0 = ob.flat(g0)
+    assert np.abs(g0).max() > 0
+    g1 = ob.flat(ot.grad_linear(ks, bs, geom, hp, tf, dimages))
+    assert rel(g1, g0) < 1e-13, rel(g1, g0)
+    assert rel(ob.flat(tr.grad_linear(tf, dimages)), g0) < 1e-13
+    for recipe in ('generic', 'fused128'):
+        assert rel(ob.flat(ob.Bf16Trainer(ks, bs, geom, hp, recipe, rounding=False).grad_linear(tf, dimages)), g0) < 1e-12, recipe
+    # another dimages (the frames swapped) gives another gradient: a frame offset cannot hide
+    g2 = ob.flat(ot.grad_linear(ks, bs, geom, hp, tf, torch.flip(dimages, dims=(0,))))
+    assert rel(g2, g0) > 1e-3

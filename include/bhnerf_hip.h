@@ -16,6 +16,18 @@
  *     no global mutable state except the thread-local error string and per-device one-time caches
  *     (CU count, kernel attributes; std::call_once): re-entrant across threads, streams and devices.
  *     The CURRENT device of the calling thread must be the device that owns `stream` and the buffers.
+ *   - what `packed`, `workspace` and every OUTPUT buffer (emission, images, dparams, losses, ...) hold on entry is irrelevant:
+ *     recycled, un-zeroed memory is fine, no result depends on it, and every element of an output is written.  Nothing outside
+ *     the sizes this header names -- bhn_packed_bytes() for `packed`, the `workspace_bytes` passed for `workspace` (at least what
+ *     bhn_render_bwd_workspace_bytes() reports, or the smaller sizes bhn_render_bwd accepts), the array shapes for the outputs
+ *     -- is ever written.  The one exception is the BHN_BF16_T8 state block inside `workspace`: a backward call WITHOUT
+ *     BHN_T8_CALIBRATE reads the ratios the previous backward call on that workspace left there (see BHN_BF16_T8 below); a
+ *     calibrating call does not.  A recorded tape is of course read by bhn_render_bwd_tape as bhn_render_fwd_train wrote it.
+ *   - alignment: `packed` and `workspace` must be 16-byte aligned -- the kernels read and write them with 16-byte vector accesses
+ *     and 16-byte-per-lane LDS DMA, and every offset the library forms inside them is a multiple of 128 bytes (hipMalloc's
+ *     256-byte alignment, and any allocator's that aligns to 16, satisfies this); float / double / int arrays need their
+ *     element's alignment only.  (tests/test_gpu_buffer_contract.py holds the fused and general MLP entry points to both
+ *     paragraphs with guard bands and poisoned buffers at 256-byte-aligned addresses.)
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it and the call returns
  *     immediately (graph-capturable: no malloc/free/sync inside).
  *   - arrays are C-contiguous float32 unless stated.  P = R*G points per frame, flat index

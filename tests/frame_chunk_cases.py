@@ -39,6 +39,14 @@ def problem(name):
         return _PROBLEMS[name]
     depth, width, mode, S, rays, B, _ = CASES[name] if name in CASES else STEP_CASES[name]
     H, Wd, G, dom = RAY_SETS[rays]
+    _PROBLEMS[name] = build_problem(depth, width, mode, S, 3, H, Wd, G, dom, B)
+    return _PROBLEMS[name]
+
+
+def build_problem(depth, width, mode, S, deg, H, Wd, G, dom, B):
+    """The builder behind problem(): a network (depth x width, posenc degree `deg`; `mode` does not enter the problem) on H x Wd rays
+    x G samples in the domain `dom`, B frames.  tests/buffer_contract_cases.py builds its ray sets with it; the draws and their order
+    are those of the frame-chunk cases (pinned by tests/test_buffer_contract_cases_cpu.py)."""
     rng = np.random.default_rng(1000 + 7 * width + depth + 31 * S)
     alpha, beta = np.meshgrid(np.linspace(-8, 8, H), np.linspace(-8, 8, Wd), indexing='ij')
     s = np.linspace(-9.6, 9.6, G)
@@ -52,12 +60,12 @@ def problem(name):
     if S:
         I = rng.uniform(0.5, 1.5, r.shape); chi = rng.uniform(0, np.pi, r.shape)
         g['J'] = f32r(np.stack([I, 0.85 * I * np.cos(2 * chi), 0.85 * I * np.sin(2 * chi)])[:S])
-    tree = onp.he_uniform_params(rng, depth, width, 21, dtype=np.float32)
+    tree = onp.he_uniform_params(rng, depth, width, 3 + 6 * deg, dtype=np.float32)
     for i in range(depth + 1):
         g['kernel%d' % i] = tree['MLP_0']['Dense_%d' % i]['kernel'].astype(np.float64)
         g['bias%d' % i] = f32r(rng.uniform(-0.1, 0.1, tree['MLP_0']['Dense_%d' % i]['bias'].shape))
     g['bias%d' % depth] = g['bias%d' % depth] + 9.0              # (sigmoid(out - 10) off its flat tail)
-    g.update(t_frames=np.array(T_FRAMES[:B]), t_start_obs=0.0, t_injection=T_INJ, hparams=np.array(list(dom) + [3, depth, width, 1.0]))
+    g.update(t_frames=np.array(T_FRAMES[:B]), t_start_obs=0.0, t_injection=T_INJ, hparams=np.array(list(dom) + [deg, depth, width, 1.0]))
     # no domain or injection mask decided within f32 rounding; pre-injection samples in frame 0, fewer of them in the last frame
     assert not mask_tie_points(g).any()
     tM = g['t_frames'].reshape(-1, 1, 1, 1) / onp.GM_C3_SGRA_HR + g['t_geos'] - T_INJ
@@ -65,5 +73,4 @@ def problem(name):
     assert len(set(T_FRAMES[:B])) == B and 0 < pre[0] < tM[0].size and pre[-1] < pre[0]
     gen = torch.Generator().manual_seed(width + depth + S)
     dimg = (torch.rand((B, max(S, 1), H * Wd), generator=gen, dtype=torch.float64) - 0.4).float().double()
-    _PROBLEMS[name] = dict(g=g, dimg=dimg, dom=dom, depth=depth, width=width, S=S, B=B, spatial=(H, Wd))
-    return _PROBLEMS[name]
+    return dict(g=g, dimg=dimg, dom=dom, depth=depth, width=width, S=S, B=B, spatial=(H, Wd))

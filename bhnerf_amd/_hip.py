@@ -47,6 +47,10 @@ class bhn_frames(C.Structure):
     _fields_ = [('B', C.c_int32), ('tM0', C.c_void_p), ('clock_probe', C.c_void_p)]      # clock_probe: NULL unless bench.py measures the kernels' clocks
 
 
+class bhn_volume_view(C.Structure):
+    _fields_ = [('facewidth', C.c_double), ('linewidth', C.c_double), ('bh_radius', C.c_double), ('bh_albedo', C.c_double * 3)]
+
+
 _P, _I32, _I64, _F, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 _MP, _GP, _FP = C.POINTER(bhn_model), C.POINTER(bhn_geom), C.POINTER(bhn_frames)
 
@@ -75,6 +79,7 @@ SIGNATURES = {
     'bhn_grid_predict_fwd': (C.c_int, [_GP, _FP, _P, _I32, _F, _P, _P]),
     'bhn_grid_render_fwd': (C.c_int, [_GP, _FP, _P, _I32, _F, _P, _P]),
     'bhn_grid_render_bwd': (C.c_int, [_GP, _FP, _P, _I32, _F, _P, _P, _P]),
+    'bhn_volume_render': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _P, _I32, C.POINTER(bhn_volume_view), _P, _P]),
     'bhn_adam_step': (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _P]),
     'bhn_adam_hyper': (C.c_int, [_I64, _F, _F, _F, C.POINTER(C.c_float)]),
     'bhn_adam_step_dev': (C.c_int, [_P, _P, _P, _P, _I64, _P, _F, _F, _F, _F, _P]),

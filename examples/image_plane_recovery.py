@@ -3,7 +3,10 @@
   Kerr geodesics (own tracer)  ->  Doppler factor  ->  a rotating Gaussian hotspot rendered through the voxel
   renderer as the 'observed' movie  ->  NeRF_Predictor trained on the image-plane chi^2  ->  3-D emission sampled back.
 
-    python examples/image_plane_recovery.py [--size 32] [--ngeo 48] [--iters 300]
+    python examples/image_plane_recovery.py [--size 32] [--ngeo 48] [--iters 300] [--render out]
+
+--render PATH also renders the recovered volume through visualization.VolumeVisualizer (wireframe cube, black-hole sphere) and
+saves PATH.npy, plus PATH.png when matplotlib is installed.
 """
 import argparse
 import os
@@ -25,6 +28,7 @@ def main():
     ap.add_argument('--width', type=int, default=128)
     ap.add_argument('--mode', default='bf16', choices=['bf16', 'f32'], help='arithmetic of the fused kernels')
     ap.add_argument('--batch', type=int, default=4, help='frames per step')
+    ap.add_argument('--render', metavar='PATH', default=None, help='render the recovered volume to PATH.npy (and PATH.png with matplotlib)')
     args = ap.parse_args()
     fov, rmax = 16.0, 8.0
     geos = kgeo.image_plane_geos(0.3, np.deg2rad(30.0), (-fov / 2, fov / 2), (-fov / 2, fov / 2), ngeo=args.ngeo,
@@ -58,6 +62,32 @@ def main():
     vol = network.sample_3d_grid(predictor.apply, opt.state.params, fov=2 * rmax, resolution=n)
     i = np.unravel_index(np.argmax(vol), vol.shape)
     print('recovered emission peaks at (x, y, z) = (%.1f, %.1f, %.1f) M; truth (5.0, 0.0, 0.0) at t = 0' % (ax[i[0]], ax[i[1]], ax[i[2]]))
+    if args.render:
+        render_volume(args.render, predictor, opt.state.params, rmax)
+
+
+def render_volume(path, predictor, params, rmax, resolution=96):
+    """The recovered emission at t = 0 as the reference's notebooks show it: sampled at the visualizer's points, rendered inside
+    the wireframe cube of face 1.9 rmax with the black hole drawn at r = 2 M."""
+    from bhnerf_amd import visualization
+    visualizer = visualization.VolumeVisualizer(resolution, resolution, resolution)
+    visualizer.set_view(cam_r=37.0, domain_r=rmax, azimuth=0.0, zenith=np.pi / 3)
+    emission = network.sample_3d_grid(predictor.apply, params, coords=visualizer.coords)
+    image = visualizer.render(emission, facewidth=1.9 * rmax, bh_radius=2.0, linewidth=0.1).clip(max=1)
+    np.save(path + '.npy', image)
+    saved = path + '.npy'
+    try:
+        import matplotlib
+        matplotlib.use('Agg')
+        import matplotlib.pyplot as plt
+        plt.imsave(path + '.png', np.clip(image, 0, 1))
+        saved += ', ' + path + '.png'
+    except ImportError:
+        pass
+    k = np.unravel_index(np.argmax(emission), emission.shape)
+    inside = np.abs(visualizer._pts[k]).max() < 0.95 * rmax
+    print('rendered %s: %d x %d image, brightest sample at (%.1f, %.1f, %.1f) M, %s the wireframe cube'
+          % (saved, image.shape[1], image.shape[0], *visualizer._pts[k], 'inside' if inside else 'OUTSIDE'))
 
 
 if __name__ == '__main__':

@@ -57,7 +57,8 @@ extern "C" {
 
 #define BHN_ABI_VERSION 5      /* 3: BHN_BF16_T8 / BHN_T8_CALIBRATE, bhn_adam_hyper, bhn_adam_step_dev, bhn_render_bwd_tape_kernel_name_for;
                                 * 4: bhn_geom.ray_span; posenc_deg <= 10, net_width <= 512 (general path);
-                                * 5: bhn_frames.clock_probe, bhn_tape_info, bhn_mfma_probe */
+                                * 5: bhn_frames.clock_probe, bhn_tape_info, bhn_mfma_probe; bhn_volume_render added later without a
+                                *    new number (additive): version 5 now has 33 entry points */
 
 enum { BHN_OK = 0, BHN_EINVAL = 1, BHN_EUNSUPPORTED = 2, BHN_EHIP = 3, BHN_EWORKSPACE = 4 };
 enum { BHN_F32 = 0, BHN_BF16 = 1, BHN_BF16_T8 = 2 };
@@ -249,6 +250,26 @@ BHN_API int bhn_grid_render_fwd(const bhn_geom *geom, const bhn_frames *fr, cons
                         float *images, void *stream);
 BHN_API int bhn_grid_render_bwd(const bhn_geom *geom, const bhn_frames *fr, const float *grid, int32_t res, float scale,
                         const float *dimages, float *dgrid, void *stream);
+
+/* visualization.VolumeVisualizer.render (visualization.py:545-591) fused: colour map -> wireframe cube (draw_cube, :702-736) ->
+ * black-hole sphere (draw_bh, :748-755) -> alpha_composite (:628-663), all N frames over the shared sample points in one launch.
+ * pts (H,W,S,3): the visualizer's sample points (set_view); emission: frame n is (H,W,S) at emission + n*frame_stride; alpha_scale
+ * (N): what the frame's emission is multiplied by to give its alpha, 1 / amax(frame n) in the reference; lut (lut_n,3): the colour
+ * table, entry int(e*lut_n) clamped to [0, lut_n-1] (matplotlib's under / over colours of its stock maps); images (N,H,W,3).
+ * Per point: rgb = clip(lut - 0.05), alpha = e*alpha_scale + 1e6 sum_q exp(-|p - q| / linewidth^2) over the 3072 wireframe points
+ * q (8 vertices x 6 directions x linspace(0, facewidth, 64): the outward stubs and double-drawn edges included); all four channels 0
+ * where max|p_c| > facewidth/2 + linewidth; inside bh_radius (> 0) rgb = ((-1,-1,1)/sqrt 3 . p) * bh_albedo, alpha = 1; clip to
+ * [0, 1]; colour x step length of image ROW 0 in the same column (the reference's dists[0, ...]); back-to-front composite with the
+ * points inside the cube (max|p_c| < facewidth/2 - linewidth, |p| > bh_radius) added un-attenuated; white background.
+ * Wireframe terms farther than 39 linewidth^2 from the point are dropped: less than 2^-24 of alpha in total (csrc/volume_render.hip).
+ * Bitwise reproducible; a frame's image does not depend on N.  BHN_EINVAL before any launch: null pointers, N/H/W/S < 1,
+ * lut_n < 2, facewidth <= 0, linewidth <= 0, bh_radius < 0.  Non-finite emission is outside the contract. */
+typedef struct { double facewidth, linewidth, bh_radius, bh_albedo[3]; } bhn_volume_view;   /* host; double: the wires lie at
+                                          * +-facewidth/2 and alpha falls by e per linewidth^2 = 0.01 of distance, so a facewidth
+                                          * rounded to float (15.2: off by 2e-7) already changes an image by 2e-6 of its maximum */
+BHN_API int bhn_volume_render(const float *pts, const float *emission, const float *alpha_scale, int32_t N, int32_t H, int32_t W,
+                      int32_t S, int64_t frame_stride, const float *lut, int32_t lut_n, const bhn_volume_view *view,
+                      float *images, void *stream);
 
 /* optax.adam + polynomial_schedule(power=1) as used by init_state (network.py:173-174, 621):
  * g' = g*grad_scale (the 1/ndev of pmean, network.py:620); t = 1-based update count. */

@@ -1,4 +1,4 @@
-"""ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h).
+"""ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h) and of libbhnerf_kerr.so (include/bhnerf_kerr.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -51,7 +51,7 @@ class bhn_volume_view(C.Structure):
     _fields_ = [('facewidth', C.c_double), ('linewidth', C.c_double), ('bh_radius', C.c_double), ('bh_albedo', C.c_double * 3)]
 
 
-_P, _I32, _I64, _F, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
+_P, _I32, _I64, _F, _D, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _MP, _GP, _FP = C.POINTER(bhn_model), C.POINTER(bhn_geom), C.POINTER(bhn_frames)
 
 # name -> (restype, argtypes); must list every symbol include/bhnerf_hip.h declares
@@ -91,17 +91,25 @@ SIGNATURES = {
     'bhn_selftest': (C.c_int, [C.POINTER(_I32), _P, _SZ]),
 }
 
+# libbhnerf_kerr.so (include/bhnerf_kerr.h): the Kerr ray tracer, a library of its own beside the hot path's
+KERR_LIB_PATH = os.path.join(CSRC, 'libbhnerf_kerr.so')
+KERR_SIGNATURES = {
+    'bhn_kerr_last_error': (C.c_char_p, []),
+    'bhn_kerr_trace': (C.c_int, [_P, _P, _I64, _D, _D, _D, _D, _D, _D, _I32, _I32, _P, _P, _P, _P]),
+}
+
 _lib = None
+_kerr_lib = None
 
 
 def build(verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
+    """Compile the HIP libraries in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     res = subprocess.run(['make', '-C', CSRC, '-j4'], capture_output=True, text=True)
     if verbose or res.returncode != 0:
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building libbhnerf_hip.so failed (make -C %s)' % CSRC)
+        raise HipError('building libbhnerf_hip.so / libbhnerf_kerr.so failed (make -C %s)' % CSRC)
     return LIB_PATH
 
 
@@ -129,6 +137,29 @@ def lib():
             fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
+
+
+def kerr_lib():
+    """The loaded ray-tracer library; raises HipError (never falls back) when it is missing."""
+    global _kerr_lib
+    if _kerr_lib is None:
+        if not os.path.exists(KERR_LIB_PATH):
+            raise HipError('%s not found: run `python -c "import __graft_entry__ as g; g.build()"` '
+                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % KERR_LIB_PATH)
+        try:
+            handle = C.CDLL(KERR_LIB_PATH)
+            for name, (res, args) in KERR_SIGNATURES.items():
+                fn = getattr(handle, name)
+                fn.restype, fn.argtypes = res, args
+        except (OSError, AttributeError) as exc:
+            raise HipError('cannot load %s: %s (rebuild it: make -C bhnerf_amd/csrc)' % (KERR_LIB_PATH, exc))
+        _kerr_lib = handle
+    return _kerr_lib
+
+
+def kerr_check(rc):
+    if rc != 0:
+        raise HipError('libbhnerf_kerr: %s (code %d)' % (kerr_lib().bhn_kerr_last_error().decode(), rc))
 
 
 def check(rc):

@@ -41,13 +41,14 @@ def image_plane_model(inc, spin, params, rot_angle=0.0, randomize_subpixel_rays=
     (inclination, spin) hypothesis (alma.py:27-64).
 
     ``params``: ``num_alpha, num_beta, fov_M, z_width, rmin`` (a radius or ``'ISCO'``), ``Q_frac``, ``b_consts``
-    (``arad, avert, ator``), ``Omega_dir`` (``'cw'|'ccw'``) and optionally ``Omega_frac`` (sub-Keplerian factor)."""
+    (``arad, avert, ator``), ``Omega_dir`` (``'cw'|'ccw'``) and optionally ``Omega_frac`` (sub-Keplerian factor) and ``tracer``
+    (``'numpy'|'hip'``: where the geodesics are integrated, ``geodesics.image_plane_geos``'s ``backend``; default ``'numpy'``)."""
     fov = params['fov_M']
     rmin = float(constants.isco_pro(spin)) if params['rmin'] == 'ISCO' else params['rmin']
     rmax = fov / 2.0
     geos = kgeo.image_plane_geos(spin, inc, num_alpha=params['num_alpha'], num_beta=params['num_beta'],
                                  alpha_range=[-fov / 2.0, fov / 2.0], beta_range=[-fov / 2.0, fov / 2.0],
-                                 randomize_subpixel_rays=randomize_subpixel_rays).fillna(0.0)
+                                 randomize_subpixel_rays=randomize_subpixel_rays, backend=params.get('tracer', 'numpy')).fillna(0.0)
 
     # prograde / retrograde Keplerian rotation, Doppler boosting
     sqrt_M = np.sqrt(geos.M)

@@ -1,0 +1,243 @@
+// Per-ray stepping code of bhn_kerr_trace: geodesics._integrate (bhnerf_amd/geodesics.py) restated for one ray.
+//
+// No HIP dependency: kerr_trace.hip compiles it for the device (one lane per ray), tools/kerr_trace_host.cpp for the CPU
+// with a plain C++ compiler, so that the same arithmetic can be run under a sanitizer and compared with the NumPy code.
+// Every expression keeps NumPy's order of operations (x ** 2 is x * x there) and floating-point contraction is switched off:
+// host and device then differ from NumPy only by the sin / cos of their maths library and by s * s * s for s ** 3, and a
+// ray's second pass repeats its first bit for bit.
+//
+// Scheme (see the module docstring of geodesics.py): second-order form r'' = R'/2, theta'' = Theta'/2 in Mino time, classical RK4
+// on (r, theta, phi, t, v_r, v_theta) with the per-ray step  dl = h (1 + r / r_c) / r^2 * clip((sin theta / 0.25)^2, 0.05, 1);
+// after a step v_r is re-derived from R where R > 1e-2 r^4 and v_theta from Theta where Theta > 1e-2 (eta + a^2 + lam^2), sign kept;
+// a step that ends at !(r > 1.02 r_hor) is not taken and ends the ray (captured; also a NaN), a ray with r > distance and v_r > 0
+// has escaped.  Pass 1 finds the ray's total Mino time, pass 2 repeats it and writes the samples at k / ngeo of that time
+// (k = 1..ngeo) by cubic Hermite interpolation inside the step that crosses them; samples a ray never reaches hold its end state.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define KT_HD __host__ __device__ __forceinline__
+#else
+#define KT_HD inline
+#endif
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+#define KT_ROWS 7        // mino, r, theta, phi, t, vr, vth
+
+struct KtParams {
+    double a, M, inc, sin_i, cos_i;      // a = spin * M; sin / cos of the inclination from the host's maths library
+    double distance, h, r_c, r_cap;      // r_cap = 1.02 r_hor
+    int32_t max_steps, ngeo;
+};
+
+// Why the arguments are outside the contract, or NULL.  Host only.
+inline const char *kt_params_error(double spin, double inclination, double distance, double M, double h, double r_c, int32_t max_steps,
+                                   int32_t ngeo) {
+    if (!(M > 0.0)) return "M must be positive";
+    if (!(fabs(spin) <= 1.0)) return "|spin| must not exceed 1";
+    if (!(inclination > 0.0 && inclination <= 0.5 * M_PI + 1e-12)) return "inclination must be in (0, pi/2]";
+    if (!(h > 0.0)) return "step h must be positive";
+    if (!(r_c > 0.0)) return "r_c must be positive";
+    if (max_steps < 1) return "max_steps must be at least 1";
+    if (ngeo < 0) return "ngeo must not be negative";
+    (void)distance;                      // any value ends every ray: a NaN or a radius inside the horizon is captured at step 1
+    return nullptr;
+}
+
+inline KtParams kt_make_params(double spin, double inclination, double distance, double M, double h, double r_c, int32_t max_steps,
+                               int32_t ngeo) {
+    KtParams p;
+    p.a = spin * M;
+    p.M = M;
+    p.inc = inclination;
+    p.sin_i = sin(inclination);
+    p.cos_i = cos(inclination);
+    p.distance = distance;
+    p.h = h;
+    p.r_c = r_c;
+    const double d = M * M - p.a * p.a;
+    p.r_cap = (M + sqrt(d > 0.0 ? d : 0.0)) * 1.02;
+    p.max_steps = max_steps;
+    p.ngeo = ngeo;
+    return p;
+}
+
+struct KtRay {                           // constants of one ray
+    double a, M, a2, lam, lam2, eta, q;  // q = eta + (lam - a)^2
+};
+
+struct KtState { double r, th, ph, t, vr, vth; };
+
+KT_HD void kt_sincos(double x, double *s, double *c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    sincos(x, s, c);
+#else
+    *s = sin(x);
+    *c = cos(x);
+#endif
+}
+
+// geodesics.radial_potential
+KT_HD double kt_radial_potential(const KtRay &k, double r) {
+    const double Delta = r * r - 2.0 * k.M * r + k.a2;
+    const double P = r * r + k.a2 - k.a * k.lam;
+    return P * P - Delta * k.q;
+}
+
+// geodesics.angular_potential (cot = cos / sin for 1 / tan)
+KT_HD double kt_angular_potential(const KtRay &k, double th) {
+    double s, c;
+    kt_sincos(th, &s, &c);
+    const double ct = c / s;
+    return k.eta + k.a2 * (c * c) - k.lam2 * (ct * ct);
+}
+
+// geodesics._rhs: derivative of (r, theta, phi, t, vr, vth); s, c = sin, cos of y.th
+KT_HD KtState kt_rhs_sc(const KtRay &k, const KtState &y, double s, double c) {
+    const double r = y.r;
+    const double Delta = r * r - 2.0 * k.M * r + k.a2;
+    const double P = r * r + k.a2 - k.a * k.lam;
+    KtState f;
+    f.r = y.vr;
+    f.th = y.vth;
+    f.ph = k.a * P / Delta - k.a + k.lam / (s * s);
+    f.t = (r * r + k.a2) * P / Delta + k.a * (k.lam - k.a * (s * s));
+    f.vr = 2.0 * r * P - (r - k.M) * k.q;                          // R'(r) / 2
+    f.vth = -k.a2 * s * c + k.lam2 * c / (s * s * s);              // Theta'(theta) / 2
+    return f;
+}
+
+KT_HD KtState kt_rhs(const KtRay &k, const KtState &y) {
+    double s, c;
+    kt_sincos(y.th, &s, &c);
+    return kt_rhs_sc(k, y, s, c);
+}
+
+KT_HD KtState kt_axpy(const KtState &y, double w, const KtState &f) {          // y + w f
+    KtState o;
+    o.r = y.r + w * f.r; o.th = y.th + w * f.th; o.ph = y.ph + w * f.ph;
+    o.t = y.t + w * f.t; o.vr = y.vr + w * f.vr; o.vth = y.vth + w * f.vth;
+    return o;
+}
+
+KT_HD KtState kt_add2(const KtState &x, const KtState &f) {                    // x + 2 f
+    KtState o;
+    o.r = x.r + 2.0 * f.r; o.th = x.th + 2.0 * f.th; o.ph = x.ph + 2.0 * f.ph;
+    o.t = x.t + 2.0 * f.t; o.vr = x.vr + 2.0 * f.vr; o.vth = x.vth + 2.0 * f.vth;
+    return o;
+}
+
+KT_HD KtState kt_add(const KtState &x, const KtState &f) {
+    KtState o;
+    o.r = x.r + f.r; o.th = x.th + f.th; o.ph = x.ph + f.ph;
+    o.t = x.t + f.t; o.vr = x.vr + f.vr; o.vth = x.vth + f.vth;
+    return o;
+}
+
+// np.sign(v) * sqrt(|pot|)
+KT_HD double kt_signed_root(double v, double pot) {
+    const double q = sqrt(fabs(pot));
+    return v > 0.0 ? q : (v < 0.0 ? -q : (v == 0.0 ? 0.0 : v));
+}
+
+KT_HD double kt_clip0(double x) { return x < 0.0 ? 0.0 : x; }                   // np.clip(x, 0, None): a NaN stays
+
+KT_HD double kt_hermite(double c0, double c1, double c2, double c3, double y, double f, double yn, double fn) {
+    return c0 * y + c1 * f + c2 * yn + c3 * fn;
+}
+
+KT_HD void kt_store(double *dst, int64_t stride, double mino, const KtState &y) {
+    dst[0] = mino; dst[stride] = y.r; dst[2 * stride] = y.th; dst[3 * stride] = y.ph;
+    dst[4 * stride] = y.t; dst[5 * stride] = y.vr; dst[6 * stride] = y.vth;
+}
+
+// One ray, both passes.  samples (7, n, ngeo) or NULL with ngeo = 0, end (7, n), status (n); this call writes column i of each.
+KT_HD void kt_trace_ray(const KtParams &p, double alpha, double beta, int64_t i, int64_t n, double *samples, double *end,
+                        int32_t *status) {
+    KtRay k;
+    k.a = p.a; k.M = p.M; k.a2 = p.a * p.a;
+    k.lam = -alpha * p.sin_i;
+    k.eta = (alpha * alpha - k.a2) * (p.cos_i * p.cos_i) + beta * beta;
+    k.lam2 = k.lam * k.lam;
+    k.q = k.eta + (k.lam - k.a) * (k.lam - k.a);
+    const double vth_scale = 1e-2 * (k.eta + k.a2 + k.lam2);
+    const int32_t ngeo = p.ngeo;
+    double *const smp = ngeo > 0 ? samples + i * (int64_t)ngeo : nullptr;      // row stride n * ngeo
+    const int64_t row = n * (int64_t)ngeo;
+    const int passes = ngeo > 0 ? 2 : 1;
+    double total = 0.0;
+    for (int pass = 0; pass < passes; ++pass) {
+        KtState y;
+        y.r = p.distance; y.th = p.inc; y.ph = 0.0; y.t = 0.0;
+        y.vr = -sqrt(kt_clip0(kt_radial_potential(k, y.r)));                   // inwards, back in time
+        {
+            const double root = sqrt(kt_clip0(kt_angular_potential(k, y.th)));
+            y.vth = -(beta > 0.0 ? root : (beta < 0.0 ? -root : (beta == 0.0 ? 0.0 : beta)));
+        }
+        double mino = 0.0;
+        int32_t nxt = 0, step = 0;
+        bool done = false;
+        while (step < p.max_steps && !done) {
+            ++step;
+            double s, c;
+            kt_sincos(y.th, &s, &c);
+            const double sq = (s / 0.25) * (s / 0.25);
+            const double dl = p.h * (1.0 + y.r / p.r_c) / (y.r * y.r) * (sq < 0.05 ? 0.05 : (sq > 1.0 ? 1.0 : sq));
+            const KtState k1 = kt_rhs_sc(k, y, s, c);
+            KtState f = kt_rhs(k, kt_axpy(y, 0.5 * dl, k1));
+            KtState acc = kt_add2(k1, f);
+            f = kt_rhs(k, kt_axpy(y, 0.5 * dl, f));
+            acc = kt_add2(acc, f);
+            f = kt_rhs(k, kt_axpy(y, dl, f));
+            acc = kt_add(acc, f);
+            KtState yn = kt_axpy(y, dl / 6.0, acc);
+            const double Rn = kt_radial_potential(k, yn.r);
+            const double r2 = yn.r * yn.r;
+            if (Rn > 1e-2 * (r2 * r2)) yn.vr = kt_signed_root(yn.vr, Rn);
+            const double Tn = kt_angular_potential(k, yn.th);
+            if (Tn > vth_scale) yn.vth = kt_signed_root(yn.vth, Tn);
+            const bool captured = !(yn.r > p.r_cap);                           // (also a NaN): the step is not taken
+            const double mino_new = mino + dl;
+            if (pass == 1 && !captured && nxt < ngeo) {
+                double tgt = ((double)(nxt + 1) / (double)ngeo) * total;
+                if (tgt <= mino_new) {
+                    const KtState fn = kt_rhs(k, yn);
+                    const double dlw = dl > 0.0 ? dl : 1.0;
+                    do {
+                        const double w = (tgt - mino) / dlw, w2 = w * w, w3 = w * w * w;
+                        const double c0 = 2 * w3 - 3 * w2 + 1, c1 = (w3 - 2 * w2 + w) * dl, c2 = 3 * w2 - 2 * w3, c3 = (w3 - w2) * dl;
+                        KtState o;
+                        o.r = kt_hermite(c0, c1, c2, c3, y.r, k1.r, yn.r, fn.r);
+                        o.th = kt_hermite(c0, c1, c2, c3, y.th, k1.th, yn.th, fn.th);
+                        o.ph = kt_hermite(c0, c1, c2, c3, y.ph, k1.ph, yn.ph, fn.ph);
+                        o.t = kt_hermite(c0, c1, c2, c3, y.t, k1.t, yn.t, fn.t);
+                        o.vr = kt_hermite(c0, c1, c2, c3, y.vr, k1.vr, yn.vr, fn.vr);
+                        o.vth = kt_hermite(c0, c1, c2, c3, y.vth, k1.vth, yn.vth, fn.vth);
+                        kt_store(smp + nxt, row, tgt, o);
+                        ++nxt;
+                        tgt = ((double)(nxt + 1) / (double)ngeo) * total;
+                    } while (nxt < ngeo && tgt <= mino_new);
+                }
+            }
+            if (!captured) {
+                y = yn;
+                mino = mino_new;
+            }
+            done = captured || (y.r > p.distance && y.vr > 0.0);
+        }
+        if (pass == 0) {
+            status[i] = done ? step : -1;
+            kt_store(end + i, n, mino, y);
+            total = mino;
+            if (!done) {                                                       // out of steps: every sample holds the state reached
+                for (int32_t j = 0; j < ngeo; ++j) kt_store(smp + j, row, mino, y);
+                return;
+            }
+        } else {
+            for (; nxt < ngeo; ++nxt) kt_store(smp + nxt, row, mino, y);       // captured rays; a last target missed by rounding
+        }
+    }
+}

@@ -166,21 +166,80 @@ def _integrate(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, t
     return out, lam, eta
 
 
-def trace(alpha, beta, spin, inclination, distance=1000.0, M=1.0, h=0.02, r_c=5.0, max_steps=400000):
+BACKENDS = ('numpy', 'hip')
+SAMPLE_ROWS = ('mino', 'r', 'theta', 'phi', 't', 'vr', 'vth')
+
+
+def _check_backend(backend):
+    if backend not in BACKENDS:
+        raise ValueError('backend must be one of %s, not %r' % (', '.join(repr(b) for b in BACKENDS), backend))
+
+
+def _trace_hip(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, ngeo, device=None):
+    """``bhn_kerr_trace`` (include/bhnerf_kerr.h; csrc/kerr_trace.hip restates ``_integrate`` with one GPU lane per ray) on
+    one set of rays: ``(end (7, n), samples (7, n, ngeo) or None, lam, eta)`` as NumPy arrays, ``end`` rows final Mino time,
+    r, theta, phi, t, vr, vth.  Raises ``_integrate``'s RuntimeError when a ray is not finished after ``max_steps``."""
+    import torch
+    from . import _hip
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64).ravel()
+    beta = np.ascontiguousarray(beta, dtype=np.float64).ravel()
+    inc = float(inclination)
+    if not (0.0 < inc <= 0.5 * np.pi + 1e-12):
+        raise ValueError('inclination must be in (0, pi/2]')
+    lib = _hip.kerr_lib()
+    if not torch.cuda.is_available():
+        raise _hip.HipError("backend='hip' needs a HIP device (there is no CPU fallback; backend='numpy' is the host tracer)")
+    dev = torch.device('cuda' if device is None else device)
+    n, ngeo = alpha.size, int(ngeo)
+    _, lam, eta = _initial_state(alpha, beta, float(spin) * M, inc, distance, M)
+    with torch.cuda.device(dev):
+        a_d, b_d = torch.as_tensor(alpha, device=dev), torch.as_tensor(beta, device=dev)
+        end = torch.empty((7, n), dtype=torch.float64, device=dev)
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+        samples = torch.empty((7, n, ngeo), dtype=torch.float64, device=dev) if ngeo > 0 else None
+        _hip.kerr_check(lib.bhn_kerr_trace(_hip.ptr(a_d), _hip.ptr(b_d), n, float(spin), inc, float(distance), float(M), float(h), float(r_c),
+                                      int(max_steps), ngeo, _hip.ptr(samples), _hip.ptr(end), _hip.ptr(status), _hip.stream_ptr(dev)))
+        if bool((status < 0).any()):
+            raise RuntimeError('geodesic integration did not terminate in %d steps' % max_steps)
+        return end.cpu().numpy(), (samples.cpu().numpy() if ngeo > 0 else None), lam, eta
+
+
+def trace(alpha, beta, spin, inclination, distance=1000.0, M=1.0, h=0.02, r_c=5.0, max_steps=400000, backend='numpy', device=None):
     """Integrate one geodesic per (alpha, beta) backwards from the observer until it is captured or has escaped.
     Returns ``(mino_end, state_end, lam, eta)`` with ``state_end`` rows ``(r, theta, phi, t, vr, vth)`` (phi and t of
-    the forward equations: negate them for the backward ray)."""
+    the forward equations: negate them for the backward ray).  ``backend='hip'`` runs the same integration on the GPU
+    (``device``: a torch device, default the current one)."""
+    _check_backend(backend)
+    if backend == 'hip':
+        end, _, lam, eta = _trace_hip(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, 0, device)
+        return end[0], end[1:], lam, eta
     return _integrate(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps)
 
 
+def _sample_rays(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, ngeo, backend, device):
+    """``ngeo`` samples per ray, uniform in Mino time: ``(samples (7, n, ngeo) with the rows SAMPLE_ROWS, lam, eta)``."""
+    if backend == 'hip':
+        _, samp, lam, eta = _trace_hip(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, ngeo, device)
+        return samp, lam, eta
+    mino_end, _, lam, eta = _integrate(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps)
+    target = (np.arange(1, ngeo + 1)[None, :] / float(ngeo)) * mino_end[:, None]            # uniform in Mino time
+    samp, _, _ = _integrate(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, targets=target)
+    return samp, lam, eta
+
+
 def image_plane_geos(spin, inclination, alpha_range, beta_range, ngeo=100, num_alpha=64, num_beta=64, distance=1000.0,
-                     E=1.0, M=1.0, randomize_subpixel_rays=False, verbose=False, h=0.02, chunk=65536):
+                     E=1.0, M=1.0, randomize_subpixel_rays=False, verbose=False, h=0.02, chunk=65536, max_steps=400000,
+                     backend='numpy', device=None):
     """Kerr geodesics for the whole image plane (signature of ``bhnerf.kgeo.image_plane_geos``, kgeo.py:6-63).
 
     Returns a ``Geodesics`` record with arrays of shape ``(num_alpha, num_beta, ngeo)`` (per-ray constants
     ``(num_alpha, num_beta)``): ``r, theta, phi, t, x, y, z, mino, affine, dtau, Sigma, Delta, Xi, omega, R, Theta``,
     ``alpha, beta, lam, eta`` and the scalars ``spin, inc, M, E, r_o``.  ``t`` is the coordinate time relative to the
-    arrival at the observer (negative along the ray), ``dtau`` the Mino step between consecutive samples."""
+    arrival at the observer (negative along the ray), ``dtau`` the Mino step between consecutive samples.
+
+    ``backend``: ``'numpy'`` (the default) integrates on the host, ``'hip'`` on the GPU (``bhn_kerr_trace``, one call per
+    ``chunk`` rays on ``device``); the record is built from the samples by the same code either way."""
+    _check_backend(backend)
     alpha_1d = np.linspace(*alpha_range, num_alpha)
     beta_1d = np.linspace(*beta_range, num_beta)
     if randomize_subpixel_rays:
@@ -188,18 +247,16 @@ def image_plane_geos(spin, inclination, alpha_range, beta_range, ngeo=100, num_a
         beta_1d = beta_1d + (np.random.random(num_beta) - 0.5) * (beta_range[1] - beta_range[0]) / max(num_beta - 1, 1)
     alpha, beta = np.meshgrid(alpha_1d, beta_1d, indexing='ij')
     n = alpha.size
-    out = {k: np.empty((n, ngeo)) for k in ('r', 'theta', 'phi', 't', 'mino', 'vr', 'vth')}
+    out = {k: np.empty((n, ngeo)) for k in SAMPLE_ROWS}
     lam_all, eta_all = np.empty(n), np.empty(n)
     af, bf = alpha.ravel(), beta.ravel()
     # beta = 0 exactly sits on the theta turning point of the observer: nudge it (measure-zero set of rays)
     bf = np.where(bf == 0.0, 1e-9, bf)
     for c0 in range(0, n, chunk):
         sl = slice(c0, min(c0 + chunk, n))
-        mino_end, _, lam, eta = _integrate(af[sl], bf[sl], spin, inclination, distance, M, h, 5.0, 400000)
+        samp, lam, eta = _sample_rays(af[sl], bf[sl], spin, inclination, distance, M, h, 5.0, max_steps, ngeo, backend, device)
         lam_all[sl], eta_all[sl] = lam, eta
-        target = (np.arange(1, ngeo + 1)[None, :] / float(ngeo)) * mino_end[:, None]            # uniform in Mino time
-        samp, _, _ = _integrate(af[sl], bf[sl], spin, inclination, distance, M, h, 5.0, 400000, targets=target)
-        for row, name in enumerate(('mino', 'r', 'theta', 'phi', 't', 'vr', 'vth')):
+        for row, name in enumerate(SAMPLE_ROWS):
             out[name][sl] = samp[row]
         if verbose:
             print('traced rays %d-%d of %d' % (c0, sl.stop, n))

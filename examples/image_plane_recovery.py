@@ -3,7 +3,7 @@
   Kerr geodesics (own tracer)  ->  Doppler factor  ->  a rotating Gaussian hotspot rendered through the voxel
   renderer as the 'observed' movie  ->  NeRF_Predictor trained on the image-plane chi^2  ->  3-D emission sampled back.
 
-    python examples/image_plane_recovery.py [--size 32] [--ngeo 48] [--iters 300] [--render out]
+    python examples/image_plane_recovery.py [--size 32] [--ngeo 48] [--iters 300] [--render out] [--tracer hip]
 
 --render PATH also renders the recovered volume through visualization.VolumeVisualizer (wireframe cube, black-hole sphere) and
 saves PATH.npy, plus PATH.png when matplotlib is installed.
@@ -29,10 +29,11 @@ def main():
     ap.add_argument('--mode', default='bf16', choices=['bf16', 'f32'], help='arithmetic of the fused kernels')
     ap.add_argument('--batch', type=int, default=4, help='frames per step')
     ap.add_argument('--render', metavar='PATH', default=None, help='render the recovered volume to PATH.npy (and PATH.png with matplotlib)')
+    ap.add_argument('--tracer', default='numpy', choices=['numpy', 'hip'], help='where the geodesics are integrated: on the host or on the GPU')
     args = ap.parse_args()
     fov, rmax = 16.0, 8.0
     geos = kgeo.image_plane_geos(0.3, np.deg2rad(30.0), (-fov / 2, fov / 2), (-fov / 2, fov / 2), ngeo=args.ngeo,
-                                 num_alpha=args.size, num_beta=args.size)
+                                 num_alpha=args.size, num_beta=args.size, backend=args.tracer)
     Omega = np.nan_to_num(1.0 / (np.sqrt(geos.x ** 2 + geos.y ** 2) ** 1.5 + geos.spin))      # Keplerian about the spin axis
     geos['g'] = kgeo.doppler_factor(geos, kgeo.azimuthal_velocity_vector(geos, Omega))
     # ground truth: a Gaussian hotspot on a 32^3 grid, orbiting with Omega

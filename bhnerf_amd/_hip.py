@@ -1,4 +1,5 @@
-"""ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h) and of libbhnerf_kerr.so (include/bhnerf_kerr.h).
+"""ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h) and libbhnerf_eht.so
+(include/bhnerf_eht.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -98,8 +99,19 @@ KERR_SIGNATURES = {
     'bhn_kerr_trace': (C.c_int, [_P, _P, _I64, _D, _D, _D, _D, _D, _D, _I32, _I32, _P, _P, _P, _P]),
 }
 
+# libbhnerf_eht.so (include/bhnerf_eht.h): the EHT chi-square from (u, v) coordinates, a library of its own as well
+EHT_LIB_PATH = os.path.join(CSRC, 'libbhnerf_eht.so')
+BHN_EINVAL, BHN_EWORKSPACE = 1, 4
+EHT_SIGNATURES = {
+    'bhn_eht_last_error': (C.c_char_p, []),
+    'bhn_eht_ws_bytes': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'bhn_eht_vis': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _D, _D, _P, _P, _SZ, _P]),
+    'bhn_eht_chi2_uv': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _D, _D, _I32, _P, _P, _F, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
+}
+
 _lib = None
 _kerr_lib = None
+_eht_lib = None
 
 
 def build(verbose=False):
@@ -109,7 +121,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building libbhnerf_hip.so / libbhnerf_kerr.so failed (make -C %s)' % CSRC)
+        raise HipError('building libbhnerf_hip.so / libbhnerf_kerr.so / libbhnerf_eht.so failed (make -C %s)' % CSRC)
     return LIB_PATH
 
 
@@ -160,6 +172,29 @@ def kerr_lib():
 def kerr_check(rc):
     if rc != 0:
         raise HipError('libbhnerf_kerr: %s (code %d)' % (kerr_lib().bhn_kerr_last_error().decode(), rc))
+
+
+def eht_lib():
+    """The loaded (u, v) EHT library; raises HipError (never falls back) when it is missing."""
+    global _eht_lib
+    if _eht_lib is None:
+        if not os.path.exists(EHT_LIB_PATH):
+            raise HipError('%s not found: run `python -c "import __graft_entry__ as g; g.build()"` '
+                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % EHT_LIB_PATH)
+        try:
+            handle = C.CDLL(EHT_LIB_PATH)
+            for name, (res, args) in EHT_SIGNATURES.items():
+                fn = getattr(handle, name)
+                fn.restype, fn.argtypes = res, args
+        except (OSError, AttributeError) as exc:
+            raise HipError('cannot load %s: %s (rebuild it: make -C bhnerf_amd/csrc)' % (EHT_LIB_PATH, exc))
+        _eht_lib = handle
+    return _eht_lib
+
+
+def eht_check(rc):
+    if rc != 0:
+        raise HipError('libbhnerf_eht: %s (code %d)' % (eht_lib().bhn_eht_last_error().decode(), rc))
 
 
 def check(rc):

@@ -9,7 +9,7 @@ import functools
 import numpy as np
 import torch
 
-from . import _hip
+from . import _hip, observation
 
 COMPACT_POINTS = True          # point-level compaction of the domain mask for the fused kernels (RayGeometry.compact)
 COMPACT_BELOW = 0.9            # ... when less than this fraction of the samples is inside the domain
@@ -494,8 +494,97 @@ def _eht_operands(images, A, target, sigma, dtype):
     return code, img, Ar, tgt, sig, N, C_, nvis, R
 
 
+def _eht_uv_operands(images, op, N):
+    """(images (N, H, W) float32, the operator on the images' device, Sx) for libbhnerf_eht; AttributeError on a shape mismatch."""
+    dev = images.device
+    H, W = op.H, op.W
+    if int(images.numel()) != N * H * W:
+        raise AttributeError('images of {} elements are not {} planes of {} x {} pixels'.format(int(images.numel()), N, H, W))
+    if not (isinstance(op.uv, torch.Tensor) and op.uv.device == dev):
+        op = op.to(dev)
+    B = int(op.uv.shape[0])
+    if B < 1 or N % B != 0:
+        raise AttributeError('{} image planes do not divide into the {} frames of uv'.format(N, B))
+    return images.reshape(N, H, W).to(torch.float32).contiguous(), op, N // B
+
+
+def eht_vis_uv(movie, op):
+    """Visibilities (nt, [S,] nvis) complex64 of movie (nt, [S,] H, W) from the operator's (u, v) (bhn_eht_vis)."""
+    lead = tuple(movie.shape[:-2])
+    if tuple(movie.shape[-2:]) != (op.H, op.W) or len(lead) < 1 or lead[0] != op.shape[0]:
+        raise AttributeError('movie {} does not match {} frames of {} x {} pixels'.format(tuple(movie.shape), op.shape[0], op.H, op.W))
+    N = int(np.prod(lead))
+    img, op, Sx = _eht_uv_operands(movie, op, N)
+    dev, lib = img.device, _hip.eht_lib()
+    nbytes = int(lib.bhn_eht_ws_bytes(N, op.nvis, 0, op.H, op.W))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    out = torch.empty((N, op.nvis, 2), dtype=torch.float32, device=dev)
+    psy, psx = op.psize
+    with torch.cuda.device(dev):
+        _hip.eht_check(lib.bhn_eht_vis(_hip.ptr(img), _hip.ptr(op.uv), N, Sx, op.nvis, op.H, op.W, psx, psy, _hip.ptr(out), _hip.ptr(ws),
+                                       nbytes, _hip.stream_ptr(dev)))
+    return torch.view_as_complex(out).reshape(lead + (op.nvis,))
+
+
+def chi2_eht_uv(images, op, target, sigma, scale, dtype, want_grad=True):
+    """chi2_eht from an observation.DirectDFT: the loss and its image gradient from the (u, v) coordinates (bhn_eht_chi2_uv),
+    no dense matrix anywhere.  Raises the AttributeErrors of the dense path for a wrong count, before any launch."""
+    code = EHT_DTYPES.get(dtype)
+    if code is None:
+        raise AttributeError('eht dtype ({}) not supported'.format(dtype))
+    if dtype == 'cphase' and op.ncp == 0:
+        raise AttributeError("dtype='cphase' needs a DirectDFT with triangles")
+    if dtype != 'cphase' and op.ncp != 0:
+        raise AttributeError("a DirectDFT with triangles is a closure-phase operator: dtype='{}' needs one without".format(dtype))
+    nterm = op.ncp if dtype == 'cphase' else op.nvis
+    if target.ndim < 2 or int(target.shape[-1]) != nterm:
+        raise AttributeError('target {} should end in {} {} for dtype={}'.format(
+            tuple(target.shape), nterm, 'closure triangles' if dtype == 'cphase' else 'visibilities', dtype))
+    N = int(np.prod(target.shape[:-1]))
+    img, op, Sx = _eht_uv_operands(images, op, N)
+    if int(target.shape[0]) != int(op.uv.shape[0]):
+        raise AttributeError('target of {} frames, uv of {}'.format(int(target.shape[0]), int(op.uv.shape[0])))
+    dev, lib = img.device, _hip.eht_lib()
+    tgt = _eht_uv_array(target, dev, torch.complex64 if dtype == 'vis' else torch.float32, None)
+    sig = _eht_uv_array(sigma, dev, torch.float32, tuple(target.shape))
+    key = (N, op.nvis, op.ncp, op.H, op.W)
+    nbytes = _EHT_WS_BYTES.get(key)
+    if nbytes is None:
+        nbytes = _EHT_WS_BYTES[key] = int(lib.bhn_eht_ws_bytes(*key))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    dimg = torch.empty_like(img) if want_grad else None
+    psy, psx = op.psize
+    args = (img.data_ptr(), op.uv.data_ptr(), N, Sx, op.nvis, op.H, op.W, psx, psy, code, tgt.data_ptr(), sig.data_ptr(), float(scale),
+            _hip.ptr(op.tri), _hip.ptr(op.tri_sign), op.ncp, loss.data_ptr(), dimg.data_ptr() if want_grad else None, ws.data_ptr(), nbytes,
+            _hip.stream_ptr(dev))
+    if dev.index is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            rc = lib.bhn_eht_chi2_uv(*args)
+    else:                                  # (the usual case: no device switch around a call of a few tens of microseconds)
+        rc = lib.bhn_eht_chi2_uv(*args)
+    _hip.eht_check(rc)
+    return loss, (dimg.reshape(images.shape) if want_grad else None)
+
+
+_EHT_WS_BYTES = {}
+
+
+def _eht_uv_array(x, dev, dtype, shape):
+    """`x` as a contiguous device tensor of `dtype` (broadcast to `shape` when given); a tensor that is all that already is taken
+    as it is (the per-step path: TemporalBatchedArgs hands over device tensors)."""
+    if not (isinstance(x, torch.Tensor) and x.device == dev and x.dtype == dtype):
+        x = torch.as_tensor(x, device=dev).to(dtype)
+    if shape is not None and tuple(x.shape) != shape:
+        x = x.expand(shape)
+    return x if x.is_contiguous() else x.contiguous()
+
+
 def chi2_eht(images, A, target, sigma, scale, dtype, want_grad=True):
-    """loss_fn_eht tail (network.py:541-564) on device -> (loss[1], dimages shaped like images or None)."""
+    """loss_fn_eht tail (network.py:541-564) on device -> (loss[1], dimages shaped like images or None).  ``A``: the dense DFT
+    matrices, or an ``observation.DirectDFT`` (the matrix-free path, chi2_eht_uv)."""
+    if isinstance(A, observation.DirectDFT):
+        return chi2_eht_uv(images, A, target, sigma, scale, dtype, want_grad=want_grad)
     code, img, Ar, tgt, sig, N, C_, nvis, R = _eht_operands(images, A, target, sigma, dtype)
     dev = img.device
     ws = torch.empty((int(_hip.lib().bhn_chi2_eht_ws_floats(N, C_, nvis, R)),), dtype=torch.float32, device=dev)

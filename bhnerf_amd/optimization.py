@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import _hip, checkpoints, engine, network, units
+from . import _hip, checkpoints, engine, network, observation, units
 
 try:  # progress bar is optional
     from tqdm.auto import tqdm
@@ -460,8 +460,22 @@ class TrainStep(object):
         (optimization.py:237-257).  See ``observation.dft_matrix`` for a direct-DFT `A`."""
         if dtype not in ('vis', 'amp', 'cphase'):
             raise AttributeError('eht dtype ({}) not supported'.format(dtype))
-        args = TemporalBatchedArgs(t_frames, [np.asarray(target), np.asarray(sigma), np.asarray(A)])
+        if not isinstance(A, observation.DirectDFT):       # (a DirectDFT stays what it is: the matrix-free path)
+            A = np.asarray(A)
+        args = TemporalBatchedArgs(t_frames, [np.asarray(target), np.asarray(sigma), A])
         return cls(dtype, args, network.gradient_step_eht, network.test_eht, scale)
+
+    @classmethod
+    def eht_uv(cls, t_frames, target, sigma, uv, fov, npix, dtype='vis', scale=1.0, triangles=None, pairs=None):
+        """Training step on EHT observables from the baselines' (u, v) coordinates instead of dense DFT matrices:
+        ``uv`` (nt, nvis, 2) float64 in wavelengths, ``fov`` in radians, ``npix`` an int or (H, W); for 'cphase' the
+        ``triangles`` (station triples with ``pairs`` (nvis, 2), or a (tri, tri_sign) table) and `target` / `sigma`
+        (nt, ncp) in radians.  See ``observation.DirectDFT``."""
+        if dtype == 'cphase' and triangles is None:
+            raise AttributeError("dtype='cphase' needs triangles")
+        if dtype != 'cphase' and triangles is not None:
+            raise AttributeError("triangles belong to dtype='cphase', not '{}'".format(dtype))
+        return cls.eht_arrays(t_frames, target, sigma, observation.DirectDFT(uv, fov, npix, triangles, pairs), dtype, scale)
 
     @classmethod
     def eht(cls, t_frames, obs, image_fov, image_size, chisqdata, pol='I', scale=1.0):
@@ -499,7 +513,9 @@ class TemporalBatchedArgs(object):
             args = [args]
         self.num_frames = len(t_frames)
         assert all([self.num_frames == arg.shape[0] for arg in args])
-        self.host_args = [np.asarray(a, dtype=np.complex64 if np.iscomplexobj(a) else np.float32) for a in args]
+        # (an observation.DirectDFT is kept as it is -- its uv stays float64 -- and batched with .take)
+        self.host_args = [a if isinstance(a, observation.DirectDFT)
+                          else np.asarray(a, dtype=np.complex64 if np.iscomplexobj(a) else np.float32) for a in args]
         self.t_values = np.asarray(units.strip(t_frames), dtype=np.float64)
         self.args = self.host_args + [self.t_values]
         self.default_t_units = units.hr
@@ -517,8 +533,9 @@ class TemporalBatchedArgs(object):
         else None."""
         if self._dev is None:
             dev = torch.device('cuda', torch.cuda.current_device())
-            self._dev = [torch.as_tensor(a, device=dev) for a in self.host_args]
-            same = len(self._dev) > 1 and len({(tuple(a.shape), a.dtype) for a in self._dev}) == 1
+            self._dev = [a.to(dev) if isinstance(a, observation.DirectDFT) else torch.as_tensor(a, device=dev) for a in self.host_args]
+            same = len(self._dev) > 1 and len({(tuple(a.shape), getattr(a, 'dtype', None)) for a in self._dev}) == 1 \
+                and not any(isinstance(a, observation.DirectDFT) for a in self._dev)
             self._stack = torch.stack(self._dev) if same else None
         return self._stack
 
@@ -530,9 +547,9 @@ class TemporalBatchedArgs(object):
             if stack is not None:
                 out = list(stack.index_select(1, idx))
             else:
-                out = [a.index_select(0, idx) for a in self._dev]
+                out = [a.take(idx) if isinstance(a, observation.DirectDFT) else a.index_select(0, idx) for a in self._dev]
         else:
-            out = [a[key, ...] for a in self.host_args]
+            out = [a.take(key) if isinstance(a, observation.DirectDFT) else a[key, ...] for a in self.host_args]
         out.append(self.t_values[key])
         return out
 

@@ -1,5 +1,5 @@
-"""ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h) and libbhnerf_eht.so
-(include/bhnerf_eht.h).
+"""ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
+(include/bhnerf_eht.h) and libbhnerf_grf.so (include/bhnerf_grf.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -109,9 +109,30 @@ EHT_SIGNATURES = {
     'bhn_eht_chi2_uv': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _D, _D, _I32, _P, _P, _F, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
 }
 
+# libbhnerf_grf.so (include/bhnerf_grf.h): Doppler factor and polarised transport factors of kgeo.py, the fourth library
+GRF_LIB_PATH = os.path.join(CSRC, 'libbhnerf_grf.so')
+
+
+class bhn_grf_geos(C.Structure):
+    _fields_ = [('n', C.c_int64), ('ngeo', C.c_int32)] + [(k, C.c_void_p) for k in (
+        'r', 'theta', 'affine', 'Delta', 'Sigma', 'Xi', 'R', 'Theta', 'lam', 'alpha', 'beta')] + [
+        ('spin', C.c_double), ('M', C.c_double), ('E', C.c_double), ('inc', C.c_double)]
+
+
+_GG = C.POINTER(bhn_grf_geos)
+GRF_SIGNATURES = {
+    'bhn_grf_last_error': (C.c_char_p, []),
+    'bhn_grf_ws_bytes': (_SZ, [_I64, _I32]),
+    'bhn_grf_doppler': (C.c_int, [_GG, _P, _D, _I32, _P, _P]),
+    'bhn_grf_fluid_field': (C.c_int, [_GG, _P, _D, _D, _D, _P, _P]),
+    'bhn_grf_domain_mean': (C.c_int, [_GG, _P, _D, _D, _D, _P, _P, _SZ, _P]),
+    'bhn_grf_transport': (C.c_int, [_GG, _P, _P, _P, _P, _D, _D, _D, _P, _P]),
+}
+
 _lib = None
 _kerr_lib = None
 _eht_lib = None
+_grf_lib = None
 
 
 def build(verbose=False):
@@ -121,7 +142,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building libbhnerf_hip.so / libbhnerf_kerr.so / libbhnerf_eht.so failed (make -C %s)' % CSRC)
+        raise HipError('building libbhnerf_hip.so / libbhnerf_kerr.so / libbhnerf_eht.so / libbhnerf_grf.so failed (make -C %s)' % CSRC)
     return LIB_PATH
 
 
@@ -195,6 +216,29 @@ def eht_lib():
 def eht_check(rc):
     if rc != 0:
         raise HipError('libbhnerf_eht: %s (code %d)' % (eht_lib().bhn_eht_last_error().decode(), rc))
+
+
+def grf_lib():
+    """The loaded (g, J) library; raises HipError (never falls back) when it is missing."""
+    global _grf_lib
+    if _grf_lib is None:
+        if not os.path.exists(GRF_LIB_PATH):
+            raise HipError('%s not found: run `python -c "import __graft_entry__ as g; g.build()"` '
+                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % GRF_LIB_PATH)
+        try:
+            handle = C.CDLL(GRF_LIB_PATH)
+            for name, (res, args) in GRF_SIGNATURES.items():
+                fn = getattr(handle, name)
+                fn.restype, fn.argtypes = res, args
+        except (OSError, AttributeError) as exc:
+            raise HipError('cannot load %s: %s (rebuild it: make -C bhnerf_amd/csrc)' % (GRF_LIB_PATH, exc))
+        _grf_lib = handle
+    return _grf_lib
+
+
+def grf_check(rc):
+    if rc != 0:
+        raise HipError('libbhnerf_grf: %s (code %d)' % (grf_lib().bhn_grf_last_error().decode(), rc))
 
 
 def check(rc):

@@ -1,15 +1,17 @@
 """ALMA light-curve helpers: the callers either side of the hot path for polarised light-curve fits
 (reference: bhnerf/alma.py).
 
-Everything here is host-side preparation (geodesics, Doppler factor, polarised transport factors -> ``raytracing_args``)
-or post-processing (chi-square of a checkpoint against the light curves).  The rendering itself goes through
+Preparation (geodesics, Doppler factor, polarised transport factors -> ``raytracing_args``) and post-processing (chi-square of a
+checkpoint against the light curves).  The preparation runs on the host by default; ``params['tracer'] = 'hip'`` integrates the
+geodesics on the GPU (``libbhnerf_kerr.so``) and ``params['factors'] = 'hip'`` computes the Doppler factor and the transport
+factors there (``libbhnerf_grf.so``, ``kgeo.emission_factors``).  The rendering itself goes through
 ``network.image_plane_checkpoint`` -> HIP forward kernel.
 """
 import os
 
 import numpy as np
 
-from . import constants, emission, kgeo, network, units
+from . import constants, emission, geodesics, kgeo, network, units
 
 _ROTATION_SIGN = {'cw': -1.0, 'ccw': 1.0}
 _STOKES = ('I', 'Q', 'U')
@@ -42,7 +44,11 @@ def image_plane_model(inc, spin, params, rot_angle=0.0, randomize_subpixel_rays=
 
     ``params``: ``num_alpha, num_beta, fov_M, z_width, rmin`` (a radius or ``'ISCO'``), ``Q_frac``, ``b_consts``
     (``arad, avert, ator``), ``Omega_dir`` (``'cw'|'ccw'``) and optionally ``Omega_frac`` (sub-Keplerian factor) and ``tracer``
-    (``'numpy'|'hip'``: where the geodesics are integrated, ``geodesics.image_plane_geos``'s ``backend``; default ``'numpy'``)."""
+    (``'numpy'|'hip'``: where the geodesics are integrated, ``geodesics.image_plane_geos``'s ``backend``; default ``'numpy'``) and
+    ``factors`` (``'numpy'|'hip'``: where the Doppler factor and J are computed, ``kgeo.emission_factors``'s ``backend``; default
+    ``'numpy'``)."""
+    factors = params.get('factors', 'numpy')
+    geodesics._check_backend(factors)
     fov = params['fov_M']
     rmin = float(constants.isco_pro(spin)) if params['rmin'] == 'ISCO' else params['rmin']
     rmax = fov / 2.0
@@ -50,21 +56,15 @@ def image_plane_model(inc, spin, params, rot_angle=0.0, randomize_subpixel_rays=
                                  alpha_range=[-fov / 2.0, fov / 2.0], beta_range=[-fov / 2.0, fov / 2.0],
                                  randomize_subpixel_rays=randomize_subpixel_rays, backend=params.get('tracer', 'numpy')).fillna(0.0)
 
-    # prograde / retrograde Keplerian rotation, Doppler boosting
+    # prograde / retrograde Keplerian rotation
     sqrt_M = np.sqrt(geos.M)
     with np.errstate(divide='ignore', invalid='ignore'):
         Omega = params.get('Omega_frac', 1.0) * _ROTATION_SIGN[params['Omega_dir']] * sqrt_M / (geos.r ** 1.5 + geos.spin * sqrt_M)
-    umu = kgeo.azimuthal_velocity_vector(geos, Omega)
-    g = kgeo.doppler_factor(geos, umu)
-
-    # fluid-frame magnetic field, normalised to unit mean magnitude over the recovery domain
-    b = kgeo.magnetic_field_fluid_frame(geos, umu, **params['b_consts'])
-    domain = (np.abs(geos.z) < params['z_width']) & (geos.r > rmin) & (geos.r < rmax)
-    b = b / np.sqrt((b[domain] ** 2).sum(axis=-1)).mean()
-
-    # polarised emission factors with parallel transport to the observer's screen
+    # Doppler boosting, fluid-frame magnetic field normalised to unit mean magnitude over the recovery domain, polarised emission
+    # factors with parallel transport to the observer's screen: on the host, or the same chain on the GPU
     with np.errstate(divide='ignore', invalid='ignore'):
-        J = kgeo.parallel_transport(geos, umu, g, b, Q_frac=params['Q_frac'], V_frac=0)
+        _, J = kgeo.emission_factors(geos, Omega, params['b_consts'], (params['z_width'], rmin, rmax), Q_frac=params['Q_frac'], V_frac=0,
+                                     backend=factors)
     J = emission.rotate_evpa(np.nan_to_num(J, nan=0.0), rot_angle)
     return geos, Omega, J
 
@@ -78,7 +78,8 @@ def get_raytracing_args(inc, spin, params, stokes=_STOKES, rot_angle=0.0, num_su
     for _ in range(num_subpixel_rays):
         geos, Omega, J = image_plane_model(inc, spin, params, rot_angle, jitter)
         t_injection = -float(geos.r_o + params['fov_M'] / 4.0)
-        out.append(network.raytracing_args(geos, Omega, t_injection, params['t_start_obs'] * units.hr, J[rows]))
+        out.append(network.raytracing_args(geos, Omega, t_injection, params['t_start_obs'] * units.hr, J[rows],
+                                           backend=params.get('factors', 'numpy')))
     return out
 
 

@@ -1,0 +1,296 @@
+// Per-point arithmetic of libbhnerf_grf.so: the GR pre-compute of bhnerf_amd/kgeo.py restated for one sample point of one ray.
+//
+// No HIP dependency: gr_factors.hip compiles it for the device (one lane per sample point), tools/gr_factors_host.cpp for the CPU
+// with a plain C++ compiler, so that the same arithmetic can be run under a sanitizer and compared with the NumPy code.
+// A restatement, not a new method: every function is named after the kgeo.py function it restates, every expression keeps NumPy's
+// order of operations (x ** 2 is x * x there, a reduction over a short last axis runs left to right, complex numbers multiply and
+// divide by NumPy's formulas, a real operand of a complex operation is (x, 0)), all arithmetic is float64 and floating-point
+// contraction is switched off.  Host and device then differ from NumPy by their maths library's sin / cos / atan2 / pow only.  Nothing
+// is clamped: sqrt of a negative number, 0 / 0 and x / 0 give the NaN or inf that NumPy gives.
+//
+// The 4-velocity is the azimuthal one of kgeo.azimuthal_velocity_vector, given as Omega per point; 4-vectors are (t, r, theta, phi).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define GRF_HD __host__ __device__ __forceinline__
+#else
+#define GRF_HD inline
+#endif
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+#define GRF_BLOCK 256        // sample points per workgroup; also the width of the reduction tree of the domain mean
+
+// The fields kgeo.py reads from the geodesic record.  (n, ngeo) row-major per point, (n) per ray.
+struct GrfGeos {
+    long long n;
+    int ngeo;
+    const double *r, *theta, *affine, *Delta, *Sigma, *Xi, *R, *Theta;
+    const double *lam, *alpha, *beta;
+    double a, M, E, sin_inc;         // a = spin (kgeo.py uses geos.spin where the metric wants a); sin(inc) from the host's maths library
+};
+
+struct GrfMetric { double tt, rr, thth, phph, tph; };
+struct GrfCplx { double re, im; };
+
+// ---- NumPy's elementwise helpers
+
+GRF_HD double grf_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : (x == 0.0 ? 0.0 : x)); }       // np.sign: NaN stays NaN
+GRF_HD double grf_clip0(double x) { return x < 0.0 ? 0.0 : x; }                                              // np.clip(x, 0, None): NaN stays NaN
+
+// arr ** p with a scalar p: NumPy takes x, x * x, sqrt(x), 1 / x and 1 for p = 1, 2, 0.5, -1 and 0, the maths library's pow otherwise
+GRF_HD double grf_pow(double x, double p) {
+    if (p == 1.0) return x;
+    if (p == 2.0) return x * x;
+    if (p == 0.5) return sqrt(x);
+    if (p == -1.0) return 1.0 / x;
+    if (p == 0.0) return 1.0;
+    return pow(x, p);
+}
+
+GRF_HD GrfCplx grf_cmul(GrfCplx x, GrfCplx y) { return GrfCplx{x.re * y.re - x.im * y.im, x.re * y.im + x.im * y.re}; }
+
+// NumPy's complex division (Smith's algorithm, the branches of its loop)
+GRF_HD GrfCplx grf_cdiv(GrfCplx x, GrfCplx y) {
+    const double yr = fabs(y.re), yi = fabs(y.im);
+    if (yr >= yi) {
+        if (yr == 0.0 && yi == 0.0) return GrfCplx{x.re / yr, x.im / yr};
+        const double rat = y.im / y.re, scl = 1.0 / (y.re + y.im * rat);
+        return GrfCplx{(x.re + x.im * rat) * scl, (x.im - x.re * rat) * scl};
+    }
+    const double rat = y.re / y.im, scl = 1.0 / (y.im + y.re * rat);
+    return GrfCplx{(x.re * rat + x.im) * scl, (x.im * rat - x.re) * scl};
+}
+
+// np.gradient(f, axis=-1)[k] with unit spacing: central (f[k+1] - f[k-1]) / 2.0, one-sided at both ends.  f points at the ray's row.
+GRF_HD double grf_gradient(const double *f, int k, int ngeo) {
+    if (k == 0) return f[1] - f[0];
+    if (k == ngeo - 1) return f[k] - f[k - 1];
+    return (f[k + 1] - f[k - 1]) / 2.0;
+}
+
+// ---- kgeo.py
+
+// wave_vector: k_mu = (-E, +-E sqrt(R) / Delta, +-E sqrt(Theta), E lam), signs from the direction of motion along the affine parameter
+GRF_HD void grf_wave_vector(const GrfGeos &g, long long ray, int k, double kmu[4]) {
+    const long long row = ray * g.ngeo, p = row + k;
+    const double ga = grf_gradient(g.affine + row, k, g.ngeo);
+    const double pm_r = grf_sign(grf_gradient(g.r + row, k, g.ngeo) / ga);
+    const double pm_th = grf_sign(grf_gradient(g.theta + row, k, g.ngeo) / ga);
+    kmu[0] = -g.E * 1.0;
+    kmu[1] = g.E * sqrt(grf_clip0(g.R[p])) * pm_r / g.Delta[p];
+    kmu[2] = g.E * sqrt(grf_clip0(g.Theta[p])) * pm_th;
+    kmu[3] = g.E * g.lam[ray] * 1.0;
+}
+
+GRF_HD GrfMetric grf_spacetime_metric(const GrfGeos &g, long long p, double sin_th) {
+    const double r = g.r[p], Sg = g.Sigma[p], s2 = sin_th * sin_th;
+    GrfMetric m;
+    m.tt = -(1.0 - 2.0 * g.M * r / Sg);
+    m.rr = Sg / g.Delta[p];
+    m.thth = Sg;
+    m.phph = g.Xi[p] * s2 / Sg;
+    m.tph = -2.0 * g.M * g.a * r * s2 / Sg;
+    return m;
+}
+
+GRF_HD GrfMetric grf_spacetime_inv_metric(const GrfGeos &g, long long p, double sin_th) {
+    const double r = g.r[p], Sg = g.Sigma[p], Dl = g.Delta[p], s2 = sin_th * sin_th;
+    GrfMetric m;
+    m.tt = -g.Xi[p] / (Dl * Sg);
+    m.rr = Dl / Sg;
+    m.thth = 1.0 / Sg;
+    m.phph = (Dl - g.a * g.a * s2) / (Dl * Sg * s2);
+    m.tph = -2.0 * g.M * g.a * r / (Dl * Sg);
+    return m;
+}
+
+GRF_HD void grf_raise_or_lower_indices(const GrfMetric &m, const double u[4], double out[4]) {
+    out[0] = m.tt * u[0] + m.tph * u[3];
+    out[1] = m.rr * u[1];
+    out[2] = m.thth * u[2];
+    out[3] = m.phph * u[3] + m.tph * u[0];
+}
+
+// azimuthal_velocity_vector: a superluminal Omega gives sqrt of a negative number, hence NaN
+GRF_HD void grf_azimuthal_velocity_vector(const GrfMetric &m, double Omega, double umu[4]) {
+    const double ut = 1.0 / sqrt(-(m.tt + 2.0 * Omega * m.tph + m.phph * (Omega * Omega)));
+    umu[0] = ut;
+    umu[1] = 0.0;
+    umu[2] = 0.0;
+    umu[3] = ut * Omega;
+}
+
+// doppler_factor: g = E / -(k_mu u^mu), the sum over mu from left to right; a NaN becomes `fillna` when `fill` is set
+GRF_HD double grf_doppler_factor(const GrfGeos &g, const double kmu[4], const double umu[4], double fillna, int fill) {
+    double s = 0.0;
+    for (int i = 0; i < 4; ++i) s += kmu[i] * umu[i];
+    const double d = g.E / -s;
+    return (fill && d != d) ? fillna : d;
+}
+
+// fluid_frame_tetrad: e[mu][a], component index then leg
+GRF_HD void grf_fluid_frame_tetrad(const GrfMetric &m, const double umu[4], const double u_mu[4], double Dl, double sin_th, double e[4][4]) {
+    double uu[4];
+    for (int i = 0; i < 4; ++i) uu[i] = u_mu[i] * umu[i];
+    const double tph = uu[0] + uu[3];
+    const double N_r = sqrt(-m.rr * tph * (1.0 + uu[2]));
+    const double N_th = sqrt(m.thth * (1.0 + uu[2]));
+    const double N_ph = sqrt(-tph * Dl * (sin_th * sin_th));
+    for (int i = 0; i < 4; ++i) e[i][0] = -umu[i];
+    e[0][1] = u_mu[1] * umu[0] / N_r;
+    e[1][1] = -tph / N_r;
+    e[2][1] = 0.0 / N_r;
+    e[3][1] = u_mu[1] * umu[3] / N_r;
+    e[0][2] = u_mu[2] * umu[0] / N_th;
+    e[1][2] = u_mu[2] * umu[1] / N_th;
+    e[2][2] = (1.0 + uu[2]) / N_th;
+    e[3][2] = u_mu[2] * umu[3] / N_th;
+    e[0][3] = u_mu[3] / N_ph;
+    e[1][3] = 0.0 / N_ph;
+    e[2][3] = 0.0 / N_ph;
+    e[3][3] = -u_mu[0] / N_ph;
+}
+
+// transform_coordinates(v, e, 'upper')[..., 1:]: out[a - 1] = sum_mu e[mu][a] v[mu], a = 1..3
+GRF_HD void grf_to_local_frame(const double e[4][4], const double v[4], double out[3]) {
+    for (int a = 1; a < 4; ++a) {
+        double s = 0.0;
+        for (int mu = 0; mu < 4; ++mu) s += e[mu][a] * v[mu];
+        out[a - 1] = s;
+    }
+}
+
+// magnetic_field_fluid_frame: the lab-frame field (radial / vertical / toroidal amplitudes) seen in the fluid frame
+GRF_HD void grf_magnetic_field_fluid_frame(const GrfMetric &m, const double u_mu[4], const double e[4][4], double sin_th, double cos_th,
+                                           double arad, double avert, double ator, double b[3]) {
+    const double Br = arad * sin_th + avert * cos_th;
+    const double Bth = avert * (-sin_th);
+    const double Bph = ator * 1.0;
+    double bup[4], b_mu[4];
+    bup[0] = Br * u_mu[1] + Bth * u_mu[2] + Bph * u_mu[3];
+    bup[1] = (Br + bup[0] * u_mu[1]) / u_mu[0];
+    bup[2] = (Bth + bup[0] * u_mu[2]) / u_mu[0];
+    bup[3] = (Bph + bup[0] * u_mu[3]) / u_mu[0];
+    grf_raise_or_lower_indices(m, bup, b_mu);
+    grf_to_local_frame(e, b_mu, b);
+}
+
+// What one point needs of its frame: metric, 4-velocity (both index positions), tetrad, sin / cos theta
+struct GrfFrame {
+    GrfMetric m;
+    double sin_th, cos_th, umu[4], u_mu[4], e[4][4];
+};
+
+GRF_HD void grf_frame(const GrfGeos &g, long long p, double Omega, GrfFrame &f) {
+    f.sin_th = sin(g.theta[p]);
+    f.cos_th = cos(g.theta[p]);
+    f.m = grf_spacetime_metric(g, p, f.sin_th);
+    grf_azimuthal_velocity_vector(f.m, Omega, f.umu);
+    grf_raise_or_lower_indices(f.m, f.umu, f.u_mu);
+    grf_fluid_frame_tetrad(f.m, f.umu, f.u_mu, g.Delta[p], f.sin_th, f.e);
+}
+
+// ---- the three per-point bodies of the library's kernels
+
+GRF_HD double grf_point_doppler(const GrfGeos &g, long long p, double Omega, double fillna, int fill) {
+    const long long ray = p / g.ngeo;
+    const int k = (int)(p - ray * g.ngeo);
+    double kmu[4], umu[4];
+    grf_wave_vector(g, ray, k, kmu);
+    const GrfMetric m = grf_spacetime_metric(g, p, sin(g.theta[p]));
+    grf_azimuthal_velocity_vector(m, Omega, umu);
+    return grf_doppler_factor(g, kmu, umu, fillna, fill);
+}
+
+GRF_HD void grf_point_fluid_field(const GrfGeos &g, long long p, double Omega, double arad, double avert, double ator, double b[3]) {
+    GrfFrame f;
+    grf_frame(g, p, Omega, f);
+    grf_magnetic_field_fluid_frame(f.m, f.u_mu, f.e, f.sin_th, f.cos_th, arad, avert, ator, b);
+}
+
+// The domain-mean selection of alma.image_plane_model: |z| < z_width, rmin < r < rmax with z = r cos(theta)
+GRF_HD bool grf_in_domain(const GrfGeos &g, long long p, double z_width, double rmin, double rmax) {
+    const double r = g.r[p];
+    return fabs(r * cos(g.theta[p])) < z_width && r > rmin && r < rmax;
+}
+
+GRF_HD double grf_field_magnitude(const double b[3]) {
+    double s = 0.0;
+    for (int i = 0; i < 3; ++i) s += b[i] * b[i];
+    return sqrt(s);
+}
+
+// _transport: local EVPA from k x b in the emitter frame, emissivity scalings, rotation to the observer's screen through the
+// Penrose-Walker constant.  gfac is the Doppler factor handed in, b the fluid-frame field (already divided by the caller's scalar).
+// J[0..2] = I, Q, U; J[3] = V when with_v.
+GRF_HD void grf_point_transport(const GrfGeos &g, long long p, double Omega, double gfac, const double b[3], double Q_frac, double V_frac,
+                                double spectral_index, int with_v, double J[4]) {
+    const long long ray = p / g.ngeo;
+    const int k = (int)(p - ray * g.ngeo);
+    GrfFrame f;
+    grf_frame(g, p, Omega, f);
+    double kmu[4], k_loc[3], f_loc[3], fg[4], kup[4];
+    grf_wave_vector(g, ray, k, kmu);
+    grf_to_local_frame(f.e, kmu, k_loc);
+    const double k_mag = grf_field_magnitude(k_loc);
+    f_loc[0] = (k_loc[1] * b[2] - k_loc[2] * b[1]) / k_mag;          // np.cross
+    f_loc[1] = (k_loc[2] * b[0] - k_loc[0] * b[2]) / k_mag;
+    f_loc[2] = (k_loc[0] * b[1] - k_loc[1] * b[0]) / k_mag;
+    for (int i = 0; i < 4; ++i) {                                    // transform_coordinates((0, f_loc), e, 'lower')
+        double s = 0.0;
+        s += f.e[i][0] * 0.0;
+        for (int j = 1; j < 4; ++j) s += f.e[i][j] * f_loc[j - 1];
+        fg[i] = s;
+    }
+    const double ft = fg[0], fr = fg[1], fth = fg[2], fph = fg[3];
+    const double b_mag = grf_field_magnitude(b);
+    const double sin_b = grf_field_magnitude(f_loc) / k_mag;
+    const double I = grf_pow(gfac, spectral_index) * grf_pow(b_mag, spectral_index + 1.0) * grf_pow(sin_b, spectral_index + 1.0);
+    const double Q = Q_frac * I;
+    const double r = g.r[p], a = g.a;
+    const GrfMetric im = grf_spacetime_inv_metric(g, p, f.sin_th);
+    grf_raise_or_lower_indices(im, kmu, kup);
+    const double s2 = f.sin_th * f.sin_th;
+    const double A = (kup[0] * fr - kup[1] * ft) + a * s2 * (kup[1] * fph - kup[3] * fr);
+    const double B = ((r * r + a * a) * (kup[3] * fth - kup[2] * fph) - a * (kup[0] * fth - kup[2] * ft)) * f.sin_th;
+    // kappa = (r - 1j a cos(theta)) (A - 1j B); 1j a is the complex scalar (0, a)
+    const GrfCplx ja = grf_cmul(GrfCplx{0.0, 1.0}, GrfCplx{a, 0.0});
+    const GrfCplx jac = grf_cmul(ja, GrfCplx{f.cos_th, 0.0});
+    const GrfCplx jB = grf_cmul(GrfCplx{0.0, 1.0}, GrfCplx{B, 0.0});
+    const GrfCplx kappa = grf_cmul(GrfCplx{r - jac.re, 0.0 - jac.im}, GrfCplx{A - jB.re, 0.0 - jB.im});
+    const double mu = -(g.alpha[ray] + a * g.sin_inc);
+    const GrfCplx jmu = grf_cmul(GrfCplx{0.0, 1.0}, GrfCplx{mu, 0.0});
+    const double beta = g.beta[ray];
+    const GrfCplx num = grf_cmul(GrfCplx{beta + jmu.re, 0.0 + jmu.im}, GrfCplx{kappa.re, -kappa.im});
+    const GrfCplx den = grf_cmul(GrfCplx{beta - jmu.re, 0.0 - jmu.im}, kappa);
+    const GrfCplx q = grf_cdiv(num, den);
+    const double chi2 = atan2(q.im, q.re);                           // np.angle
+    J[0] = I;
+    J[1] = cos(chi2) * Q;
+    J[2] = sin(chi2) * Q;
+    if (with_v) {
+        const double cot_b = sqrt(1.0 - sin_b * sin_b) / sin_b;
+        J[3] = V_frac * grf_pow(gfac, -spectral_index - 0.5) * grf_pow(b_mag, spectral_index + 1.5) * grf_pow(sin_b, spectral_index + 1.5) * cot_b;
+    }
+}
+
+// ---- the domain mean: a fixed-order two-stage reduction
+
+// In-place tree sum of GRF_BLOCK values, the order of the device's LDS reduction (v[t] += v[t + s] for s = 128, 64, .. 1): v[0]
+inline double grf_tree_sum_host(double *v) {
+    for (int s = GRF_BLOCK / 2; s > 0; s >>= 1)
+        for (int t = 0; t < s; ++t) v[t] += v[t + s];
+    return v[0];
+}
+
+// Why the arguments are outside the contract, or NULL.  Host only.
+inline const char *grf_geos_error(const GrfGeos &g) {
+    if (!(g.r && g.theta && g.affine && g.Delta && g.Sigma && g.Xi && g.R && g.Theta && g.lam && g.alpha && g.beta)) return "null field in geos";
+    if (g.n < 1) return "bad ray count n";
+    if (g.ngeo < 2) return "ngeo must be at least 2 (the gradient along the ray)";
+    return nullptr;
+}

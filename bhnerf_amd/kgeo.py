@@ -14,6 +14,10 @@ unpinned against the reference (its functions need xarray and the external ``kge
 instead by the invariants they must satisfy -- ``u.u = -1``, ``k.k = 0``, orthonormal tetrads, the special-
 relativistic Doppler factor far from the hole, conservation of the Penrose-Walker constant along a geodesic
 (``tests/test_geodesics_cpu.py``).
+
+``emission_factors`` is the chain ``alma.image_plane_model`` runs after the geodesics are traced (4-velocity -> Doppler factor ->
+fluid-frame field -> its mean over the recovery domain -> parallel transport) as one function, on the host (``backend='numpy'``:
+the functions above, composed) or on the GPU (``backend='hip'``: ``libbhnerf_grf.so``, include/bhnerf_grf.h).
 """
 import numpy as np
 import torch
@@ -275,3 +279,96 @@ def parallel_transport_zamo(geos, beta_v, chi, g, b, Q_frac=0.2, spectral_index=
     """The same in the boosted ZAMO frame, ``J = [I, Q, U]`` (kgeo.py:521-593)."""
     J, _ = _transport(geos, zamo_frame_tetrad(geos, beta_v, chi), g, b, Q_frac, 0.0, spectral_index, False)
     return J
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Doppler factor and polarised transport factors of one hypothesis, on the host or on the GPU
+# ---------------------------------------------------------------------------------------------------------------
+_GRF_POINT_FIELDS = ('r', 'theta', 'affine', 'Delta', 'Sigma', 'Xi', 'R', 'Theta')
+_GRF_RAY_FIELDS = ('lam', 'alpha', 'beta')
+
+
+def _no_fill(fillna):
+    return (isinstance(fillna, bool) and fillna is False) or fillna is None
+
+
+def _emission_factors_numpy(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna):
+    umu = azimuthal_velocity_vector(geos, Omega)
+    g = doppler_factor(geos, umu, fillna)
+    if b_consts is None:
+        return g, None
+    b = magnetic_field_fluid_frame(geos, umu, **b_consts)
+    if domain is not None:
+        z_width, rmin, rmax = domain
+        r = _f(geos, 'r')
+        sel = (np.abs(r * np.cos(_f(geos, 'theta'))) < z_width) & (r > rmin) & (r < rmax)          # |z| of the record
+        b = b / np.sqrt((b[sel] ** 2).sum(axis=-1)).mean()
+    with np.errstate(divide='ignore', invalid='ignore'):
+        J = parallel_transport(geos, umu, g, b, Q_frac=Q_frac, V_frac=V_frac, spectral_index=spectral_index)
+    return g, J
+
+
+def _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device):
+    """The calls of include/bhnerf_grf.h on one record: fields uploaded once, g (and J) downloaded."""
+    import ctypes as C
+    r = _f(geos, 'r')
+    if r.ndim < 1 or r.shape[-1] < 2:            # np.gradient's own error, before anything touches the device
+        raise ValueError('Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.')
+    if b_consts is not None and (Q_frac > 1.0 or Q_frac < 0.0):
+        raise AttributeError('Q_frac should be in [0,1]')
+    lib = _hip.grf_lib()
+    if not torch.cuda.is_available():
+        raise _hip.HipError("backend='hip' needs a HIP device (there is no CPU fallback; backend='numpy' computes the factors on the host)")
+    dev = torch.device('cuda' if device is None else device)
+    shape, ngeo = r.shape, r.shape[-1]
+    n = r.size // ngeo
+    with torch.cuda.device(dev):
+        def up(v, shp):
+            v = np.asarray(v, dtype=np.float64)
+            return torch.as_tensor(np.ascontiguousarray(v if v.shape == shp else np.broadcast_to(v, shp).copy()), device=dev)
+
+        fields = {k: up(_f(geos, k), shape) for k in _GRF_POINT_FIELDS}
+        fields.update({k: up(_f(geos, k), shape[:-1]) for k in _GRF_RAY_FIELDS})
+        Om = up(Omega, shape)
+        rec = _hip.bhn_grf_geos(n, ngeo, *[fields[k].data_ptr() for k in _GRF_POINT_FIELDS + _GRF_RAY_FIELDS],
+                                float(_f(geos, 'spin')), float(_f(geos, 'M')), float(_f(geos, 'E')), float(_f(geos, 'inc')))
+        stream = _hip.stream_ptr(dev)
+        g = torch.empty(shape, dtype=torch.float64, device=dev)
+        no_fill = _no_fill(fillna)
+        _hip.grf_check(lib.bhn_grf_doppler(C.byref(rec), _hip.ptr(Om), 0.0 if no_fill else float(fillna), 0 if no_fill else 1, _hip.ptr(g), stream))
+        if b_consts is None:
+            return g.cpu().numpy(), None
+        b = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+        _hip.grf_check(lib.bhn_grf_fluid_field(C.byref(rec), _hip.ptr(Om), float(b_consts['arad']), float(b_consts['avert']),
+                                               float(b_consts['ator']), _hip.ptr(b), stream))
+        mean = None
+        if domain is not None:
+            z_width, rmin, rmax = (float(v) for v in domain)
+            nbytes = int(lib.bhn_grf_ws_bytes(n, ngeo))
+            ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+            mean = torch.empty((1,), dtype=torch.float64, device=dev)
+            _hip.grf_check(lib.bhn_grf_domain_mean(C.byref(rec), _hip.ptr(b), z_width, rmin, rmax, _hip.ptr(mean), _hip.ptr(ws), nbytes, stream))
+        S = 4 if V_frac != 0 else 3
+        J = torch.empty((S,) + shape, dtype=torch.float64, device=dev)
+        _hip.grf_check(lib.bhn_grf_transport(C.byref(rec), _hip.ptr(Om), _hip.ptr(g), _hip.ptr(b), _hip.ptr(mean), float(Q_frac), float(V_frac),
+                                             float(spectral_index), _hip.ptr(J), stream))
+        return g.cpu().numpy(), J.cpu().numpy()
+
+
+def emission_factors(geos, Omega, b_consts=None, domain=None, Q_frac=0.2, V_frac=0.01, spectral_index=1, fillna=0.0, backend='numpy',
+                     device=None):
+    """Doppler factor ``g`` and polarised transport factors ``J`` of matter on circular orbits with angular velocity ``Omega``:
+    ``azimuthal_velocity_vector -> doppler_factor -> magnetic_field_fluid_frame -> (domain mean) -> parallel_transport``, what
+    ``alma.image_plane_model`` computes after the geodesics are traced.  Returns ``(g, J)``; ``J`` is None when ``b_consts``
+    (``arad, avert, ator``) is None.  ``domain=(z_width, rmin, rmax)`` divides the field by its mean magnitude over the points with
+    ``|z| < z_width, rmin < r < rmax``; None leaves it as it is.
+
+    ``backend='numpy'`` (the default) composes the functions above on the host.  ``'hip'`` uploads the fields of the record once and
+    makes the calls of ``include/bhnerf_grf.h`` (``libbhnerf_grf.so``, csrc/gr_factors.hip: the same expressions, one GPU lane per
+    sample point) on ``device`` (a torch device, default the current one); float64 NumPy arrays of the same shapes come back.
+    There is no CPU fallback: ``'hip'`` without a device raises ``HipError``."""
+    from .geodesics import _check_backend
+    _check_backend(backend)
+    if backend == 'hip':
+        return _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device)
+    return _emission_factors_numpy(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna)

@@ -643,14 +643,17 @@ def image_plane_checkpoint(raytracing_args, checkpoint_dir, t, rmin=0.0, rmax=np
     return image_plane
 
 
-def raytracing_args(geos, Omega, t_injection, t_start_obs, J=1.0):
+def raytracing_args(geos, Omega, t_injection, t_start_obs, J=1.0, backend='numpy', device=None):
     """Ordered dict of the non-optimised ray-tracing arguments (network.py:850-894).
 
     ``geos`` is any mapping/object with x, y, z, dtau, Sigma, t.  When it is a traced geodesic record
     (``kgeo.image_plane_geos``: r, theta, affine, potentials, constants of motion) the Doppler factor is derived from
     the azimuthal 4-velocity of ``Omega`` as the reference does (network.py:875-876); a pre-computed table may carry
-    its own ``g`` instead."""
+    its own ``g`` instead.  ``backend`` (``'numpy'|'hip'``) is where that Doppler factor is computed
+    (``kgeo.emission_factors``; ``device``: a torch device for ``'hip'``, default the current one)."""
     from . import kgeo
+    from .geodesics import _check_backend
+    _check_backend(backend)
     get = (lambda k: geos[k]) if isinstance(geos, dict) else (lambda k: getattr(geos, k))
 
     def has(k):
@@ -661,7 +664,10 @@ def raytracing_args(geos, Omega, t_injection, t_start_obs, J=1.0):
             return False
 
     if all(has(k) for k in ('r', 'theta', 'affine', 'R', 'Theta', 'Delta', 'Xi', 'lam', 'E', 'M', 'spin')):
-        gfac = kgeo.doppler_factor(geos, kgeo.azimuthal_velocity_vector(geos, Omega))
+        if backend == 'hip':
+            gfac = kgeo.emission_factors(geos, Omega, backend='hip', device=device)[0]
+        else:
+            gfac = kgeo.doppler_factor(geos, kgeo.azimuthal_velocity_vector(geos, Omega))
     elif has('g'):
         gfac = get('g')
     else:

@@ -9,7 +9,7 @@ The ALMA data file does not ship with either repository: when `preprocess.data_p
 orbiting Gaussian hotspot rendered through the same geometry at 30 deg, plus a constant shadow polarisation, Faraday
 rotation and noise) is written there first.
 
-    python examples/fit_alma_lp.py 20 30 40 [--config examples/fit_alma_lp.yaml] [--seeds 4] [--tracer hip]
+    python examples/fit_alma_lp.py 20 30 40 [--config examples/fit_alma_lp.yaml] [--seeds 4] [--tracer hip] [--factors hip]
 """
 import argparse
 import os
@@ -56,12 +56,16 @@ def main():
     ap.add_argument('--seeds', type=int, nargs='+')
     ap.add_argument('--config', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), 'fit_alma_lp.yaml'))
     ap.add_argument('--tracer', choices=['numpy', 'hip'], help="where the geodesics are integrated (default: the config's model.tracer, else numpy)")
+    ap.add_argument('--factors', choices=['numpy', 'hip'],
+                    help="where the Doppler factor and the transport factors J are computed (default: the config's model.factors, else numpy)")
     args = ap.parse_args()
     with open(args.config) as f:
         config = yaml.safe_load(f)
     pre, model, opt_cfg = config['preprocess'], config['model'], config['optimization']
     if args.tracer:
         model['tracer'] = args.tracer
+    if args.factors:
+        model['factors'] = args.factors
     if not os.path.exists(pre['data_path']):
         synthetic_flare(pre['data_path'], model, pre)
 

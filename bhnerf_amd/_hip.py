@@ -129,10 +129,14 @@ GRF_SIGNATURES = {
     'bhn_grf_transport': (C.c_int, [_GG, _P, _P, _P, _P, _D, _D, _D, _P, _P]),
 }
 
-_lib = None
-_kerr_lib = None
-_eht_lib = None
-_grf_lib = None
+# library name -> (path, signature table, last-error symbol, what bhn_version() must return): the four libraries `make` builds
+LIBRARIES = {
+    'libbhnerf_hip': (LIB_PATH, SIGNATURES, 'bhn_last_error', ABI_VERSION),
+    'libbhnerf_kerr': (KERR_LIB_PATH, KERR_SIGNATURES, 'bhn_kerr_last_error', None),
+    'libbhnerf_eht': (EHT_LIB_PATH, EHT_SIGNATURES, 'bhn_eht_last_error', None),
+    'libbhnerf_grf': (GRF_LIB_PATH, GRF_SIGNATURES, 'bhn_grf_last_error', None),
+}
+_loaded = {}                 # path -> handle
 
 
 def build(verbose=False):
@@ -142,108 +146,78 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building libbhnerf_hip.so / libbhnerf_kerr.so / libbhnerf_eht.so / libbhnerf_grf.so failed (make -C %s)' % CSRC)
+        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in LIBRARIES), CSRC))
     return LIB_PATH
 
 
-def lib():
-    """The loaded library; raises HipError (never falls back) when it is missing."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
+def load(path, signatures, abi_version=None):
+    """The library at `path` with the restype / argtypes of `signatures` set, loaded once per path; raises HipError (never falls
+    back) when it is missing, does not load or lacks a symbol.  abi_version: what its bhn_version() must return."""
+    if path not in _loaded:
+        if not os.path.exists(path):
             raise HipError('%s not found: run `python -c "import __graft_entry__ as g; g.build()"` '
-                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % LIB_PATH)
+                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % path)
         try:
-            handle = C.CDLL(LIB_PATH)
-        except OSError as exc:
-            raise HipError('cannot load %s: %s' % (LIB_PATH, exc))
-        try:
-            handle.bhn_version.restype = C.c_int
-            have = int(handle.bhn_version())
-        except AttributeError:
-            have = -1
-        if have != ABI_VERSION:      # a stale build would fail later, at a symbol lookup or as "bad mode"
-            raise HipError('%s implements ABI version %d, this package binds version %d: rebuild it (make -C bhnerf_amd/csrc)'
-                           % (LIB_PATH, have, ABI_VERSION))
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
+            handle = C.CDLL(path)
+            if abi_version is not None:      # a stale build would fail later, at a symbol lookup or as "bad mode"
+                version = getattr(handle, 'bhn_version', None)
+                have = int(version()) if version is not None else -1
+                if have != abi_version:
+                    raise HipError('%s implements ABI version %d, this package binds version %d: rebuild it (make -C bhnerf_amd/csrc)'
+                                   % (path, have, abi_version))
+            for name, (res, args) in signatures.items():
+                fn = getattr(handle, name)
+                fn.restype, fn.argtypes = res, args
+        except (OSError, AttributeError) as exc:
+            raise HipError('cannot load %s: %s (rebuild it: make -C bhnerf_amd/csrc)' % (path, exc))
+        _loaded[path] = handle
+    return _loaded[path]
+
+
+def _lib(library):
+    path, signatures, _, abi_version = LIBRARIES[library]
+    return load(path, signatures, abi_version)
+
+
+def _check(library, rc):
+    if rc != 0:
+        raise HipError('%s: %s (code %d)' % (library, getattr(_lib(library), LIBRARIES[library][2])().decode(), rc))
+
+
+def lib():
+    """The loaded library; raises HipError (never falls back) when it is missing or implements another ABI version."""
+    return _lib('libbhnerf_hip')
 
 
 def kerr_lib():
-    """The loaded ray-tracer library; raises HipError (never falls back) when it is missing."""
-    global _kerr_lib
-    if _kerr_lib is None:
-        if not os.path.exists(KERR_LIB_PATH):
-            raise HipError('%s not found: run `python -c "import __graft_entry__ as g; g.build()"` '
-                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % KERR_LIB_PATH)
-        try:
-            handle = C.CDLL(KERR_LIB_PATH)
-            for name, (res, args) in KERR_SIGNATURES.items():
-                fn = getattr(handle, name)
-                fn.restype, fn.argtypes = res, args
-        except (OSError, AttributeError) as exc:
-            raise HipError('cannot load %s: %s (rebuild it: make -C bhnerf_amd/csrc)' % (KERR_LIB_PATH, exc))
-        _kerr_lib = handle
-    return _kerr_lib
-
-
-def kerr_check(rc):
-    if rc != 0:
-        raise HipError('libbhnerf_kerr: %s (code %d)' % (kerr_lib().bhn_kerr_last_error().decode(), rc))
+    """The loaded ray-tracer library."""
+    return _lib('libbhnerf_kerr')
 
 
 def eht_lib():
-    """The loaded (u, v) EHT library; raises HipError (never falls back) when it is missing."""
-    global _eht_lib
-    if _eht_lib is None:
-        if not os.path.exists(EHT_LIB_PATH):
-            raise HipError('%s not found: run `python -c "import __graft_entry__ as g; g.build()"` '
-                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % EHT_LIB_PATH)
-        try:
-            handle = C.CDLL(EHT_LIB_PATH)
-            for name, (res, args) in EHT_SIGNATURES.items():
-                fn = getattr(handle, name)
-                fn.restype, fn.argtypes = res, args
-        except (OSError, AttributeError) as exc:
-            raise HipError('cannot load %s: %s (rebuild it: make -C bhnerf_amd/csrc)' % (EHT_LIB_PATH, exc))
-        _eht_lib = handle
-    return _eht_lib
-
-
-def eht_check(rc):
-    if rc != 0:
-        raise HipError('libbhnerf_eht: %s (code %d)' % (eht_lib().bhn_eht_last_error().decode(), rc))
+    """The loaded (u, v) EHT library."""
+    return _lib('libbhnerf_eht')
 
 
 def grf_lib():
-    """The loaded (g, J) library; raises HipError (never falls back) when it is missing."""
-    global _grf_lib
-    if _grf_lib is None:
-        if not os.path.exists(GRF_LIB_PATH):
-            raise HipError('%s not found: run `python -c "import __graft_entry__ as g; g.build()"` '
-                           '(or make -C bhnerf_amd/csrc). There is no CPU fallback.' % GRF_LIB_PATH)
-        try:
-            handle = C.CDLL(GRF_LIB_PATH)
-            for name, (res, args) in GRF_SIGNATURES.items():
-                fn = getattr(handle, name)
-                fn.restype, fn.argtypes = res, args
-        except (OSError, AttributeError) as exc:
-            raise HipError('cannot load %s: %s (rebuild it: make -C bhnerf_amd/csrc)' % (GRF_LIB_PATH, exc))
-        _grf_lib = handle
-    return _grf_lib
-
-
-def grf_check(rc):
-    if rc != 0:
-        raise HipError('libbhnerf_grf: %s (code %d)' % (grf_lib().bhn_grf_last_error().decode(), rc))
+    """The loaded (g, J) library."""
+    return _lib('libbhnerf_grf')
 
 
 def check(rc):
-    if rc != 0:
-        raise HipError('libbhnerf_hip: %s (code %d)' % (lib().bhn_last_error().decode(), rc))
+    _check('libbhnerf_hip', rc)
+
+
+def kerr_check(rc):
+    _check('libbhnerf_kerr', rc)
+
+
+def eht_check(rc):
+    _check('libbhnerf_eht', rc)
+
+
+def grf_check(rc):
+    _check('libbhnerf_grf', rc)
 
 
 def stream_ptr(device=None):

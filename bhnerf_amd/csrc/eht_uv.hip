@@ -18,34 +18,12 @@
 // a call holds.  The image is read nvis / EHT_KB times in the forward pass (from L2 after the first), the tables are the only
 // other traffic: nothing of size nvis x H x W is ever read or written.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/bhnerf_eht.h"
 #include "eht_uv.h"
+#include "side_lib.h"
 
-static thread_local char g_eht_err[512] = "";
-
-static int eht_fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_eht_err, sizeof(g_eht_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-extern "C" const char *bhn_eht_last_error(void) { return g_eht_err; }
-
-#define EHT_CHECK_ARG(cond, ...) \
-    do {                         \
-        if (!(cond)) return eht_fail(BHN_EINVAL, __VA_ARGS__); \
-    } while (0)
-
-#define EHT_LAUNCHED(name)                                                                                        \
-    do {                                                                                                          \
-        const hipError_t e_ = hipGetLastError();                                                                  \
-        if (e_ != hipSuccess) return eht_fail(BHN_EHIP, "launch of " name " failed: %s", hipGetErrorString(e_)); \
-    } while (0)
+extern "C" const char *bhn_eht_last_error(void) { return side_last_error(); }
 
 __global__ __launch_bounds__(256) void eht_twiddle_kernel(const double *__restrict__ uv, EhtPlan p, int B, double psize_x, double psize_y,
                                                           EhtC *__restrict__ Eu, EhtC *__restrict__ Ev) {
@@ -196,13 +174,13 @@ extern "C" size_t bhn_eht_ws_bytes(int32_t N, int32_t nvis, int32_t ncp, int32_t
 // the argument checks and the plan of both entry points; nothing is launched when this fails
 static int eht_prepare(const float *images, const double *uv, int32_t N, int32_t Sx, int32_t nvis, int32_t ncp, int32_t H, int32_t W,
                        double psize_x, double psize_y, void *ws, size_t ws_bytes, EhtPlan *p) {
-    EHT_CHECK_ARG(images && uv && ws, "null pointer");
+    BHN_CHECK_ARG(images && uv && ws, "null pointer");
     const char *why = eht_sizes_error(N, Sx, nvis, ncp, H, W, psize_x, psize_y);
-    EHT_CHECK_ARG(!why, "%s (N %d, Sx %d, nvis %d, ncp %d, H %d, W %d, pixel %g x %g rad)", why, N, Sx, nvis, ncp, H, W, psize_x, psize_y);
-    EHT_CHECK_ARG(eht_make_plan(N, nvis, ncp, H, W, p), "sizes too large for one call (N %d, nvis %d, ncp %d, H %d, W %d)", N, nvis, ncp, H, W);
-    EHT_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 7) == 0 && (reinterpret_cast<uintptr_t>(uv) & 7) == 0, "ws and uv must be 8-byte aligned");
+    BHN_CHECK_ARG(!why, "%s (N %d, Sx %d, nvis %d, ncp %d, H %d, W %d, pixel %g x %g rad)", why, N, Sx, nvis, ncp, H, W, psize_x, psize_y);
+    BHN_CHECK_ARG(eht_make_plan(N, nvis, ncp, H, W, p), "sizes too large for one call (N %d, nvis %d, ncp %d, H %d, W %d)", N, nvis, ncp, H, W);
+    BHN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 7) == 0 && (reinterpret_cast<uintptr_t>(uv) & 7) == 0, "ws and uv must be 8-byte aligned");
     if (ws_bytes < p->bytes)
-        return eht_fail(BHN_EWORKSPACE, "workspace of %zu bytes, bhn_eht_ws_bytes(%d, %d, %d, %d, %d) = %zu", ws_bytes, N, nvis, ncp, H, W, p->bytes);
+        return side_fail(BHN_EWORKSPACE, "workspace of %zu bytes, bhn_eht_ws_bytes(%d, %d, %d, %d, %d) = %zu", ws_bytes, N, nvis, ncp, H, W, p->bytes);
     return BHN_OK;
 }
 
@@ -214,21 +192,20 @@ static int eht_forward(const float *images, const double *uv, const EhtPlan &p, 
     const int B = p.N / Sx;
     const long long tw = (long long)B * p.nvis * (p.W + p.H);
     hipLaunchKernelGGL(eht_twiddle_kernel, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, st, uv, p, B, psize_x, psize_y, Eu, Ev);
-    EHT_LAUNCHED("eht_twiddle_kernel");
+    if (int rc = side_launched("eht_twiddle_kernel")) return rc;
     hipLaunchKernelGGL(eht_fwd_kernel, dim3((unsigned)p.kblocks, (unsigned)p.RS, (unsigned)p.N), dim3((unsigned)p.block), 0, st, images, Eu, Ev, p,
                        Sx, part);
-    EHT_LAUNCHED("eht_fwd_kernel");
+    if (int rc = side_launched("eht_fwd_kernel")) return rc;
     if (!vis) return BHN_OK;                               // (bhn_eht_chi2_uv combines in its loss stage)
     hipLaunchKernelGGL(eht_combine_kernel, dim3((unsigned)((p.N * p.nvis + 255) / 256)), dim3(256), 0, st, part, p, vis);
-    EHT_LAUNCHED("eht_combine_kernel");
-    return BHN_OK;
+    return side_launched("eht_combine_kernel");
 }
 
 extern "C" int bhn_eht_vis(const float *images, const double *uv, int32_t N, int32_t Sx, int32_t nvis, int32_t H, int32_t W, double psize_x,
                            double psize_y, float *vis_out, void *ws, size_t ws_bytes, void *stream) {
     EhtPlan p;
-    EHT_CHECK_ARG(vis_out, "null pointer");
-    EHT_CHECK_ARG((reinterpret_cast<uintptr_t>(vis_out) & 7) == 0, "vis_out must be 8-byte aligned");
+    BHN_CHECK_ARG(vis_out, "null pointer");
+    BHN_CHECK_ARG((reinterpret_cast<uintptr_t>(vis_out) & 7) == 0, "vis_out must be 8-byte aligned");
     const int rc = eht_prepare(images, uv, N, Sx, nvis, 0, H, W, psize_x, psize_y, ws, ws_bytes, &p);
     if (rc != BHN_OK) return rc;
     return eht_forward(images, uv, p, Sx, psize_x, psize_y, static_cast<char *>(ws), reinterpret_cast<EhtC *>(vis_out), (hipStream_t)stream);
@@ -239,10 +216,10 @@ extern "C" int bhn_eht_chi2_uv(const float *images, const double *uv, int32_t N,
                                const int32_t *tri, const int8_t *tri_sign, int32_t ncp, float *loss, float *dimages, void *ws,
                                size_t ws_bytes, void *stream) {
     EhtPlan p;
-    EHT_CHECK_ARG(target && sigma && loss, "null pointer");
-    EHT_CHECK_ARG(dtype >= 0 && dtype <= 2, "eht dtype (%d) not supported", dtype);
-    EHT_CHECK_ARG(ncp <= 0 || (tri && tri_sign), "ncp = %d closure triangles with a NULL table", ncp);
-    EHT_CHECK_ARG(dtype != EHT_DTYPE_CPHASE || ncp >= 1, "closure phases need a triangle table (ncp = %d)", ncp);
+    BHN_CHECK_ARG(target && sigma && loss, "null pointer");
+    BHN_CHECK_ARG(dtype >= 0 && dtype <= 2, "eht dtype (%d) not supported", dtype);
+    BHN_CHECK_ARG(ncp <= 0 || (tri && tri_sign), "ncp = %d closure triangles with a NULL table", ncp);
+    BHN_CHECK_ARG(dtype != EHT_DTYPE_CPHASE || ncp >= 1, "closure phases need a triangle table (ncp = %d)", ncp);
     const int rc = eht_prepare(images, uv, N, Sx, nvis, ncp, H, W, psize_x, psize_y, ws, ws_bytes, &p);
     if (rc != BHN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -253,17 +230,16 @@ extern "C" int bhn_eht_chi2_uv(const float *images, const double *uv, int32_t N,
     if (rf != BHN_OK) return rf;
     hipLaunchKernelGGL(eht_loss_kernel, dim3((unsigned)N), dim3(256), 0, st, reinterpret_cast<const EhtC *>(w + p.off_part), p, vis, tri, tri_sign,
                        target, sigma, scale, dtype, dphi, loss_part, dimages ? 1 : 0);
-    EHT_LAUNCHED("eht_loss_kernel");
+    if (int rc = side_launched("eht_loss_kernel")) return rc;
     hipLaunchKernelGGL(eht_loss_sum_kernel, dim3(1), dim3(256), 0, st, loss, loss_part, (int)N);
-    EHT_LAUNCHED("eht_loss_sum_kernel");
+    if (int rc = side_launched("eht_loss_sum_kernel")) return rc;
     if (!dimages) return BHN_OK;
     if (dtype == EHT_DTYPE_CPHASE) {
         hipLaunchKernelGGL(eht_gather_kernel, dim3((unsigned)((N * nvis + 3) / 4)), dim3(256), 0, st, vis, p, tri, tri_sign, dphi);
-        EHT_LAUNCHED("eht_gather_kernel");
+        if (int rc = side_launched("eht_gather_kernel")) return rc;
     }
     hipLaunchKernelGGL(eht_adjoint_kernel, dim3((unsigned)((W + p.block - 1) / p.block), (unsigned)((H + EHT_ADJ_ROWS - 1) / EHT_ADJ_ROWS), (unsigned)N),
                        dim3((unsigned)p.block), 0, st, vis, reinterpret_cast<const EhtC *>(w + p.off_eu),
                        reinterpret_cast<const EhtC *>(w + p.off_ev), p, Sx, dimages);
-    EHT_LAUNCHED("eht_adjoint_kernel");
-    return BHN_OK;
+    return side_launched("eht_adjoint_kernel");
 }

@@ -8,28 +8,12 @@
 //
 // Built into a library of its own (include/bhnerf_grf.h): the ABIs of the other three libraries are not touched.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/bhnerf_grf.h"
 #include "gr_factors.h"
+#include "side_lib.h"
 
-static thread_local char g_grf_err[512] = "";
-
-static int grf_fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_grf_err, sizeof(g_grf_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-extern "C" const char *bhn_grf_last_error(void) { return g_grf_err; }
-
-#define BHN_CHECK_ARG(cond, ...) \
-    do {                         \
-        if (!(cond)) return grf_fail(BHN_EINVAL, __VA_ARGS__); \
-    } while (0)
+extern "C" const char *bhn_grf_last_error(void) { return side_last_error(); }
 
 __global__ __launch_bounds__(GRF_BLOCK) void grf_doppler_kernel(GrfGeos g, const double *__restrict__ Omega, double fillna, int fill,
                                                                 double *__restrict__ out, long long total) {
@@ -115,8 +99,7 @@ __global__ __launch_bounds__(GRF_BLOCK) void grf_transport_kernel(GrfGeos g, con
 static long long grf_blocks(int64_t n, int32_t ngeo) {
     if (n < 1 || ngeo < 2) return 0;
     if (n > ((int64_t)1 << 40) / ngeo) return 0;                  // 4 n ngeo doubles of J stay far inside 2^63 bytes
-    const long long blocks = ((long long)n * ngeo + GRF_BLOCK - 1) / GRF_BLOCK;
-    return blocks <= 0x7fffffffLL ? blocks : 0;
+    return side_blocks((long long)n * ngeo, GRF_BLOCK);
 }
 
 // Checks the record, which every entry point takes, and fills the kernels' view of it; the message is set on failure
@@ -137,12 +120,6 @@ static int grf_prepare(const bhn_grf_geos *geos, GrfGeos *out, long long *blocks
     return BHN_OK;
 }
 
-static int grf_launched(const char *name) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return grf_fail(BHN_EHIP, "launch of %s failed: %s", name, hipGetErrorString(e));
-    return BHN_OK;
-}
-
 extern "C" size_t bhn_grf_ws_bytes(int64_t n, int32_t ngeo) { return (size_t)grf_blocks(n, ngeo) * 2 * sizeof(double); }
 
 extern "C" int bhn_grf_doppler(const bhn_grf_geos *geos, const double *Omega, double fillna, int32_t fill, double *g, void *stream) {
@@ -153,7 +130,7 @@ extern "C" int bhn_grf_doppler(const bhn_grf_geos *geos, const double *Omega, do
     BHN_CHECK_ARG(g, "null output g");
     hipLaunchKernelGGL(grf_doppler_kernel, dim3((unsigned)blocks), dim3(GRF_BLOCK), 0, (hipStream_t)stream, k, Omega, fillna, fill != 0, g,
                        k.n * k.ngeo);
-    return grf_launched("grf_doppler_kernel");
+    return side_launched("grf_doppler_kernel");
 }
 
 extern "C" int bhn_grf_fluid_field(const bhn_grf_geos *geos, const double *Omega, double arad, double avert, double ator, double *b,
@@ -165,7 +142,7 @@ extern "C" int bhn_grf_fluid_field(const bhn_grf_geos *geos, const double *Omega
     BHN_CHECK_ARG(b, "null output b");
     hipLaunchKernelGGL(grf_fluid_field_kernel, dim3((unsigned)blocks), dim3(GRF_BLOCK), 0, (hipStream_t)stream, k, Omega, arad, avert, ator, b,
                        k.n * k.ngeo);
-    return grf_launched("grf_fluid_field_kernel");
+    return side_launched("grf_fluid_field_kernel");
 }
 
 extern "C" int bhn_grf_domain_mean(const bhn_grf_geos *geos, const double *b, double z_width, double rmin, double rmax, double *mean,
@@ -176,13 +153,13 @@ extern "C" int bhn_grf_domain_mean(const bhn_grf_geos *geos, const double *b, do
     BHN_CHECK_ARG(b && mean, "null b or mean");
     BHN_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0, "null or misaligned workspace");
     const size_t need = (size_t)blocks * 2 * sizeof(double);
-    if (ws_bytes < need) return grf_fail(BHN_EWORKSPACE, "workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if (ws_bytes < need) return side_fail(BHN_EWORKSPACE, "workspace of %zu bytes, %zu needed", ws_bytes, need);
     double *partial = (double *)ws, *count = partial + blocks;
     hipLaunchKernelGGL(grf_domain_partial_kernel, dim3((unsigned)blocks), dim3(GRF_BLOCK), 0, (hipStream_t)stream, k, b, z_width, rmin, rmax,
                        partial, count, k.n * k.ngeo);
-    if (int rc = grf_launched("grf_domain_partial_kernel")) return rc;
+    if (int rc = side_launched("grf_domain_partial_kernel")) return rc;
     hipLaunchKernelGGL(grf_domain_final_kernel, dim3(1), dim3(GRF_BLOCK), 0, (hipStream_t)stream, partial, count, blocks, mean);
-    return grf_launched("grf_domain_final_kernel");
+    return side_launched("grf_domain_final_kernel");
 }
 
 extern "C" int bhn_grf_transport(const bhn_grf_geos *geos, const double *Omega, const double *g, const double *b, const double *divisor,
@@ -195,5 +172,5 @@ extern "C" int bhn_grf_transport(const bhn_grf_geos *geos, const double *Omega, 
     BHN_CHECK_ARG(!(Q_frac > 1.0 || Q_frac < 0.0), "Q_frac should be in [0,1], not %g", Q_frac);
     hipLaunchKernelGGL(grf_transport_kernel, dim3((unsigned)blocks), dim3(GRF_BLOCK), 0, (hipStream_t)stream, k, Omega, g, b, divisor, Q_frac,
                        V_frac, spectral_index, V_frac != 0.0 ? 1 : 0, J, k.n * k.ngeo);
-    return grf_launched("grf_transport_kernel");
+    return side_launched("grf_transport_kernel");
 }

@@ -8,28 +8,12 @@
 //
 // Built into a library of its own, libbhnerf_kerr.so (include/bhnerf_kerr.h): the ABI of libbhnerf_hip.so is not touched.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/bhnerf_kerr.h"
 #include "kerr_trace.h"
+#include "side_lib.h"
 
-static thread_local char g_kerr_err[512] = "";
-
-static int kerr_fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_kerr_err, sizeof(g_kerr_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-extern "C" const char *bhn_kerr_last_error(void) { return g_kerr_err; }
-
-#define BHN_CHECK_ARG(cond, ...) \
-    do {                         \
-        if (!(cond)) return kerr_fail(BHN_EINVAL, __VA_ARGS__); \
-    } while (0)
+extern "C" const char *bhn_kerr_last_error(void) { return side_last_error(); }
 
 #define KT_BLOCK 64
 
@@ -50,12 +34,10 @@ extern "C" int bhn_kerr_trace(const double *alpha, const double *beta, int64_t n
     BHN_CHECK_ARG(!why, "%s (spin %g, inclination %g, M %g, h %g, r_c %g, max_steps %d, ngeo %d)", why, spin, inclination, M, h, r_c,
                   max_steps, ngeo);
     BHN_CHECK_ARG(ngeo == 0 || samples, "ngeo = %d samples per ray asked for, samples is NULL", ngeo);
-    const long long blocks = ((long long)n + KT_BLOCK - 1) / KT_BLOCK;
-    BHN_CHECK_ARG(blocks <= 0x7fffffffLL, "too many rays (%lld) for one launch", (long long)n);
+    const long long blocks = side_blocks(n, KT_BLOCK);
+    BHN_CHECK_ARG(blocks > 0, "too many rays (%lld) for one launch", (long long)n);
     const KtParams p = kt_make_params(spin, inclination, distance, M, h, r_c, max_steps, ngeo);
     hipLaunchKernelGGL(kerr_trace_kernel, dim3((unsigned)blocks), dim3(KT_BLOCK), 0, (hipStream_t)stream, alpha, beta, (long long)n, p,
                        samples, end, status);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return kerr_fail(BHN_EHIP, "launch of kerr_trace_kernel failed: %s", hipGetErrorString(e));
-    return BHN_OK;
+    return side_launched("kerr_trace_kernel");
 }

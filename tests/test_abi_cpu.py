@@ -4,11 +4,14 @@ argument validation) agrees with the oracle.  No compute entry point is called (
 import ctypes as C
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import oracle_np as onp
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import side_lib_support as side                                        # noqa: E402
+from oracle import oracle_np as onp                                    # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -51,6 +54,30 @@ def test_dynamic_symbol_table_is_the_declared_abi_and_nothing_else(lib):
     out = subprocess.run([nm, '-D', '--defined-only', so], capture_output=True, text=True, check=True).stdout
     defined = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
     assert defined == header_symbols(), sorted(set(defined) ^ set(header_symbols()))
+
+
+def test_loader_reports_a_missing_library(tmp_path):
+    from bhnerf_amd import _hip
+    with pytest.raises(_hip.HipError, match='not found'):
+        _hip.load(str(tmp_path / 'libbhnerf_none.so'), {})
+
+
+def test_loader_reports_a_library_that_lacks_a_bound_symbol(lib, tmp_path):
+    """A copy of libbhnerf_kerr.so (the loader keeps one handle per path) bound with a table that names one symbol more."""
+    import shutil
+    from bhnerf_amd import _hip
+    path = str(tmp_path / 'libbhnerf_kerr_copy.so')
+    shutil.copy(_hip.KERR_LIB_PATH, path)
+    with pytest.raises(_hip.HipError, match='rebuild it'):
+        _hip.load(path, dict(_hip.KERR_SIGNATURES, bhn_kerr_missing=(C.c_int, [])))
+    assert path not in _hip._loaded
+
+
+def test_side_library_skeleton_under_the_sanitizers(tmp_path_factory):
+    """tools/side_lib_host.cpp, csrc/side_lib.h without HIP: the message buffer is cut at 511 characters and terminated, and two
+    threads each read back their own messages.  A child process: nothing built with a sanitizer is loaded into this one."""
+    exe, _ = side.build_host_program(tmp_path_factory, 'side_lib_host')
+    side.run_host(exe)
 
 
 def test_tape_info_reports_the_layout_the_kernels_use(lib):

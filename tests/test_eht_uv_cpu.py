@@ -3,16 +3,13 @@ that needs no device.
 
 The plan (workspace layout, row splits) and the per-element arithmetic live in csrc/eht_uv.h and compile with a plain C++
 compiler.  tools/eht_uv_host.cpp walks the launches of bhn_eht_vis / bhn_eht_chi2_uv one workgroup after the other; here it is
-built with g++ -O2 -fsanitize=address,undefined, run as a child process with its outputs and workspace in heap blocks of exactly
+built with g++ -O2 and the sanitizers (tests/side_lib_support.py), run as a child process with its outputs and workspace in heap blocks of exactly
 the documented sizes, and compared with the float64 table-form reference of tests/eht_uv_cases.py at the project's f32 bound
 (2e-5 of the largest element; the loss 2e-5 relative).  Nothing built with a sanitizer is loaded into this Python process.
 
 Also here: DirectDFT.dense() against observation.dft_matrix, closure_table, the batching of TemporalBatchedArgs, the float64
 reference itself against oracle_np.loss_eht on the dense conjugated-legs form, and the symbol table of the library."""
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -20,9 +17,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eht_uv_cases as E                                               # noqa: E402
+import side_lib_support as side                                        # noqa: E402
 from bhnerf_amd import observation                                     # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = ('vis', 'amp', 'cphase')
 
 
@@ -130,14 +127,7 @@ def test_table_form_reference_equals_the_dense_oracle(name):
 @pytest.fixture(scope='module')
 def host_program(tmp_path_factory):
     """tools/eht_uv_host.cpp built with the sanitizers -> run(case dict, dtype, want_grad) -> (vis, loss, dimages or None)."""
-    gxx = shutil.which('g++')
-    assert gxx, 'g++ is needed to build tools/eht_uv_host.cpp'
-    work = tmp_path_factory.mktemp('eht_uv_host')
-    exe = str(work / 'eht_uv_host')
-    cmd = [gxx, '-O2', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-Wall',
-           '-I', os.path.join(ROOT, 'bhnerf_amd', 'csrc'), os.path.join(ROOT, 'tools', 'eht_uv_host.cpp'), '-o', exe]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
+    exe, work = side.build_host_program(tmp_path_factory, 'eht_uv_host')
 
     def run(c, dtype, want_grad=True, scale=1.0, tag='case'):
         H, W, B, Sx = c['H'], c['W'], c['B'], max(c['Sx'], 1)
@@ -151,9 +141,7 @@ def host_program(tmp_path_factory):
         with open(fin, 'wb') as f:
             for a in (head, c['uv'], c['images'], tgt, sigma.astype(np.float32)) + ((c['tri'], c['sign']) if ncp else ()):
                 f.write(np.ascontiguousarray(a).tobytes())
-        res = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert res.returncode == 0, (res.returncode, res.stderr[-4000:])
-        assert not res.stderr.strip(), res.stderr[-4000:]           # a sanitizer report
+        side.run_host(exe, fin, fout)
         raw = open(fout, 'rb').read()
         npix = N * H * W
         assert len(raw) == 8 * N * nvis + 4 + (4 * npix if want_grad else 0)          # the documented sizes, nothing else
@@ -260,21 +248,6 @@ def test_eht_library_exports_its_header_and_keeps_the_library_conventions():
     """libbhnerf_eht.so: the dynamic symbol table is the declarations of include/bhnerf_eht.h and nothing else, the ctypes table
     binds exactly those, and the library references no allocator, no getenv and no synchronisation.  The other two libraries and
     include/bhnerf_hip.h know nothing of it."""
-    import __graft_entry__ as entry
-    entry.build()
     from bhnerf_amd import _hip
-    nm = shutil.which('nm')
-    assert nm, 'nm is needed to read the symbol table'
-    strip = lambda text: re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(bhn_\w+)\s*\(', strip(open(os.path.join(ROOT, 'include', 'bhnerf_eht.h')).read()))))
-    assert declared == ['bhn_eht_chi2_uv', 'bhn_eht_last_error', 'bhn_eht_vis', 'bhn_eht_ws_bytes'] == sorted(_hip.EHT_SIGNATURES)
-    out = subprocess.run([nm, '-D', '--defined-only', _hip.EHT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == declared
-    undefined = subprocess.run([nm, '-D', '--undefined-only', _hip.EHT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for banned in ('hipMalloc', 'hipFree', 'hipHostMalloc', 'getenv', 'hipStreamSynchronize', 'hipDeviceSynchronize', 'malloc'):
-        assert banned not in undefined, banned
-    for header in ('bhnerf_hip.h', 'bhnerf_kerr.h'):
-        assert 'bhn_eht' not in strip(open(os.path.join(ROOT, 'include', header)).read())
-    for path in (_hip.LIB_PATH, _hip.KERR_LIB_PATH):
-        assert 'bhn_eht' not in subprocess.run([nm, '-D', '--defined-only', path], capture_output=True, text=True, check=True).stdout
-    assert not any(k.startswith('bhn_eht') for k in list(_hip.SIGNATURES) + list(_hip.KERR_SIGNATURES))
+    side.assert_library_conventions('bhnerf_eht.h', _hip.EHT_LIB_PATH, _hip.EHT_SIGNATURES, 'bhn_eht',
+                                    ['bhn_eht_chi2_uv', 'bhn_eht_last_error', 'bhn_eht_vis', 'bhn_eht_ws_bytes'])

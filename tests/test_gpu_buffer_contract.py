@@ -39,6 +39,7 @@ import buffer_contract_cases as bc
 from buffer_contract_cases import CASES, expected_flags, problem, reference, tensor_cuts
 from conftest import golden_tree
 from frame_chunk_cases import T_INJ
+from guarded import Guarded
 from oracle import oracle_bf16 as ob
 from oracle import oracle_np as onp
 from test_gpu_backward import GTOL, L2TOL, l2err
@@ -86,36 +87,6 @@ def bf16_bounds(name):
 def dev():
     assert torch.cuda.is_available()
     return torch.device('cuda:0')
-
-
-class Guarded:
-    """`nbytes` of device memory between two guard bands, all pre-filled."""
-
-    def __init__(self, label, nbytes, fill, dev):
-        self.label, self.n, self.fill = label, int(nbytes), fill
-        self.gfill = 0xA5 if fill == 0x00 else fill
-        self.raw = torch.empty((GUARD + self.n + GUARD,), dtype=torch.uint8, device=dev)
-        self.raw.fill_(self.gfill)
-        self.mid = self.raw[GUARD:GUARD + self.n]
-        self.mid.fill_(fill)
-        assert self.mid.data_ptr() % 256 == 0
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.mid.data_ptr())
-
-    def f32(self):
-        return self.mid.view(torch.float32).cpu().numpy()
-
-    def disturbed(self):
-        """None, or where the first guard byte that no longer holds the fill lies (byte offset from the buffer's start)."""
-        for band, base in ((self.raw[:GUARD], -GUARD), (self.raw[GUARD + self.n:], self.n)):
-            bad = torch.nonzero(band != self.gfill)
-            if bad.numel():
-                i = int(bad[0])
-                return '%s (%d bytes): guard byte at offset %d of the buffer is 0x%02x, was 0x%02x (%d guard bytes disturbed)' % (
-                    self.label, self.n, base + i, int(band[i]), self.gfill, int(bad.numel()))
-        return None
 
 
 def f32(v):
@@ -197,7 +168,7 @@ def run_sequence(dev, name, fill, su, least):
     before = {k: v.clone() for k, v in su['inputs'].items()}
     ws_full = int(lib.bhn_render_bwd_workspace_bytes(M, eng.mode, B, geom.P_eff, 0))
     assert ws_full > 0
-    mk = lambda label, n: Guarded(label, n, fill, dev)
+    mk = lambda label, n: Guarded(label, n, fill, dev, guard=GUARD, guard_fill=0xA5 if fill == 0x00 else None)
     nimg, npar = B * geom.Sx * geom.R * 4, eng.nparams * 4
     bufs = dict(packed=mk('packed', int(lib.bhn_packed_bytes(M, eng.mode))), emission=mk('emission', B * su['npts'] * 4),
                 images=mk('images of bhn_render_fwd', nimg), images_train=mk('images of bhn_render_fwd_train', nimg),

@@ -5,7 +5,6 @@ loss_fn_eht and TrainStep.eht_uv, against the float64 table-form reference of te
 Bounds: the project's f32 bound, 2e-5 -- the loss relative, visibilities and dimages relative to their largest element.  A
 'cphase' case must have its smallest visibility amplitude >= 0.05 of the largest (asserted on the float64 reference), so that
 no case sits on the 1 / |vis| pole of the closure-phase gradient."""
-import ctypes as C
 import os
 import sys
 
@@ -16,6 +15,7 @@ import torch
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eht_uv_cases as E                                               # noqa: E402
+from guarded import Guarded                                            # noqa: E402
 
 DTYPES = ('vis', 'amp', 'cphase')
 # relative L2 between the parameter gradients of the matrix-free and the dense training step, measured on an MI355X (DESIGN
@@ -117,33 +117,7 @@ def test_bitwise_reproducible_independent_of_the_batch_and_linear_in_scale(dev, 
     assert float((dimg3 - 2 * dimg).abs().max()) <= 1e-6 * float(dimg3.abs().max())
 
 
-GUARD = 4096          # bytes on either side of a buffer
-
-
-class _Guarded:
-    """`nbytes` bytes of device memory at a 256-byte-aligned address between two guard bands of a known pattern, poisoned with
-    NaN bytes (0xFF)."""
-
-    def __init__(self, nbytes, dev):
-        self.nbytes = nbytes
-        self.raw = torch.full((GUARD + nbytes + GUARD + 256,), 0xA5, dtype=torch.uint8, device=dev)
-        self.off = GUARD + (-(self.raw.data_ptr() + GUARD)) % 256
-        assert self.off >= GUARD and (self.raw.data_ptr() + self.off) % 256 == 0
-        self.view = self.raw[self.off:self.off + nbytes]
-        self.view.fill_(0xFF)
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.raw.data_ptr() + self.off)
-
-    def guards_intact(self):
-        return bool((self.raw[:self.off] == 0xA5).all()) and bool((self.raw[self.off + self.nbytes:] == 0xA5).all())
-
-    def f32(self):
-        return self.view.view(torch.float32)
-
-    def untouched(self):
-        return bool((self.view == 0xFF).all())
+GUARD = 4096          # bytes on either side of a buffer: 0xA5 there, the buffer itself poisoned with NaN bytes (0xFF)
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
@@ -170,7 +144,9 @@ def test_buffer_contract(dev, name, Sx, dtype):
         return lib.bhn_eht_chi2_uv(_hip.ptr(img), _hip.ptr(uv), N, S, nvis, H, W, psx, psy, DTYPES.index(dtype), _hip.ptr(tgt), _hip.ptr(sig),
                                    1.0, _hip.ptr(tri) if ncp else None, _hip.ptr(sign) if ncp else None, ncp, loss, dimages, ws, ws_bytes, stream)
 
-    loss, dimg, ws = _Guarded(4, dev), _Guarded(4 * N * H * W, dev), _Guarded(need, dev)
+    mk = lambda label, nbytes: Guarded(label, nbytes, 0xFF, dev, guard=GUARD, guard_fill=0xA5)
+    loss, dimg, ws = mk('loss', 4), mk('dimages', 4 * N * H * W), mk('ws', need)
+    intact = lambda *bufs: all(b.disturbed() is None for b in bufs)
     # one byte too little workspace: refused, nothing launched
     assert call(loss.ptr, dimg.ptr, ws.ptr, need - 1) == _hip.BHN_EWORKSPACE
     with pytest.raises(_hip.HipError, match='workspace'):
@@ -182,26 +158,26 @@ def test_buffer_contract(dev, name, Sx, dtype):
     torch.cuda.synchronize()
     ref_loss, ref_grad, ref_vis = c['ref'][dtype]
     assert dimg.untouched() and abs(float(loss.f32()[0]) - ref_loss) <= E.F32_TOL * abs(ref_loss)
-    assert loss.guards_intact() and ws.guards_intact() and dimg.guards_intact()
+    assert intact(loss, ws, dimg)
     # loss and gradient into poisoned buffers of exactly the documented sizes
-    loss.view.fill_(0xFF); ws.view.fill_(0xFF)
+    loss.mid.fill_(0xFF); ws.mid.fill_(0xFF)
     assert call(loss.ptr, dimg.ptr, ws.ptr, need) == 0
     torch.cuda.synchronize()
-    got = dimg.f32().cpu().numpy().reshape(ref_grad.shape)
+    got = dimg.f32().reshape(ref_grad.shape)
     assert np.isfinite(got).all() and np.isfinite(float(loss.f32()[0]))                    # every element written
-    assert loss.guards_intact() and ws.guards_intact() and dimg.guards_intact()
+    assert intact(loss, ws, dimg)
     assert E.rel_max(got, ref_grad) <= E.F32_TOL and abs(float(loss.f32()[0]) - ref_loss) <= E.F32_TOL * abs(ref_loss)
     if dtype == 'vis':                                                                     # bhn_eht_vis, the same way
         vneed = int(lib.bhn_eht_ws_bytes(N, nvis, 0, H, W))
-        vis, vws = _Guarded(8 * N * nvis, dev), _Guarded(vneed, dev)
+        vis, vws = mk('vis', 8 * N * nvis), mk('ws of bhn_eht_vis', vneed)
         args = (_hip.ptr(img), _hip.ptr(uv), N, S, nvis, H, W, psx, psy, vis.ptr, vws.ptr)
         assert lib.bhn_eht_vis(*args, vneed - 1, stream) == _hip.BHN_EWORKSPACE
         torch.cuda.synchronize()
         assert vis.untouched() and vws.untouched()
         assert lib.bhn_eht_vis(*args, vneed, stream) == 0
         torch.cuda.synchronize()
-        v = vis.f32().cpu().numpy().view(np.complex64).reshape(ref_vis.shape)
-        assert np.isfinite(v.view(np.float32)).all() and vis.guards_intact() and vws.guards_intact()
+        v = vis.f32().view(np.complex64).reshape(ref_vis.shape)
+        assert np.isfinite(v.view(np.float32)).all() and intact(vis, vws)
         assert E.rel_max(v, ref_vis) <= E.F32_TOL
 
 

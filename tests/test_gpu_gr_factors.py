@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gr_factor_cases as gc                                           # noqa: E402
+from guarded import Guarded                                            # noqa: E402
 from bhnerf_amd import _hip, kgeo                                      # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -133,35 +134,6 @@ GUARD = 1 << 16
 FILLS = (0xFF, 0x7F)            # NaN as float64;  1.4e306 as float64
 
 
-class Guarded:
-    """`nbytes` of device memory between two guard bands at a 256-byte-aligned address, all pre-filled."""
-
-    def __init__(self, label, nbytes, fill, dev):
-        self.label, self.n, self.fill = label, int(nbytes), fill
-        self.raw = torch.empty((GUARD + self.n + GUARD,), dtype=torch.uint8, device=dev)
-        self.raw.fill_(fill)
-        self.mid = self.raw[GUARD:GUARD + self.n]
-        assert self.mid.data_ptr() % 256 == 0
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.mid.data_ptr())
-
-    def disturbed(self):
-        for band, base in ((self.raw[:GUARD], -GUARD), (self.raw[GUARD + self.n:], self.n)):
-            bad = torch.nonzero(band != self.fill)
-            if bad.numel():
-                return '%s (%d bytes): guard byte at offset %d of the buffer changed (%d guard bytes disturbed)' % (
-                    self.label, self.n, base + int(bad[0]), int(bad.numel()))
-        return None
-
-    def poisoned(self, itemsize):
-        """Number of elements that still hold the fill pattern."""
-        if self.n == 0:
-            return 0
-        return int((self.mid.cpu().numpy().reshape(-1, itemsize) == self.fill).all(axis=1).sum())
-
-
 @pytest.mark.parametrize('name,V_frac', [('B', 0.01), ('C', 0.0), ('tiny', 0.0)])
 def test_guard_bands_stay_intact_and_every_output_element_is_written(dev, name, V_frac):
     """Case B with the V row, case C (the library itself writes NaN there) and the one-ray case (a tail workgroup only)."""
@@ -173,8 +145,8 @@ def test_guard_bands_stay_intact_and_every_output_element_is_written(dev, name, 
     blocks = (d.total + 255) // 256
     results = {}
     for fill in FILLS:
-        bufs = dict(g=Guarded('g', 8 * d.total, fill, dev), b=Guarded('b', 8 * 3 * d.total, fill, dev), mean=Guarded('mean', 8, fill, dev),
-                    ws=Guarded('ws', 16 * blocks, fill, dev), J=Guarded('J', 8 * S * d.total, fill, dev))
+        sizes = dict(g=8 * d.total, b=8 * 3 * d.total, mean=8, ws=16 * blocks, J=8 * S * d.total)
+        bufs = {k: Guarded(k, nbytes, fill, dev, guard=GUARD) for k, nbytes in sizes.items()}
         run_library(d, field, domain, dev, True, V_frac, 1, out={k: v.ptr for k, v in bufs.items()})
         bad = [m for m in (v.disturbed() for v in bufs.values()) if m]
         assert not bad, 'fill 0x%02X: %s' % (fill, '; '.join(bad))

@@ -14,13 +14,12 @@ inside the same 1e-10.  The per-row maxima are printed.  MEASURED on the MI355X:
 Closed forms: the radial (Gralla & Lupsasca I_r) and polar (Jacobi sn) checks of tests/test_geodesics_cpu.py on the DEVICE's output, at
 that file's bounds.  Independence, reproducibility, the caller-owned-buffer contract (guard bands, poisoned outputs, in the style of
 tests/test_gpu_buffer_contract.py), the exhausted step budget, and the way through alma.get_raytracing_args into a training step."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from bhnerf_amd import geodesics as G
+from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -229,35 +228,6 @@ GUARD = 1 << 16
 FILLS = (0xFF, 0x7F)            # NaN as float64, -1 as int32;  1.4e306 as float64, 0x7F7F7F7F as int32
 
 
-class Guarded:
-    """`nbytes` of device memory between two guard bands at a 256-byte-aligned address, all pre-filled."""
-
-    def __init__(self, label, nbytes, fill, dev):
-        self.label, self.n, self.fill = label, int(nbytes), fill
-        self.raw = torch.empty((GUARD + self.n + GUARD,), dtype=torch.uint8, device=dev)
-        self.raw.fill_(fill)
-        self.mid = self.raw[GUARD:GUARD + self.n]
-        assert self.mid.data_ptr() % 256 == 0
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.mid.data_ptr())
-
-    def disturbed(self):
-        for band, base in ((self.raw[:GUARD], -GUARD), (self.raw[GUARD + self.n:], self.n)):
-            bad = torch.nonzero(band != self.fill)
-            if bad.numel():
-                return '%s (%d bytes): guard byte at offset %d of the buffer changed (%d guard bytes disturbed)' % (
-                    self.label, self.n, base + int(bad[0]), int(bad.numel()))
-        return None
-
-    def poisoned(self, itemsize):
-        """Number of elements that still hold the fill pattern."""
-        if self.n == 0:
-            return 0
-        return int((self.mid.cpu().numpy().reshape(-1, itemsize) == self.fill).all(axis=1).sum())
-
-
 @pytest.mark.parametrize('ngeo', [40, 0])
 def test_guard_bands_stay_intact_and_every_output_element_is_written(dev, ngeo):
     from bhnerf_amd import _hip
@@ -269,8 +239,8 @@ def test_guard_bands_stay_intact_and_every_output_element_is_written(dev, ngeo):
     a_d, b_d = torch.as_tensor(alpha, device=dev), torch.as_tensor(beta, device=dev)
     results = {}
     for fill in FILLS:
-        samples = Guarded('samples', 8 * 7 * n * ngeo, fill, dev) if ngeo else None
-        end, status = Guarded('end', 8 * 7 * n, fill, dev), Guarded('status', 4 * n, fill, dev)
+        samples = Guarded('samples', 8 * 7 * n * ngeo, fill, dev, guard=GUARD) if ngeo else None
+        end, status = Guarded('end', 8 * 7 * n, fill, dev, guard=GUARD), Guarded('status', 4 * n, fill, dev, guard=GUARD)
         rc = _hip.kerr_lib().bhn_kerr_trace(_hip.ptr(a_d), _hip.ptr(b_d), n, spin, inc, 1000.0, 1.0, H, R_C, MAX_STEPS, ngeo,
                                        samples.ptr if ngeo else None, end.ptr, status.ptr, _hip.stream_ptr(dev))
         _hip.kerr_check(rc)

@@ -3,7 +3,7 @@ device.
 
 The per-point arithmetic lives in csrc/gr_factors.h and compiles with a plain C++ compiler.  tools/gr_factors_host.cpp is a
 stand-alone program around it that walks the library's launches workgroup by workgroup; here it is built with
-g++ -O2 -fsanitize=address,undefined, run as a child process on the cases of tests/gr_factor_cases.py, and compared with the NumPy
+g++ -O2 and the sanitizers (tests/side_lib_support.py), run as a child process on the cases of tests/gr_factor_cases.py, and compared with the NumPy
 functions of kgeo.py composed as alma.image_plane_model composes them -- the same arithmetic the device lanes run, so what is checked
 is the restatement itself, and the sanitizers check the index arithmetic (the k -+ 1 neighbours at both ends of a ray, the tail
 workgroup, the two reduction stages) on blocks of exactly the documented size.  Nothing is loaded into this Python process but the
@@ -13,9 +13,6 @@ Also here: kgeo.emission_factors(backend='numpy') is the composed functions bit 
 device call, and the library's symbol table."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -23,9 +20,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gr_factor_cases as gc                                           # noqa: E402
+import side_lib_support as side                                        # noqa: E402
 from bhnerf_amd import kgeo                                            # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 _HOST = {}
 
@@ -43,14 +40,7 @@ def host_case(name, V_frac=0.0, spectral_index=1):
 @pytest.fixture(scope='module')
 def host_program(tmp_path_factory):
     """tools/gr_factors_host.cpp built with the sanitizers -> a function of a record and the parameters -> (g, b, mean, J)."""
-    gxx = shutil.which('g++')
-    assert gxx, 'g++ is needed to build tools/gr_factors_host.cpp'
-    work = tmp_path_factory.mktemp('gr_factors_host')
-    exe = str(work / 'gr_factors_host')
-    cmd = [gxx, '-O2', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-Wall',
-           '-I', os.path.join(ROOT, 'bhnerf_amd', 'csrc'), os.path.join(ROOT, 'tools', 'gr_factors_host.cpp'), '-o', exe]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
+    exe, work = side.build_host_program(tmp_path_factory, 'gr_factors_host')
 
     def run(geos, Omega, field, domain, fill, V_frac, spectral_index, tag):
         shape = geos.r.shape
@@ -62,9 +52,7 @@ def host_program(tmp_path_factory):
         parts += [np.asarray(Omega, dtype=np.float64).ravel()] + [np.asarray(geos[k], dtype=np.float64).ravel() for k in gc.RAY_FIELDS]
         fin, fout = str(work / (tag + '.in')), str(work / (tag + '.out'))
         np.concatenate(parts).tofile(fin)
-        res = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert res.returncode == 0, (res.returncode, res.stderr[-4000:])
-        assert not res.stderr.strip(), res.stderr[-4000:]           # a sanitizer report
+        side.run_host(exe, fin, fout)
         raw = np.fromfile(fout, dtype=np.float64)
         total = n * ngeo
         assert raw.size == total + 3 * total + 1 + S * total        # the documented sizes, nothing else
@@ -223,26 +211,7 @@ def test_library_exports_its_header_and_keeps_the_library_conventions():
     """libbhnerf_grf.so: the dynamic symbol table is the declarations of include/bhnerf_grf.h and nothing else, the ctypes table
     binds exactly those, and the library references no allocator, no getenv and no synchronisation.  The other three libraries,
     their headers and their ctypes tables do not know the new names."""
-    import __graft_entry__ as entry
-    entry.build()
     from bhnerf_amd import _hip
-    nm = shutil.which('nm')
-    assert nm, 'nm is needed to read the symbol table'
-    strip = lambda text: re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    header = lambda name: strip(open(os.path.join(ROOT, 'include', name)).read())
-    declared = sorted(set(re.findall(r'\b(bhn_\w+)\s*\(', header('bhnerf_grf.h'))))
-    assert declared == sorted(_hip.GRF_SIGNATURES)
-    assert declared == ['bhn_grf_domain_mean', 'bhn_grf_doppler', 'bhn_grf_fluid_field', 'bhn_grf_last_error', 'bhn_grf_transport',
-                        'bhn_grf_ws_bytes']
-    symbols = lambda path, which: subprocess.run([nm, '-D', which, path], capture_output=True, text=True, check=True).stdout
-    out = symbols(_hip.GRF_LIB_PATH, '--defined-only')
-    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == declared
-    undefined = symbols(_hip.GRF_LIB_PATH, '--undefined-only')
-    for banned in ('hipMalloc', 'hipFree', 'hipHostMalloc', 'getenv', 'hipStreamSynchronize', 'hipDeviceSynchronize', 'malloc'):
-        assert banned not in undefined, banned
-    for other in ('bhnerf_hip.h', 'bhnerf_kerr.h', 'bhnerf_eht.h'):
-        assert 'bhn_grf' not in header(other), other
-    for path in (_hip.LIB_PATH, _hip.KERR_LIB_PATH, _hip.EHT_LIB_PATH):
-        assert 'bhn_grf' not in symbols(path, '--defined-only'), path
-    for table in (_hip.SIGNATURES, _hip.KERR_SIGNATURES, _hip.EHT_SIGNATURES):
-        assert not any(k.startswith('bhn_grf') for k in table)
+    side.assert_library_conventions('bhnerf_grf.h', _hip.GRF_LIB_PATH, _hip.GRF_SIGNATURES, 'bhn_grf',
+                                    ['bhn_grf_domain_mean', 'bhn_grf_doppler', 'bhn_grf_fluid_field', 'bhn_grf_last_error',
+                                     'bhn_grf_transport', 'bhn_grf_ws_bytes'])

@@ -1,7 +1,7 @@
 """CPU tests of the GPU Kerr tracer (bhn_kerr_trace, csrc/kerr_trace.hip): everything about it that needs no device.
 
 The per-ray stepping code lives in csrc/kerr_trace.h and compiles with a plain C++ compiler.  tools/kerr_trace_host.cpp is a
-stand-alone program around it; here it is built with g++ -O2 -fsanitize=address,undefined, run as a child process on small ray
+stand-alone program around it; here it is built with g++ -O2 and the sanitizers (tests/side_lib_support.py), run as a child process on small ray
 sets, and compared with geodesics._integrate (the NumPy tracer) -- the same arithmetic the device lanes run, so what is checked is
 the restatement itself (scheme, step rule, constants, capture / escape rules, the Hermite sampling and the end-state fill), and the
 sanitizers check the sample-index arithmetic (several targets inside one step, the fill that starts at the next unwritten sample)
@@ -16,15 +16,15 @@ Also here: back-end selection of geodesics.trace / image_plane_geos, and bhn_ker
 message before any device call)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-from bhnerf_amd import geodesics as G
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import side_lib_support as side                                        # noqa: E402
+from bhnerf_amd import geodesics as G                                  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GR_TOL = 1e-10
 ROWS = ('mino', 'r', 'theta', 'phi', 't', 'vr', 'vth')
 H, R_C, MAX_STEPS = 0.02, 5.0, 400000
@@ -52,22 +52,13 @@ def rays(case):
 @pytest.fixture(scope='module')
 def host_program(tmp_path_factory):
     """tools/kerr_trace_host.cpp built with the sanitizers -> a function (case) -> (end (7, n), status (n), samples (7, n, ngeo))."""
-    gxx = shutil.which('g++')
-    assert gxx, 'g++ is needed to build tools/kerr_trace_host.cpp'
-    work = tmp_path_factory.mktemp('kerr_trace_host')
-    exe = str(work / 'kerr_trace_host')
-    cmd = [gxx, '-O2', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-Wall',
-           '-I', os.path.join(ROOT, 'bhnerf_amd', 'csrc'), os.path.join(ROOT, 'tools', 'kerr_trace_host.cpp'), '-o', exe]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
+    exe, work = side.build_host_program(tmp_path_factory, 'kerr_trace_host')
 
     def run(alpha, beta, spin, inc, dist, M, ngeo, max_steps=MAX_STEPS, tag='case'):
         n = alpha.size
         fin, fout = str(work / (tag + '.in')), str(work / (tag + '.out'))
         np.concatenate([[n, ngeo, max_steps, spin, inc, dist, M, H, R_C], alpha, beta]).astype(np.float64).tofile(fin)
-        res = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert res.returncode == 0, (res.returncode, res.stderr[-4000:])
-        assert not res.stderr.strip(), res.stderr[-4000:]           # a sanitizer report
+        side.run_host(exe, fin, fout)
         raw = open(fout, 'rb').read()
         assert len(raw) == 8 * 7 * n + 4 * n + 8 * 7 * n * ngeo     # the documented sizes, nothing else
         end = np.frombuffer(raw, dtype=np.float64, count=7 * n).reshape(7, n)
@@ -201,20 +192,6 @@ def test_tracer_library_exports_its_header_and_keeps_the_library_conventions():
     binds exactly those, and the library references no allocator, no getenv and no synchronisation (the conventions of
     include/bhnerf_hip.h, which tests/test_abi_cpu.py holds libbhnerf_hip.so to).  The hot path's ABI is not touched: the tracer is
     not declared in include/bhnerf_hip.h and not exported by libbhnerf_hip.so."""
-    import re
-    import __graft_entry__ as entry
-    entry.build()
     from bhnerf_amd import _hip
-    nm = shutil.which('nm')
-    assert nm, 'nm is needed to read the symbol table'
-    strip = lambda text: re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = sorted(set(re.findall(r'\b(bhn_\w+)\s*\(', strip(open(os.path.join(ROOT, 'include', 'bhnerf_kerr.h')).read()))))
-    assert declared == ['bhn_kerr_last_error', 'bhn_kerr_trace'] == sorted(_hip.KERR_SIGNATURES)
-    out = subprocess.run([nm, '-D', '--defined-only', _hip.KERR_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(line.split()[-1] for line in out.splitlines() if line.strip()) == declared
-    undefined = subprocess.run([nm, '-D', '--undefined-only', _hip.KERR_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for banned in ('hipMalloc', 'hipFree', 'hipHostMalloc', 'getenv', 'hipStreamSynchronize', 'hipDeviceSynchronize', 'malloc'):
-        assert banned not in undefined, banned
-    assert 'bhn_kerr' not in strip(open(os.path.join(ROOT, 'include', 'bhnerf_hip.h')).read())
-    assert 'bhn_kerr' not in subprocess.run([nm, '-D', '--defined-only', _hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert not any(k.startswith('bhn_kerr') for k in _hip.SIGNATURES)
+    side.assert_library_conventions('bhnerf_kerr.h', _hip.KERR_LIB_PATH, _hip.KERR_SIGNATURES, 'bhn_kerr',
+                                    ['bhn_kerr_last_error', 'bhn_kerr_trace'])

@@ -104,32 +104,21 @@ def check_table():
 _REFS = {}
 
 
-def tensor_cuts(prob):
-    g = prob['g']
-    return np.cumsum([0] + [g[k % i].size for i in range(prob['depth'] + 1) for k in ('kernel%d', 'bias%d')])
-
-
 def reference(name, recipe=None, drop=None, want_ties=False):
     """dict(emission (B, H*W*G), images (B, Sx, R), grad: the flat gradient of sum(images * dimg) in flax tree order), float64 arrays --
     `recipe` None: oracle_torch in float64, else oracle_bf16's emulator of that recipe.  `drop` (H, W, G) bool: the problem without those
     ray samples (Doppler weight 0: the ReLU-tie adjudication of test_gpu_frame_chunks).  want_ties: instead the (H, W, G) bool of the
     ray samples that reach the image and have a ReLU tie on the reference's own forward."""
-    import torch
-    from conftest import golden_tree, relu_tie_count
+    from conftest import relu_tie_count
     from frame_chunk_cases import T_INJ
-    from oracle import oracle_bf16 as ob, oracle_np as onp, oracle_torch as ot
+    from mlp_problems import oracle_inputs, t64, without_samples
+    from oracle import oracle_bf16 as ob, oracle_torch as ot
     key = (name, recipe, drop is not None, want_ties)
     if key in _REFS:
         return _REFS[key]
     prob = problem(name)
-    g, S, dom = prob['g'], prob['S'], prob['dom']
-    if drop is not None:
-        g = dict(g, g=np.where(drop, 0.0, g['g']))
-    t64 = lambda x: torch.tensor(np.asarray(x, dtype=np.float64))
-    ks, bs = ot.tree_to_lists(golden_tree(g), torch.float64)
-    geom_t = dict(coords=t64(g['coords']), Omega=t64(g['Omega']), t_geos=t64(g['t_geos']), g=t64(g['g']), dtau=t64(g['dtau']),
-                  Sigma=t64(g['Sigma']), J=t64(g['J']) if S else None, t_start_obs=0.0, t_injection=T_INJ)
-    hp = dict(GM_c3=onp.GM_C3_SGRA_HR, scale=dom[0], rmin=dom[1], rmax=dom[2], z_width=dom[3], posenc_deg=prob['deg'], net_depth=prob['depth'])
+    g, S, dom = without_samples(prob['g'], drop), prob['S'], prob['dom']
+    ks, bs, geom_t, hp = oracle_inputs(g)
     tf = t64(g['t_frames'])
     d_em = prob['dimg'].reshape((prob['B'], max(S, 1)) + prob['spatial'])
     d_em = d_em if S else d_em[:, 0]

@@ -4,7 +4,7 @@ tests/test_eht_uv_cpu.py and tests/test_gpu_eht_uv.py.
 The reference is the TABLE form in float64: a dense complex128 A (B, nvis, H W) from the formula of observation.dft_matrix, the
 visibilities A . image, and for closure phases the bispectrum through (tri, tri_sign) -- each baseline's visibility once, a
 conjugate where the sign is -1.  Loss and image gradient come from torch's complex autograd.  tests/test_eht_uv_cpu.py holds it
-to oracle_np.loss_eht and to the `_ref_loss` of tests/test_gpu_eht.py on the dense conjugated-legs form at the small shapes.
+to oracle_np.loss_eht and to dense_ref_loss below (the dense conjugated-legs form of tests/test_gpu_eht.py) at the small shapes.
 
 Inputs: station positions rng.normal(size=(B, ns, 2)) * 3e9 wavelengths, every station pair a baseline, every triple a triangle;
 field of view 16 M of Sgr A*; images a Gaussian blob plus 5 % uniform noise, normalised to ~2 Jy.  The data (target) are the
@@ -22,6 +22,21 @@ MIN_AMP = 0.05                                        # smallest |vis| / largest
 # name -> (H, W, B, seed, stations)
 CASES = {'12x20': (12, 20, 3, 0, 5), '13x7': (13, 7, 2, 1, 4)}
 BIG = (64, 64, 2, 5, 20)                              # 190 baselines, 1140 triangles: the seed satisfies MIN_AMP (asserted)
+
+
+def dense_ref_loss(images, A, target, sigma, scale, dtype):
+    """(loss, d loss / d images) of the dense-matrix EHT chi^2 by float64 complex autograd; 'cphase': A holds the three conjugated legs."""
+    img = torch.tensor(images, dtype=torch.float64, requires_grad=True)
+    At, tg, sg = torch.tensor(A), torch.tensor(target), torch.tensor(sigma)
+    vec = img.reshape(img.shape[0], -1, 1).to(torch.complex128)
+    if dtype == 'cphase':
+        vis = (At.to(torch.complex128) @ vec[:, None]).squeeze(-1)
+        loss = scale * ((1.0 - torch.cos(tg - torch.angle(vis.prod(dim=-2)))) / sg ** 2).sum()
+    else:
+        vis = (At.to(torch.complex128) @ vec).squeeze(-1)
+        loss = scale * (((vis - tg).abs() / sg) ** 2).sum() if dtype == 'vis' else scale * (((vis.abs() - tg) / sg).abs() ** 2).sum()
+    loss.backward()
+    return loss.item(), img.grad.numpy()
 
 
 def blobs(rng, shape):

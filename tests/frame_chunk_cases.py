@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from conftest import mask_tie_points
+from mlp_problems import f32r, stokes_factors, tilted_ray_grid
 from oracle import oracle_np as onp
 
 DENSE, SHELL = (8.0, 0.0, np.inf, np.inf), (8.0, 2.5, 8.0, 4.0)            # scale, rmin, rmax, z_width
@@ -33,8 +34,8 @@ _PROBLEMS = {}
 
 
 def problem(name):
-    """The problem of a case in the layout of a g5_* fixture (float64 arrays of f32-rounded values; geometry in the style of
-    test_gpu_backward.random_problem) + the upstream image gradient `dimg` (B, Sx, R), rand - 0.4."""
+    """The problem of a case in the layout of a g5_* fixture (float64 arrays of f32-rounded values; mlp_problems.tilted_ray_grid, as
+    mlp_problems.random_problem) + the upstream image gradient `dimg` (B, Sx, R), rand - 0.4."""
     if name in _PROBLEMS:
         return _PROBLEMS[name]
     depth, width, mode, S, rays, B, _ = CASES[name] if name in CASES else STEP_CASES[name]
@@ -48,18 +49,9 @@ def build_problem(depth, width, mode, S, deg, H, Wd, G, dom, B):
     x G samples in the domain `dom`, B frames.  tests/buffer_contract_cases.py builds its ray sets with it; the draws and their order
     are those of the frame-chunk cases (pinned by tests/test_buffer_contract_cases_cpu.py)."""
     rng = np.random.default_rng(1000 + 7 * width + depth + 31 * S)
-    alpha, beta = np.meshgrid(np.linspace(-8, 8, H), np.linspace(-8, 8, Wd), indexing='ij')
-    s = np.linspace(-9.6, 9.6, G)
-    inc = np.deg2rad(60.0)
-    coords = np.stack([alpha[..., None] * np.ones(G), beta[..., None] * np.cos(inc) + s * np.sin(inc),
-                       -beta[..., None] * np.sin(inc) + s * np.cos(inc)])
-    r = np.sqrt((coords ** 2).sum(0)) + 0.3
-    f32r = lambda v: np.asarray(v, dtype=np.float32).astype(np.float64)
-    g = dict(coords=f32r(coords), Omega=f32r(1.0 / (r ** 1.5 + 0.1)), t_geos=f32r(-(1000.0 - (s + 9.6)) * np.ones_like(r)),
-             g=f32r(rng.uniform(0.6, 1.4, r.shape)), Sigma=f32r(r ** 2), dtau=f32r((s[1] - s[0]) / r ** 2), J=np.array(1.0))
-    if S:
-        I = rng.uniform(0.5, 1.5, r.shape); chi = rng.uniform(0, np.pi, r.shape)
-        g['J'] = f32r(np.stack([I, 0.85 * I * np.cos(2 * chi), 0.85 * I * np.sin(2 * chi)])[:S])
+    geo, r = tilted_ray_grid(H, Wd, G)
+    g = {k: f32r(v) for k, v in dict(geo, g=rng.uniform(0.6, 1.4, r.shape)).items()}
+    g['J'] = f32r(stokes_factors(rng, r.shape, S)) if S else np.array(1.0)
     tree = onp.he_uniform_params(rng, depth, width, 3 + 6 * deg, dtype=np.float32)
     for i in range(depth + 1):
         g['kernel%d' % i] = tree['MLP_0']['Dense_%d' % i]['kernel'].astype(np.float64)

@@ -10,6 +10,7 @@ import torch
 import buffer_contract_cases as bc
 import frame_chunk_cases as fc
 from conftest import mask_tie_points
+from mlp_problems import tensor_cuts
 from oracle import oracle_np as onp
 
 # sha256 (first 16 hex digits) of every frame_chunk_cases problem as the builder drew it BEFORE build_problem was factored out of
@@ -76,7 +77,7 @@ def test_float64_reference_is_nonzero_in_every_tensor(name):
     ref = bc.reference(name)
     assert np.isfinite(ref['images']).all() and (np.abs(ref['images']).reshape(-1, ref['images'].shape[-1]).max(axis=1) > 0).all()   # every frame and plane
     assert (ref['emission'] != 0).any(axis=1).all()
-    cuts = bc.tensor_cuts(prob)
+    cuts = tensor_cuts(prob['g'])
     assert cuts[-1] == ref['grad'].size and np.isfinite(ref['grad']).all()
     for i, (c0, c1) in enumerate(zip(cuts[:-1], cuts[1:])):
         assert np.abs(ref['grad'][c0:c1]).max() > 0, (name, 'tensor %d' % i)

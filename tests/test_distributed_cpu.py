@@ -28,7 +28,7 @@ def _worker(rank, world, port, out):
         from bhnerf_amd import network, optimization
         from oracle import oracle_torch as ot
         from conftest import golden_tree
-        import test_oracle_golden as tg
+        from mlp_problems import oracle_trainer
         g = dict(np.load(os.path.join(root, 'tests', 'golden', 'g5_predict_e.npz')))      # 4 frames, 4x128
         assert optimization.device_count() == world and network._world() == (rank, world)
         idx = np.array([2, 0, 3, 1])                                  # the batch every rank draws
@@ -37,7 +37,7 @@ def _worker(rank, world, port, out):
         with pytest.raises(ValueError):
             optimization.shard(np.arange(3))
         # per-device SUM of chi^2 over this rank's frames and its gradient, with the oracle
-        tr, t = tg._torch_trainer(g)
+        tr, t = oracle_trainer(g)
         shape = (4,) + g['coords'].shape[1:3]
         tgt = {k: t(g[k + '_full']).reshape(shape) for k in ('target', 'sigma', 'offset')}
         loss, _, grads = tr.loss_and_grad(t(g['t_frames'][mine]), tgt['target'][mine], tgt['sigma'][mine], tgt['offset'][mine], 1.0, 'full')
@@ -69,9 +69,9 @@ def test_two_rank_gradient_exchange_matches_mean_of_sums():
     # reference semantics: grad = (1/ndev) * sum over ALL frames of the batch of d chi^2_frame
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import test_oracle_golden as tg
+    from mlp_problems import oracle_trainer
     g = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g5_predict_e.npz')))
-    tr, t = tg._torch_trainer(g)
+    tr, t = oracle_trainer(g)
     shape = (4,) + g['coords'].shape[1:3]
     tgt = {k: t(g[k + '_full']).reshape(shape) for k in ('target', 'sigma', 'offset')}
     loss, _, grads = tr.loss_and_grad(t(g['t_frames']), tgt['target'], tgt['sigma'], tgt['offset'], 1.0, 'full')
@@ -149,9 +149,9 @@ def _step_worker(rank, world, port, out, overlap=False):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     from bhnerf_amd import constants, network, optimization, units
     from oracle import oracle_np as onp
-    import test_oracle_golden as tg
+    from mlp_problems import oracle_trainer
     g = dict(np.load(os.path.join(root, 'tests', 'golden', 'g5_predict_e.npz')))      # 4 frames, 4x128
-    tr, t = tg._torch_trainer(g)
+    tr, t = oracle_trainer(g)
     assert abs(constants.GM_c3('hr') - onp.GM_C3_SGRA_HR) < 1e-12 * onp.GM_C3_SGRA_HR
     eng = _StubEngine(tr, g['t_start_obs'], g['t_injection'], onp.GM_C3_SGRA_HR)
     H, W = g['coords'].shape[1:3]
@@ -225,9 +225,9 @@ def test_two_rank_training_steps_match_single_process_reference(world):
     # reference: one process, all four frames, gradient / world (pmean of per-device sums), float64
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import test_oracle_golden as tg
+    from mlp_problems import oracle_trainer
     g = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g5_predict_e.npz')))
-    tr, t = tg._torch_trainer(g)
+    tr, t = oracle_trainer(g)
     tr.num_iters, tr.lr_init, tr.lr_final = 3, 1e-3, 1e-4
     p0 = torch.cat([p.detach().reshape(-1) for i in range(len(tr.k)) for p in (tr.k[i], tr.b[i])]).numpy().copy()
     shape = (4,) + g['coords'].shape[1:3]
@@ -263,9 +263,9 @@ def test_two_rank_overlapped_allreduce_is_the_one_step_stale_update():
     assert np.array_equal(res[0][1], res[1][1])                       # identical parameters on both ranks, bitwise
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import test_oracle_golden as tg
+    from mlp_problems import oracle_trainer
     g = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g5_predict_e.npz')))
-    tr, t = tg._torch_trainer(g)
+    tr, t = oracle_trainer(g)
     tr.num_iters, tr.lr_init, tr.lr_final = 3, 1e-3, 1e-4
     p0 = torch.cat([p.detach().reshape(-1) for i in range(len(tr.k)) for p in (tr.k[i], tr.b[i])]).numpy().copy()
     shape = (4,) + g['coords'].shape[1:3]
@@ -298,9 +298,9 @@ def _single_process_step(monkeypatch, train=True, fits=True, group=0):
     sys.path.insert(0, os.path.join(root, 'tests'))
     from bhnerf_amd import network, units
     from oracle import oracle_np as onp
-    import test_oracle_golden as tg
+    from mlp_problems import oracle_trainer
     g = dict(np.load(os.path.join(root, 'tests', 'golden', 'g5_predict_e.npz')))      # 4 frames, 4x128
-    tr, t = tg._torch_trainer(g)
+    tr, t = oracle_trainer(g)
     eng = _StubEngine(tr, g['t_start_obs'], g['t_injection'], onp.GM_C3_SGRA_HR)
     eng.fits, eng.group = fits, group
     H, W = g['coords'].shape[1:3]

@@ -107,7 +107,6 @@ def test_temporal_batched_args_keeps_the_operator_and_its_float64_uv():
 @pytest.mark.parametrize('name', list(E.CASES))
 def test_table_form_reference_equals_the_dense_oracle(name):
     from oracle import oracle_np as onp
-    from test_gpu_eht import _ref_loss                                # float64 complex autograd on dense matrices
     c = E.case(name)
     assert c['min_amp'] >= E.MIN_AMP, c['min_amp']
     print('\n[eht uv] %s: smallest |vis| / largest = %.3f' % (name, c['min_amp']))
@@ -119,7 +118,7 @@ def test_table_form_reference_equals_the_dense_oracle(name):
         loss, grad, _ = c['ref'][dtype]
         want = onp.loss_eht(img64, t64, sigma.astype(np.float64), A, 1.0, dtype)
         assert abs(loss - want) <= 1e-9 * abs(want), (dtype, loss, want)
-        ref_loss, ref_grad = _ref_loss(img64, A, t64, sigma.astype(np.float64), 1.0, dtype)
+        ref_loss, ref_grad = E.dense_ref_loss(img64, A, t64, sigma.astype(np.float64), 1.0, dtype)
         assert abs(ref_loss - want) <= 1e-9 * abs(want)
         assert E.rel_max(grad, ref_grad) < 1e-9, dtype
 

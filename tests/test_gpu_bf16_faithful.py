@@ -28,175 +28,19 @@ import pytest
 import torch
 
 from conftest import golden_tree
+from gpu_support import chi2_step, dev, device_setup, problem_of, ray_args  # noqa: F401
+from mlp_bounds import (FIELDS, GENERAL_SHAPES, RANDOM_SHAPES, bounds, check_mutants, expected_recipe, kernel_width, l2err as l2, maxerr as mx,
+                        mutant_ratios, problem_class)
+from mlp_problems import (CONFIG2, CONFIG2_DOMAINS, config_problem, f32r, oracle_inputs_of, random_problem_inputs, ray_subset,
+                          rays_through_domain, stokes_domain, stokes_problem, t64, targets, tensor_cuts, without_samples)
 from oracle import oracle_bf16 as ob
 from oracle import oracle_np as onp
 from oracle import oracle_torch as ot
 
 pytestmark = pytest.mark.gpu
 
-# bounds against the emulator (the f64 bounds of the same cases: 1e-2 images, 6e-2 / 3e-2 / 2e-2 gradient)
-# Observed on the MI355X, per case (image error / maximum, emission relative L2, loss relative error, gradient relative L2 = the worst
-# of the chi^2, recorded-tape and recompute routes, worst relative L2 of one kernel / bias tensor); for the cases with relu ties
-# adjudicated (7x128, 8x256 S0, 8x384, 8x512) the figures of the problem without the tied samples.  The kernels are bitwise
-# reproducible, so the bound of a case is 4x its own figure, capped at the required bound of its class (CAPS).
-OBSERVED = {
-    '4x256 S0 deg3':               (0.00017, 0.00018, 4e-07, 4.2e-05, 6.8e-05),
-    '4x128 S3 deg3':               (0.00012, 0.0001, 1.4e-07, 2.5e-05, 4.2e-05),
-    '8x64 S2 deg3':                (0.00012, 0.00012, 5.1e-07, 9.8e-05, 0.00026),
-    '6x32 S0 deg3':                (1.4e-05, 3.4e-05, 1.4e-06, 1.7e-05, 3.8e-05),
-    '4x128 S0 deg0':               (1.1e-05, 8.8e-06, 5.5e-08, 1.6e-06, 3.4e-06),
-    '4x256 S3 deg1':               (0.00017, 0.00018, 1.6e-06, 0.0022, 0.0028),
-    '4x64 S0 deg2':                (7e-05, 0.0001, 7.2e-08, 1.3e-05, 1.6e-05),
-    '4x128 S2 deg4':               (0.00014, 7.2e-05, 1.6e-06, 4.2e-05, 0.00014),
-    '4x100 S0 deg3':               (8.6e-05, 0.00018, 3.5e-07, 0.00055, 0.00099),
-    '4x48 S3 deg3':                (6.1e-05, 0.00013, 4.1e-08, 2.6e-05, 4.7e-05),
-    '6x200 S0 deg2':               (0.00015, 0.00023, 1.8e-06, 2.5e-05, 5.7e-05),
-    '4x20 S0 deg3':                (1.2e-06, 1e-06, 2.8e-08, 5.8e-06, 2.3e-05),
-    '5x64 S0 deg3':                (7e-05, 4.8e-05, 1.1e-06, 0.0002, 0.00053),
-    '7x128 S2 deg3':               (9.9e-05, 0.00025, 1.1e-06, 0.00022, 0.00052),
-    '3x32 S0 deg3':                (3e-05, 9.6e-05, 1.6e-07, 1.6e-05, 2.2e-05),
-    '2x64 S3 deg2':                (2.4e-07, 4e-07, 5.9e-08, 2e-06, 6.7e-06),
-    '5x256 S0 deg3':               (0.00017, 0.00016, 2.6e-06, 0.00025, 0.0007),
-    '8x256 S0 deg3':               (0.00055, 0.00046, 2.1e-06, 0.00094, 0.0026),
-    '8x256 S3 deg3':               (0.00034, 0.0005, 3.6e-07, 0.00082, 0.0027),
-    '4x64 S1 deg3':                (3e-05, 1.8e-05, 1.7e-06, 3.5e-05, 8.7e-05),
-    '6x256 S1 deg2':               (0.00014, 0.00024, 7.1e-06, 0.00012, 0.0003),
-    '2x256 S0 deg3':               (4.5e-05, 4.8e-05, 6.8e-06, 2e-05, 6e-05),
-    '4x128 S3 deg5':               (7.7e-05, 0.00014, 7.9e-08, 0.00044, 0.0014),
-    '4x512 S0 deg3':               (9.6e-05, 0.00017, 2.8e-07, 4.6e-05, 0.00012),
-    '3x300 S1 deg6':               (0.00013, 0.00017, 4.8e-06, 0.00022, 0.00066),
-    '2x64 S0 deg7':                (0.00017, 0.00015, 7.5e-07, 3.5e-05, 5.7e-05),
-    '8x384 S2 deg4':               (0.00042, 0.0004, 2.3e-06, 0.0016, 0.0055),
-    '8x512 S0 deg8':               (0.00076, 0.00089, 1.3e-05, 0.0031, 0.014),
-    '5x40 S3 deg10':               (0.00076, 0.00097, 9e-05, 0.00049, 0.0018),
-    'g5_a full':                   (3.7e-07, 3.2e-07, 2.4e-07, 5.1e-08, 2.5e-07),
-    'g5_a lc':                     (3.7e-07, 3.2e-07, 2.8e-07, 5.5e-08, 2.7e-07),
-    'g5_b full':                   (3.9e-07, 3.7e-07, 1.1e-07, 1.1e-07, 2.8e-06),
-    'g5_b lc':                     (3.9e-07, 3.7e-07, 2.5e-08, 1.1e-07, 2.8e-06),
-    'g5_c full':                   (3.1e-07, 4.6e-07, 2.6e-08, 5.9e-08, 2e-07),
-    'g5_c lc':                     (3.1e-07, 4.6e-07, 1.6e-07, 4.8e-08, 1.5e-07),
-    'g5_d full':                   (1.6e-07, 2.8e-07, 2.2e-08, 4.7e-08, 5.3e-07),
-    'g5_d lc':                     (1.6e-07, 2.8e-07, 1.4e-07, 4.7e-08, 5.3e-07),
-    'g5_e full':                   (3.3e-07, 3.4e-07, 5.5e-09, 9.5e-07, 4.1e-06),
-    'g5_e lc':                     (3.3e-07, 3.4e-07, 9.6e-09, 6.1e-07, 3.9e-06),
-    'g5_f full':                   (2.4e-07, 2.8e-07, 1e-07, 3.6e-08, 2.7e-07),
-    'g5_f lc':                     (2.4e-07, 2.8e-07, 8.7e-07, 3.7e-08, 5.8e-07),
-    '4x128 rows 48 skip 1':        (0.00021, 0.00016, 4.8e-08, 2.2e-05, 6.2e-05),
-    '4x128 rows 47 skip 1':        (0.00018, 0.00015, 3.8e-07, 2.8e-05, 8.9e-05),
-    '4x128 rows 48 skip 0':        (8.2e-05, 7.1e-05, 3.9e-08, 2.5e-05, 7.9e-05),
-    '4x128 rows 47 skip 0':        (8.6e-05, 7.4e-05, 3.5e-07, 2.3e-05, 7.6e-05),
-    '4x113 rows 48 skip 1':        (0.00012, 9.6e-05, 2.7e-07, 3e-05, 7.6e-05),
-    '4x113 rows 47 skip 1':        (0.00013, 0.00011, 1.7e-06, 3e-05, 9.5e-05),
-    '4x113 rows 48 skip 0':        (0.00011, 0.00011, 3.7e-07, 2.7e-05, 9.1e-05),
-    '4x113 rows 47 skip 0':        (0.00016, 0.0001, 2.3e-07, 3e-05, 0.00011),
-    '4x97 rows 48 skip 1':         (0.00014, 8.9e-05, 1.2e-07, 1.7e-05, 7.1e-05),
-    '4x97 rows 47 skip 1':         (8.8e-05, 9.4e-05, 7.9e-08, 1.5e-05, 4.7e-05),
-    '4x97 rows 48 skip 0':         (0.00014, 0.00012, 1.6e-06, 3.5e-05, 0.0001),
-    '4x97 rows 47 skip 0':         (0.0001, 0.00012, 2.2e-07, 2.6e-05, 7.3e-05),
-    'config 2 subset masked':      (0.00018, 0.00014, 2.6e-07, 6.6e-05, 0.00013),
-    'config 2 subset all_active':  (0.00015, 0.00015, 2.6e-06, 3.6e-05, 0.00011),
-    'config 5 subset lc S3':       (0.00032, 0.00013, 5.7e-06, 5.6e-05, 0.00011),
-}
-FIELDS = ('image', 'emission', 'loss', 'grad', 'tensor')
-# required bounds (20x under the float64 comparisons' 1e-2 images / 6e-2 and 2e-2 gradient L2); 'deep' (8 hidden layers at width
-# >= 256) is not capped: see problem_class
-CAPS = {'golden': dict(image=5e-4, grad=3e-3, tensor=6e-3), 'random': dict(image=5e-4, grad=3e-3, tensor=6e-3),
-        'fused128': dict(image=5e-4, grad=3e-3, tensor=6e-3), 'subset': dict(image=5e-4, grad=1e-3, tensor=2e-3), 'deep': dict()}
-
-
-def bounds(name, cls, deg=3):
-    """The bounds of case `name`: 4x OBSERVED, capped by CAPS[cls] (the image cap grows with the posenc degree above 5: octave i
-    multiplies the f32 rounding of the warped coordinate by 2^i before the sine, as in test_shapes_outside_the_fused_kernels)."""
-    b = {k: 4.0 * v for k, v in zip(FIELDS, OBSERVED[name])}
-    for k, cap in CAPS[cls].items():
-        b[k] = min(b[k], cap * (max(1.0, 2.0 ** (deg - 5)) if k == 'image' else 1.0))
-    return b
-
-
-def problem_class(depth, width):
-    """'deep': eight hidden layers at width >= 256 -- the bf16 rounding flips of the f32 accumulation compound down eight layers
-    of the chain (not ties: taking the tied samples out does not move them), observed up to 3.1e-3 L2 / 1.4e-2 per tensor, the
-    error growing from the output layer towards layer 0 (the per-layer profile check_case prints).  The emulator with float32
-    instead of float64 accumulation (accum32) moves these problems by 1.6e-4 ... 5.8e-4 with the same profile, 10 ... 100x more
-    than the shallow ones (tests/test_oracle_bf16_cpu.py::test_accumulation_noise_explains_the_largest_errors)."""
-    return 'deep' if depth >= 8 and width >= 256 else 'random'
-
-
-# Mutants (oracle_bf16.MUTANTS) that each case's bounds must see: distance >= 5x the bound in at least one bounded figure (gradient L2,
-# one tensor, images).  Required: act_truncate on every case but TRUNC_BLIND; bias_scale on the goldens and on the fused 4x128 and
-# config 2 / 5 cases (their per-tensor bounds see one output-bias entry x (1 + 2^-8)); drop_group on the goldens and the random /
-# general-path problems but DROP_BLIND; dout_unrounded on the goldens.  Not required (distances printed, measured 0.1 ... 4x): dropping
-# ONE 32-point group out of 2,000 ... 6,000 (fused 4x128, config 2 / 5) or leaving dout unrounded (3e-5 ... 1e-3 of the gradient)
-# moves those problems by less than the kernels' accumulation noise does -- the float32-accumulating emulator (accum32) moves them
-# by as much (tests/test_oracle_bf16_cpu.py::test_accumulation_noise_explains_the_largest_errors).
-TRUNC_BLIND = {'8x512 S0 deg8'}          # 3x: eight layers at width 512, posenc degree 8 -- the noisiest problem (problem_class)
-DROP_BLIND = {'4x100 S0 deg3', '5x256 S0 deg3', '5x40 S3 deg10', '8x256 S0 deg3', '8x384 S2 deg4', '8x512 S0 deg8'}
-
-
-def mutant_ratios(variants, b, cuts):
-    """{mutant: (gradient L2, worst tensor L2, image error / max, distance / bound)} from Bf16Trainer.loss_and_grad_variants."""
-    _, i0, g0 = variants[None]
-    g0, i0 = ob.flat(g0), i0.numpy()
-    out = {}
-    for m in ob.MUTANTS:
-        _, i1, g1 = variants[m]
-        g1 = ob.flat(g1)
-        tens = max(l2(g1[c0:c1], g0[c0:c1]) for c0, c1 in zip(cuts[:-1], cuts[1:]) if np.linalg.norm(g0[c0:c1]) > 0)
-        d = (l2(g1, g0), tens, mx(i1.numpy(), i0))
-        out[m] = d + (max(d[0] / b['grad'], d[1] / b['tensor'], d[2] / b['image']),)
-    return out
-
-
-def required_mutants(name, cls):
-    req = [] if name in TRUNC_BLIND else ['act_truncate']
-    if cls in ('golden', 'fused128', 'subset'):
-        req.append('bias_scale')
-    if cls in ('golden', 'random', 'deep') and name not in DROP_BLIND:
-        req.append('drop_group')
-    return req + (['dout_unrounded'] if cls == 'golden' else [])
-
-
-def check_mutants(name, cls, ratios):
-    print('mutants %-26s %s' % (name, '  '.join('%s %.1e/%.1e/%.1e (%.1fx)' % ((m,) + v) for m, v in ratios.items())))
-    for m in required_mutants(name, cls):
-        assert ratios[m][3] >= 5.0, (name, m, ratios[m])
-
-
-RANDOM_SHAPES = [(256, 4, 0, 3), (128, 4, 3, 3), (64, 8, 2, 3), (32, 6, 0, 3), (128, 4, 0, 0), (256, 4, 3, 1), (64, 4, 0, 2),
-                 (128, 4, 2, 4), (100, 4, 0, 3), (48, 4, 3, 3), (200, 6, 0, 2), (20, 4, 0, 3), (64, 5, 0, 3), (128, 7, 2, 3),
-                 (32, 3, 0, 3), (64, 2, 3, 2), (256, 5, 0, 3), (256, 8, 0, 3), (256, 8, 3, 3), (64, 4, 1, 3), (256, 6, 1, 2),
-                 (256, 2, 0, 3)]           # test_random_problem_f32_and_bf16's 21 shapes + 2x256 (no W_out fold at the ga0_chain width)
-GENERAL_SHAPES = [(128, 4, 3, 5), (512, 4, 0, 3), (300, 3, 1, 6), (64, 2, 0, 7), (384, 8, 2, 4), (512, 8, 0, 8), (40, 5, 3, 10)]
-
-
-def l2(a, b):
-    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
-
-
-def mx(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
-
-
-def expected_recipe(depth, kernel_width, general):
-    """The path the library's selection rules (common.h bhn_folds_wout, fused_bwd.hip ga0_chain_ok, bwd128_supported) give a bf16
-    network -- written out here so that a change of the selection fails loudly instead of comparing against another recipe."""
-    if general:
-        return 'general'
-    if kernel_width == 128 and depth == 4:
-        return 'fused128'
-    if depth < 3:
-        return 'generic'
-    return 'ga0_chain' if kernel_width == 256 else 'fold'
-
-
-def kernel_width(w):
-    return next(k for k in (32, 64, 128, 256) if w <= k) if w <= 256 else w
+# The figures observed on the MI355X per case (OBSERVED), the caps of each class (CAPS), the bound rule, the mutant requirements and the
+# shape lists live in tests/mlp_bounds.py: tests/test_oracle_bf16_cpu.py reads them too.
 
 
 def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, target, sigma, offset, dt='full', loss_scale=1.0,
@@ -204,17 +48,11 @@ def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, ta
     """Device (bf16) vs emulator on one problem: geo holds float64 arrays of f32-rounded values (coords (3,H,W,G), Omega, t_geos,
     g, dtau, Sigma, J (S,H,W,G) or None); `drop` (H,W,G) bool: ray samples taken out of the problem (Doppler weight g = 0 on
     both sides: the relu-tie adjudication).  Returns (errors, recipe, the emulator's tied ray samples)."""
-    from bhnerf_amd import network, units, engine as E
-    if drop is not None:
-        geo = dict(geo, g=np.where(drop, 0.0, geo['g']))
+    geo = without_samples(geo, drop)
     J = geo.get('J')
     S = 0 if J is None else J.shape[0]
-    t64 = lambda x: torch.tensor(np.asarray(x, dtype=np.float64))
-    f = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-    pred = network.NeRF_Predictor(*dom, posenc_deg=deg, net_depth=depth, net_width=width, do_skip=do_skip, mode='bf16', device=dev)
-    eng = pred.engine()
-    geom = pred.geometry(f(geo['coords']), f(geo['Omega']), f(geo['t_geos']), None if J is None else f(J), f(geo['g']), f(geo['dtau']),
-                         f(geo['Sigma']))
+    g = problem_of(tree, geo, t_frames, t_inj, dom, deg, depth, width)
+    pred, eng, geom, flat, tM0 = device_setup(g, 'bf16', dev, do_skip=do_skip)
     if compact is not None:
         assert (geom.compact is not None) == compact, (name, 'layout')
     flags = eng.tape_info((geom.P_eff + 31) // 32)['flags']
@@ -223,14 +61,9 @@ def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, ta
     assert flags['general'] == general and flags['fused128'] == (recipe == 'fused128') and flags['ga0_chain'] == (recipe == 'ga0_chain')
     assert flags['general'] or flags['drop_ga'] == (recipe in ('fold', 'ga0_chain'))      # (fused128: the fold is bwd128_kernel's own)
     # the emulator
-    ks, bs = ot.tree_to_lists(tree, torch.float64)
-    geom_t = dict(coords=t64(geo['coords']), Omega=t64(geo['Omega']), t_geos=t64(geo['t_geos']), g=t64(geo['g']), dtau=t64(geo['dtau']),
-                  Sigma=t64(geo['Sigma']), J=None if J is None else t64(J), t_start_obs=0.0, t_injection=t_inj)
-    hp = dict(GM_c3=onp.GM_C3_SGRA_HR, scale=dom[0], rmin=dom[1], rmax=dom[2], z_width=dom[3], posenc_deg=deg, net_depth=depth,
-              do_skip=do_skip)
+    ks, bs, geom_t, hp = oracle_inputs_of(tree, geo, t_inj, dom, deg, depth, do_skip=do_skip)
     em = ob.Bf16Trainer(ks, bs, geom_t, hp, recipe)
-    sizes = [v.size for i in range(depth + 1) for v in (tree['MLP_0']['Dense_%d' % i]['kernel'], tree['MLP_0']['Dense_%d' % i]['bias'])]
-    cuts = np.cumsum([0] + sizes)
+    cuts = tensor_cuts(g, depth)
     if mutant_cls is not None:            # (the mutants share the faithful forward: loss_and_grad_variants)
         variants = em.loss_and_grad_variants(t64(t_frames), t64(target), t64(sigma), t64(offset), loss_scale, dt)
         check_mutants(name, mutant_cls, mutant_ratios(variants, bounds(name, mutant_cls, deg), cuts))
@@ -240,18 +73,12 @@ def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, ta
     gref = ob.flat(grads_ref)
     img_ref = img_ref.numpy()
     # (1) the chi^2 step through the reference-shaped API
-    params = eng.flatten(tree).requires_grad_(True)
-    ptree = network.ParamTree(); ptree.flat = params
     sq = (lambda v: v[:, 0]) if S == 1 else (lambda v: v)
-    loss, [images] = network.loss_fn_image(ptree, pred.apply, sq(target), sq(sigma), sq(offset), t_frames, f(geo['coords']),
-                                           f(geo['Omega']), 1.0 if J is None else f(J), f(geo['g']), f(geo['dtau']), f(geo['Sigma']),
-                                           0.0, f(geo['t_geos']), t_inj, loss_scale, units.hr, dt)
-    loss.backward()
-    img = images.detach().cpu().numpy().reshape(img_ref.shape)
-    gdev = params.grad.cpu().numpy().astype(np.float64)
+    loss, images, gdev = chi2_step(pred, flat, ray_args(g), t_frames, sq(target), sq(sigma), sq(offset), loss_scale, dt)
+    img = images.cpu().numpy().reshape(img_ref.shape)
+    gdev = gdev.astype(np.float64)
     assert np.abs(img_ref).max() > 0 and np.abs(gref).max() > 0
     # (2) emission: bhn_predict_fwd
-    tM0 = E.frame_offsets(t_frames, 0.0, t_inj, onp.GM_C3_SGRA_HR, dev)
     eng.pack(eng.flatten(tree))
     emis = eng.predict(geom, tM0).cpu().numpy().reshape(len(t_frames), -1)
     emis_ref = em.emission(t64(t_frames)).numpy().reshape(emis.shape)
@@ -300,8 +127,7 @@ def check_and_adjudicate(name, cls, deg, run):
 
 
 def random_case(width, depth, S, deg):
-    from test_gpu_backward import random_problem
-    prob = random_problem(width, depth, S, deg)
+    prob = random_problem_inputs(width, depth, S, deg)
     g = prob['g']
     geo = {k: g[k] for k in ('coords', 'Omega', 't_geos', 'g', 'dtau', 'Sigma')}
     geo['J'] = g['J'] if S else None
@@ -323,10 +149,8 @@ def test_random_problems_against_emulator(dev, width, depth, S, deg):
 @pytest.mark.parametrize('dt', ['full', 'lc'])
 @pytest.mark.parametrize('tag', ['a', 'b', 'c', 'd', 'e', 'f'])
 def test_goldens_against_emulator(dev, golden, tag, dt):
-    from test_gpu_backward import targets
     g = golden('g5_predict_' + tag)
     hp = g['hparams']
-    f32r = lambda v: np.asarray(v, dtype=np.float32).astype(np.float64)           # the device's inputs, in float64
     geo = {k: f32r(g[k]) for k in ('coords', 'Omega', 't_geos', 'g', 'dtau', 'Sigma')}
     geo['J'] = f32r(g['J']) if g['J'].ndim else None
     tree = golden_tree({k: (f32r(v) if k.startswith(('kernel', 'bias')) else v) for k, v in g.items()})
@@ -347,7 +171,6 @@ def test_fused_4x128_against_emulator(dev, rows, width, do_skip):
     H, Wd, G, B = rows, 32, 64, 2
     geo = synthetic.synthetic_geodesics(H, Wd, G, fov_M=16.0, inc_deg=60.0, seed=7)
     t_inj = float(geo['t_injection'])
-    f32r = lambda v: np.asarray(v, dtype=np.float32).astype(np.float64)
     geo = {k: f32r(geo[k]) for k in ('coords', 'Omega', 't_geos', 'g', 'dtau', 'Sigma')}
     geo['J'] = None
     rng = np.random.default_rng(21 + width)
@@ -367,55 +190,33 @@ def test_fused_4x128_against_emulator(dev, rows, width, do_skip):
 def test_config2_ray_subset_against_emulator(dev, domain):
     """The headline path (4x256, ga0_chain): config 2's geometry and weights (test_gpu_fullsize.py), 256 rays x 64 samples x
     8 frames."""
-    from bhnerf_amd import synthetic
-    from test_gpu_fullsize import DOMAINS
-    Hf = Wf = 128; G, B = 64, 8
-    geo = synthetic.synthetic_geodesics(Hf, Wf, G, fov_M=16.0, inc_deg=60.0, seed=0)
-    t_frames = np.linspace(0.0, 1.0, 64)[:B]
-    rng = np.random.default_rng(5)
-    tree = onp.he_uniform_params(rng, 4, 256, 21, dtype=np.float32)
-    for i in range(5):
-        d = tree['MLP_0']['Dense_%d' % i]
-        d['bias'] = rng.uniform(-0.05, 0.05, d['bias'].shape).astype(np.float32)
-    tree['MLP_0']['Dense_4']['bias'] = tree['MLP_0']['Dense_4']['bias'] + 9.0
-    rays = np.sort(np.random.default_rng(12).choice(Hf * Wf, size=256, replace=False))
-    sub = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape((-1, G))[rays].reshape(16, 16, G)).astype(np.float64)
-    sgeo = dict(coords=np.stack([sub(geo['coords'][i]) for i in range(3)]), Omega=sub(geo['Omega']), t_geos=sub(geo['t_geos']),
-                g=sub(geo['g']), dtau=sub(geo['dtau']), Sigma=sub(geo['Sigma']), J=None)
+    c = CONFIG2
+    p = config_problem(**c)
+    geo, tree, t_frames, B = p['geo'], p['tree'], p['t_frames'], len(p['t_frames'])
+    rays = np.sort(np.random.default_rng(12).choice(c['H'] * c['W'], size=256, replace=False))
+    sgeo = {k: (None if v is None else f32r(v)) for k, v in ray_subset(geo, rays).items()}
     rng = np.random.default_rng(13)
     target = rng.uniform(0, 1e-2, (B, 16, 16)); sigma = rng.uniform(0.5, 2.0, (B, 16, 16)); offset = np.zeros((B, 16, 16))
     name = 'config 2 subset %s' % domain
     check_and_adjudicate(name, 'subset', 3, lambda drop: check_case(
-        name, dev, tree, sgeo, t_frames, float(geo['t_injection']), DOMAINS[domain], 4, 256, 3, target, sigma, offset,
+        name, dev, tree, sgeo, t_frames, float(geo['t_injection']), CONFIG2_DOMAINS[domain], 4, 256, 3, target, sigma, offset,
         compact=(domain == 'masked'), drop=drop, mutant_cls=None if drop is not None else 'subset'))
 
 
 def test_config5_ray_subset_lc_stokes_against_emulator(dev):
     """Config 5 (4x128, fused backward) 'lc' chi^2 of the three Stokes light curves on the 256 rays of
     test_gpu_fullsize_stokes.py's gradient test (point-compacted domain, S = 3)."""
-    from test_gpu_fullsize_stokes import make_problem
-    p = make_problem('config5', dev)
+    p = stokes_problem('config5')
     c, geo = p['c'], p['geo']
-    G, HW = c['G'], c['H'] * c['W']
-    r2 = (geo['coords'] ** 2).sum(0).reshape(HW, G)
-    inside = ((r2 >= c['rmin'] ** 2) & (r2 <= c['rmax'] ** 2) & (np.abs(geo['coords'][2].reshape(HW, G)) <= c['z_width'])).sum(1)
-    cand = np.nonzero(inside >= 4)[0]
-    rays = np.sort(np.random.default_rng(41).choice(cand, size=256, replace=False))
-    sub = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape((-1, G))[rays].reshape(16, 16, G)).astype(np.float64)
-    sgeo = dict(coords=np.stack([sub(geo['coords'][i]) for i in range(3)]), Omega=sub(geo['Omega']), t_geos=sub(geo['t_geos']),
-                g=sub(geo['g']), dtau=sub(geo['dtau']), Sigma=sub(geo['Sigma']), J=np.stack([sub(geo['J'][s]) for s in range(3)]))
+    sgeo = {k: f32r(v) for k, v in ray_subset(geo, rays_through_domain(geo, c, 41), stokes=True).items()}
     # the light curves of the subset -> test_gpu_fullsize_stokes' well-conditioned chi^2 (residual >= 40 %, one noise level)
-    t64 = lambda x: torch.tensor(np.asarray(x, dtype=np.float64))
-    ks, bs = ot.tree_to_lists(p['tree'], torch.float64)
-    geom_t = dict(coords=t64(sgeo['coords']), Omega=t64(sgeo['Omega']), t_geos=t64(sgeo['t_geos']), g=t64(sgeo['g']), dtau=t64(sgeo['dtau']),
-                  Sigma=t64(sgeo['Sigma']), J=t64(sgeo['J']), t_start_obs=0.0, t_injection=float(geo['t_injection']))
-    hp = dict(GM_c3=p['GM_c3'], scale=c['rmax'], rmin=c['rmin'], rmax=c['rmax'], z_width=c['z_width'], posenc_deg=3, net_depth=4)
-    lc0 = ot.CpuTrainer(ks, bs, geom_t, hp).forward(t64(p['t_frames'])).detach().sum(dim=(-1, -2)).numpy()
+    tr = ot.CpuTrainer(*oracle_inputs_of(p['tree'], sgeo, geo['t_injection'], stokes_domain(c), 3, 4, GM_c3=p['GM_c3']))
+    lc0 = tr.forward(t64(p['t_frames'])).detach().sum(dim=(-1, -2)).numpy()
     rng = np.random.default_rng(42)
     target = lc0 * rng.uniform(0.3, 0.6, lc0.shape)
     sigma = np.abs(lc0[:, :1]).mean() * rng.uniform(0.05, 0.2, lc0.shape)
     offset = np.zeros_like(lc0)
     name = 'config 5 subset lc S3'
     check_and_adjudicate(name, 'subset', 3, lambda drop: check_case(
-        name, dev, p['tree'], sgeo, p['t_frames'], float(geo['t_injection']), (c['rmax'], c['rmin'], c['rmax'], c['z_width']), 4, 128, 3,
+        name, dev, p['tree'], sgeo, p['t_frames'], float(geo['t_injection']), stokes_domain(c), 4, 128, 3,
         target, sigma, offset, dt='lc', compact=True, drop=drop, mutant_cls=None if drop is not None else 'subset'))

@@ -19,9 +19,9 @@ Asserted: the path (engine.tape_info flags, groups per tile, the ray set's remai
 unchanged; emission, both images and all gradients BITWISE equal across the three fills (the kernels are bitwise reproducible; an
 element nobody writes is NaN under 0xFF); and, on the 0x00 run, the results against a reference outside the code under test: f32 against
 the float64 oracle (1e-5 of the maximum for emission and images -- times 2^(deg-5) for the images of the posenc-degree-10 case, as
-test_shapes_outside_the_fused_kernels -- and test_gpu_backward's GTOL / L2TOL for the gradient against oracle_torch.grad_linear), bf16
+test_shapes_outside_the_fused_kernels -- and mlp_bounds' GTOL / L2TOL for the gradient against oracle_torch.grad_linear), bf16
 against the oracle_bf16 emulator of the recipe that ran inside 4x the figures observed on the MI355X (OBSERVED), capped at
-test_gpu_bf16_faithful's CAPS['random']; the 8-bit tape against the float64 oracle at test_tape8_mode_gradient's bounds.  ReLU ties are
+mlp_bounds' CAPS['random']; the 8-bit tape against the float64 oracle at test_tape8_mode_gradient's bounds.  ReLU ties are
 adjudicated as in test_gpu_frame_chunks (the same problem without the tied ray samples must meet the same bounds).  The taped and the
 recomputed gradient relate as the older tests hold them: bitwise on every path, the images of the training forward bitwise on the
 general path and within test_taped_training_path_equals_recompute_path's rtol 1e-6 / atol 1e-7 of the maximum on the fused ones; the
@@ -36,15 +36,12 @@ import pytest
 import torch
 
 import buffer_contract_cases as bc
-from buffer_contract_cases import CASES, expected_flags, problem, reference, tensor_cuts
-from conftest import golden_tree
-from frame_chunk_cases import T_INJ
+from buffer_contract_cases import CASES, expected_flags, problem, reference
+from gpu_support import dev, device_setup  # noqa: F401
 from guarded import Guarded
+from mlp_bounds import GTOL, IMG_TOL, L2TOL, TOL, capped_bounds, caps_of, l2err, maxerr as mx
+from mlp_problems import tensor_cuts
 from oracle import oracle_bf16 as ob
-from oracle import oracle_np as onp
-from test_gpu_backward import GTOL, L2TOL, l2err
-from test_gpu_bf16_faithful import CAPS
-from test_gpu_forward import IMG_TOL, TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -75,36 +72,16 @@ FIELDS = ('image', 'emission', 'grad', 'tensor')
 
 
 def bf16_bounds(name):
-    deg = CASES[name][4]
-    cap = dict(CAPS['random'], image=CAPS['random']['image'] * max(1.0, 2.0 ** (deg - 5)))
+    cap = caps_of('random', CASES[name][4])
     if name in CAPS_ONLY or name not in OBSERVED:          # (not in OBSERVED: a new case's first, measuring run)
         return dict(cap, emission=cap['image'])
-    b = {k: 4.0 * v for k, v in zip(FIELDS, OBSERVED[name])}
-    return {k: min(v, cap.get(k, np.inf)) for k, v in b.items()}
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
-
-
-def f32(v):
-    return np.ascontiguousarray(np.asarray(v, dtype=np.float32))
+    return capped_bounds(FIELDS, OBSERVED[name], cap)
 
 
 def setup(dev, name, drop=None):
     """Predictor, engine, geometry and the read-only inputs of a case (drop: the tie adjudication's ray samples, Doppler weight 0)."""
-    from bhnerf_amd import network, engine as E
-    depth, width, mode, S, deg, rays, recipe, nwf = CASES[name]
     prob = problem(name)
-    g = prob['g'] if drop is None else dict(prob['g'], g=np.where(drop, 0.0, prob['g']['g']))
-    pred = network.NeRF_Predictor(*prob['dom'], posenc_deg=deg, net_depth=depth, net_width=width, mode=mode, device=dev)
-    eng = pred.engine()
-    geom = pred.geometry(f32(g['coords']), f32(g['Omega']), f32(g['t_geos']), f32(g['J']) if S else None, f32(g['g']), f32(g['dtau']),
-                         f32(g['Sigma']))
-    params = eng.flatten(golden_tree(g))
-    tM0 = E.frame_offsets(g['t_frames'], 0.0, T_INJ, onp.GM_C3_SGRA_HR, dev)
+    pred, eng, geom, params, tM0 = device_setup(prob['g'], CASES[name][2], dev, drop=drop)
     dimg = prob['dimg'].float().to(dev).contiguous()
     assert tuple(dimg.shape) == (prob['B'], geom.Sx, geom.R)
     k = geom.compact
@@ -279,8 +256,7 @@ def compare(name, out, ref, su):
         n = geom.compact['n']
         assert not e[:, n:].any(), (name, 'emission of the dom = 0 padding points')
         e, e_ref = e[:, :n], e_ref[:, bc.domain_mask(prob).reshape(-1)]
-    mx = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
-    cuts = tensor_cuts(prob)
+    cuts = tensor_cuts(prob['g'])
     gref = ref['grad']
     routes = {k: out[k].astype(np.float64) for k in ('grad_tape', 'grad_rec', 'grad_least')}
     tens = [max(l2err(g[c0:c1], gref[c0:c1]) for g in routes.values()) for c0, c1 in zip(cuts[:-1], cuts[1:])]
@@ -305,7 +281,7 @@ def test_results_against_reference_and_between_routes(dev, name):
         assert first_difference(a, b_) is None, (name, 'images of the training forward', first_difference(a, b_))
     else:
         assert np.allclose(a, b_, rtol=1e-6, atol=1e-7 * float(np.abs(b_).max())), (name, 'images of the training forward')
-    cuts = tensor_cuts(su['prob'])
+    cuts = tensor_cuts(su['prob']['g'])
     vs_full = 0.0
     for c0, c1 in zip(cuts[:-1], cuts[1:]):
         x, y = out['grad_least'][c0:c1].astype(np.float64), out['grad_rec'][c0:c1].astype(np.float64)

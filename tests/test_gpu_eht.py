@@ -4,27 +4,10 @@ import numpy as np
 import pytest
 import torch
 
+from eht_uv_cases import dense_ref_loss
+from gpu_support import dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
-
-
-def _ref_loss(images, A, target, sigma, scale, dtype):
-    img = torch.tensor(images, dtype=torch.float64, requires_grad=True)
-    At, tg, sg = torch.tensor(A), torch.tensor(target), torch.tensor(sigma)
-    vec = img.reshape(img.shape[0], -1, 1).to(torch.complex128)
-    if dtype == 'cphase':
-        vis = (At.to(torch.complex128) @ vec[:, None]).squeeze(-1)
-        loss = scale * ((1.0 - torch.cos(tg - torch.angle(vis.prod(dim=-2)))) / sg ** 2).sum()
-    else:
-        vis = (At.to(torch.complex128) @ vec).squeeze(-1)
-        loss = scale * (((vis - tg).abs() / sg) ** 2).sum() if dtype == 'vis' else scale * (((vis.abs() - tg) / sg).abs() ** 2).sum()
-    loss.backward()
-    return loss.item(), img.grad.numpy()
 
 
 @pytest.mark.parametrize('dtype', ['vis', 'amp', 'cphase'])
@@ -37,7 +20,7 @@ def test_chi2_eht_golden_and_gradient(dev, golden, dtype):
     images = torch.tensor(g['images'], dtype=torch.float32, device=dev)
     loss, dimg = engine.chi2_eht(images.reshape(3, -1), A, target, g['sigma'], scale, dtype)
     assert abs(loss.item() - float(g['loss_' + dtype])) < 2e-5 * abs(float(g['loss_' + dtype]))     # reference's own value
-    ref_loss, ref_grad = _ref_loss(g['images'], A, target, g['sigma'], scale, dtype)
+    ref_loss, ref_grad = dense_ref_loss(g['images'], A, target, g['sigma'], scale, dtype)
     assert abs(ref_loss - float(g['loss_' + dtype])) < 1e-9 * abs(ref_loss)
     err = np.abs(dimg.cpu().numpy().reshape(ref_grad.shape) - ref_grad).max() / np.abs(ref_grad).max()
     assert err < 2e-5, err

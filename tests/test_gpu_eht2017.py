@@ -12,6 +12,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from eht_uv_cases import dense_ref_loss                                # noqa: E402
+from gpu_support import dev                                           # noqa: E402,F401
 
 NPIX, G, NT = 256, 100, 8
 FOV_M = 16.0
@@ -19,15 +21,8 @@ RAD_PER_M = 5.03e-6 / 3600.0 * np.pi / 180.0          # GM/c^2/D of Sgr A* in ra
 
 
 @pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
-
-
-@pytest.fixture(scope='module')
 def setup(dev, golden):
     from bhnerf_amd import constants, network, observation, synthetic, units
-    from test_gpu_eht import _ref_loss                                     # noqa: F401  (float64 complex autograd)
     g = golden('g11_eht2017')
     frames = np.arange(0, 64, 64 // NT)                                    # 8 of the 64 frames of the track
     t_hr = g['t_hr'][frames]
@@ -65,7 +60,6 @@ def _render(s):
 def test_loss_fn_eht_at_config4_size_vs_oracle(dev, setup):
     from bhnerf_amd import engine, observation
     from oracle import oracle_np as onp
-    from test_gpu_eht import _ref_loss
     s = setup
     images = _render(s)                                                    # (8, 256, 256) float32 on the device
     assert images.shape == (NT, NPIX, NPIX) and float(images.sum()) > 0
@@ -86,7 +80,7 @@ def test_loss_fn_eht_at_config4_size_vs_oracle(dev, setup):
         ref = onp.loss_eht(host, target.astype(np.complex128 if dtype == 'vis' else np.float64), sigma.astype(np.float64),
                            A.astype(np.complex128), 1.0, dtype)
         assert abs(loss.item() - ref) <= 2e-5 * abs(ref), (dtype, loss.item(), ref)                 # f32 tolerance of north_star
-        ref_loss, ref_grad = _ref_loss(host, A, target, sigma, 1.0, dtype)
+        ref_loss, ref_grad = dense_ref_loss(host, A, target, sigma, 1.0, dtype)
         assert abs(ref_loss - ref) <= 1e-6 * abs(ref)                     # the two float64 references agree
         err = np.abs(dimg.cpu().numpy().reshape(ref_grad.shape) - ref_grad).max() / np.abs(ref_grad).max()
         assert err < 2e-5, (dtype, err)

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import eht_uv_cases as E                                               # noqa: E402
 from guarded import Guarded                                            # noqa: E402
+from gpu_support import dev                                           # noqa: E402,F401
 
 DTYPES = ('vis', 'amp', 'cphase')
 # relative L2 between the parameter gradients of the matrix-free and the dense training step, measured on an MI355X (DESIGN
@@ -23,12 +24,6 @@ DTYPES = ('vis', 'amp', 'cphase')
 # differences) and never above 1e-3.
 MEASURED_STEP_GRAD_L2 = {'vis': 6.43e-8, 'cphase': 9.08e-7}
 STEP_GRAD_BOUND = {k: min(10.0 * v, 1e-3) for k, v in MEASURED_STEP_GRAD_L2.items()}
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
 
 
 def _chi2(c, dtype, dev, want_grad=True, scale=1.0, op=None, images=None):

@@ -9,23 +9,18 @@ import pytest
 import torch
 
 from conftest import golden_tree
+from gpu_support import predictor_of
+from mlp_bounds import IMG_TOL, TOL, relerr
 from oracle import oracle_np as onp
 
 pytestmark = pytest.mark.gpu
 PRED = ['a', 'b', 'c', 'd', 'e', 'f']
-TOL = {'f32': 1e-5, 'bf16': 2e-2}          # emission (observed <= 9.4e-7 / 1.0e-2, tools/diag_tol.py)
-IMG_TOL = {'f32': 1e-5, 'bf16': 1e-2}      # images (observed <= 6.8e-7 / 5.7e-3)
 
 
 @pytest.fixture(scope='module')
 def dev():
     assert torch.cuda.is_available(), 'GPU tests need a HIP device'
     return torch.device('cuda:0')
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def test_selftest_lane_maps(dev):
@@ -84,11 +79,7 @@ def test_geom_prepare(dev, golden):
 
 
 def _predictor(g, mode, dev):
-    from bhnerf_amd import network
-    hp = g['hparams']
-    pred = network.NeRF_Predictor(hp[0], hp[1], hp[2], hp[3], posenc_deg=int(hp[4]), net_depth=int(hp[5]),
-                                  net_width=int(hp[6]), mode=mode, device=dev)
-    return pred, golden_tree(g)
+    return predictor_of(g, mode, dev), golden_tree(g)
 
 
 @pytest.mark.parametrize('mode', ['f32', 'bf16'])

@@ -4,10 +4,10 @@ host offsets tM0 and dimages, clamps the later grids to the first pass's, calibr
 slabs once at the end; every kernel flush reads its slab back and adds.  A share that is stored instead of added changes ONE tensor,
 far below the bf16 mode's bounds against the float64 oracle -- so each case here holds the CHUNKED gradient
 
-* to its reference: f32 against the float64 linear-gradient oracle (oracle_torch.grad_linear) inside test_gpu_backward's GTOL /
+* to its reference: f32 against the float64 linear-gradient oracle (oracle_torch.grad_linear) inside mlp_bounds' GTOL /
   L2TOL (2e-5), bf16 against the rounding-faithful emulator of the path that ran (oracle_bf16, the recipe asserted through
   engine.tape_info) inside 4x the figures observed on the MI355X (OBSERVED; the kernels are bitwise reproducible), capped at
-  test_gpu_bf16_faithful's CAPS['random'] (3e-3 whole gradient, 6e-3 worst tensor); ReLU ties adjudicated as there (the tied ray
+  mlp_bounds' CAPS['random'] (3e-3 whole gradient, 6e-3 worst tensor); ReLU ties adjudicated as there (the tied ray
   samples get Doppler weight 0 on both sides, same bounds);
 * to the all-at-once call on another predictor, per parameter tensor, rtol 1e-5 / atol 1e-6 of the tensor's largest entry
   (test_workspace_frame_chunking_is_equivalent's bound: the recomputed tape is the same point by point, only the order of the f32
@@ -22,15 +22,14 @@ in the first frames, dimages differs in every frame and Stokes plane: a wrong fr
 """
 import numpy as np
 import pytest
-import torch
 
-from conftest import golden_tree, relu_tie_count
-from frame_chunk_cases import CASES, RAY_SETS, T_INJ, problem
+from conftest import relu_tie_count
+from frame_chunk_cases import CASES, RAY_SETS, problem
+from gpu_support import dev, device_setup  # noqa: F401
+from mlp_bounds import CAPS, GTOL, L2TOL, capped_bounds, expected_recipe, kernel_width, l2err
+from mlp_problems import oracle_inputs, t64, tensor_cuts, without_samples
 from oracle import oracle_bf16 as ob
-from oracle import oracle_np as onp
 from oracle import oracle_torch as ot
-from test_gpu_backward import GTOL, L2TOL, l2err
-from test_gpu_bf16_faithful import CAPS, expected_recipe, kernel_width
 
 pytestmark = pytest.mark.gpu
 
@@ -56,30 +55,16 @@ OBSERVED = {
 
 
 def bf16_bounds(key):
-    cap = CAPS['random']
-    return min(4.0 * OBSERVED[key][0], cap['grad']), min(4.0 * OBSERVED[key][1], cap['tensor'])
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
+    b = capped_bounds(('grad', 'tensor'), OBSERVED[key], CAPS['random'])
+    return b['grad'], b['tensor']
 
 
 _REFS, _RUNS = {}, {}
 
 
-def t64(x):
-    return torch.tensor(np.asarray(x, dtype=np.float64))
-
-
-def f32(v):
-    return np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-
-
 def dropped(prob, drop):
     """The problem without the ray samples `drop` (H, W, G): Doppler weight 0 on both sides (the ReLU-tie adjudication)."""
-    return prob if drop is None else dict(prob, g=dict(prob['g'], g=np.where(drop, 0.0, prob['g']['g'])))
+    return dict(prob, g=without_samples(prob['g'], drop))
 
 
 def reference(name, recipe, drop=None, want_ties=False):
@@ -91,11 +76,7 @@ def reference(name, recipe, drop=None, want_ties=False):
         return _REFS[key]
     prob = dropped(problem(name), drop)
     g, S = prob['g'], prob['S']
-    ks, bs = ot.tree_to_lists(golden_tree(g), torch.float64)
-    geom_t = dict(coords=t64(g['coords']), Omega=t64(g['Omega']), t_geos=t64(g['t_geos']), g=t64(g['g']), dtau=t64(g['dtau']),
-                  Sigma=t64(g['Sigma']), J=t64(g['J']) if S else None, t_start_obs=0.0, t_injection=T_INJ)
-    dom = prob['dom']
-    hp = dict(GM_c3=onp.GM_C3_SGRA_HR, scale=dom[0], rmin=dom[1], rmax=dom[2], z_width=dom[3], posenc_deg=3, net_depth=prob['depth'])
+    ks, bs, geom_t, hp = oracle_inputs(g)
     d_em = prob['dimg'].reshape((prob['B'], max(S, 1)) + prob['spatial'])
     d_em = d_em if S else d_em[:, 0]
     em = None if recipe is None else ob.Bf16Trainer(ks, bs, geom_t, hp, recipe)
@@ -110,19 +91,11 @@ def reference(name, recipe, drop=None, want_ties=False):
     return out
 
 
-def tensor_cuts(g, depth):
-    return np.cumsum([0] + [g[k % i].size for i in range(depth + 1) for k in ('kernel%d', 'bias%d')])
-
-
 def device_gradients(dev, prob, mode, k, calls):
     """`calls` x eng.render_bwd on a FRESH predictor -- all frames at once (k None), or with max_workspace_bytes = the size query
     for k frames -> (gradients, info)."""
-    from bhnerf_amd import network, engine as E
-    g, S, B, depth, width = prob['g'], prob['S'], prob['B'], prob['depth'], prob['width']
-    pred = network.NeRF_Predictor(*prob['dom'], posenc_deg=3, net_depth=depth, net_width=width, mode=mode, device=dev)
-    eng = pred.engine()
-    geom = pred.geometry(f32(g['coords']), f32(g['Omega']), f32(g['t_geos']), f32(g['J']) if S else None, f32(g['g']), f32(g['dtau']),
-                         f32(g['Sigma']))
+    g, B = prob['g'], prob['B']
+    pred, eng, geom, flat, tM0 = device_setup(g, mode, dev)
     P, gpf = geom.P_eff, geom.P_eff // 32
     flags = eng.tape_info(gpf)['flags']
     if k is None:
@@ -136,8 +109,7 @@ def device_gradients(dev, prob, mode, k, calls):
             # need by the tape of at most 11 groups per frame.  One more frame costs more than k + 1 such margins, so the tape of
             # k + 1 frames does not fit the query for k in either tiling: THIS is what makes the launch stop at k frames per pass
             assert q(k + 1, P) - q(k, P) > (k + 1) * (q(1, P + 12 * 32) - q(1, P))
-    eng.pack(eng.flatten(golden_tree(g)))
-    tM0 = E.frame_offsets(g['t_frames'], 0.0, T_INJ, onp.GM_C3_SGRA_HR, dev)
+    eng.pack(flat)
     dimg = prob['dimg'].float().to(dev).contiguous()
     assert tuple(dimg.shape) == (B, geom.Sx, geom.R)
     grads = [eng.render_bwd(geom, tM0, dimg).cpu().numpy().astype(np.float64) for _ in range(calls)]

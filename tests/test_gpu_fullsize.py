@@ -14,38 +14,19 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import oracle_np as onp
+from gpu_support import chi2_step, dev, device_setup, problem_of  # noqa: F401
+from mlp_problems import CONFIG2, CONFIG2_DOMAINS as DOMAINS, config_problem, flat_grad, oracle_images, oracle_inputs_of, ray_subset, t64
 from oracle import oracle_torch as ot
 
 pytestmark = pytest.mark.gpu
-H = W = 128
-G = 64
-B = 8
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
+H, W, G, B = CONFIG2['H'], CONFIG2['W'], CONFIG2['G'], len(CONFIG2['t_frames'])
 
 
 @pytest.fixture(scope='module')
 def problem(dev):
-    from bhnerf_amd import constants, engine, synthetic
-    geo = synthetic.synthetic_geodesics(H, W, G, fov_M=16.0, inc_deg=60.0, seed=0)
-    t_frames = np.linspace(0.0, 1.0, 64)[:B]
-    rng = np.random.default_rng(5)
-    tree = onp.he_uniform_params(rng, 4, 256, 21, dtype=np.float32)
-    for i in range(5):
-        d = tree['MLP_0']['Dense_%d' % i]
-        d['bias'] = rng.uniform(-0.05, 0.05, d['bias'].shape).astype(np.float32)
-    tree['MLP_0']['Dense_4']['bias'] = tree['MLP_0']['Dense_4']['bias'] + 9.0      # emission ~ sigmoid(-1): a visible image
-    tM0 = engine.frame_offsets(t_frames, 0.0, geo['t_injection'], constants.GM_c3('hr'), dev)
-    return dict(geo=geo, t_frames=t_frames, tree=tree, tM0=tM0, GM_c3=constants.GM_c3('hr'))
-
-
-DOMAINS = {'masked': (8.0, 2.0, 8.0, 4.0),                    # scale, rmin, rmax, z_width: tutorial-style recovery domain
-           'all_active': (8.0, 0.0, np.inf, np.inf)}          # bench.py's headline variant
+    from bhnerf_amd import engine
+    p = config_problem(**CONFIG2)
+    return dict(p, tM0=engine.frame_offsets(p['t_frames'], 0.0, p['geo']['t_injection'], p['GM_c3'], dev))
 
 
 @pytest.fixture(params=['masked', 'all_active'])
@@ -54,30 +35,14 @@ def domain(request):
 
 
 def setup(problem, mode, dev, domain='masked'):
-    from bhnerf_amd import network
-    geo = problem['geo']
-    pred = network.NeRF_Predictor(*DOMAINS[domain], net_depth=4, net_width=256, mode=mode, device=dev)
-    eng = pred.engine()
-    geom = pred.geometry(geo['coords'], geo['Omega'], geo['t_geos'], None, geo['g'], geo['dtau'], geo['Sigma'])
-    eng.pack(eng.flatten(problem['tree']))
+    g = problem_of(problem['tree'], problem['geo'], problem['t_frames'], problem['geo']['t_injection'], DOMAINS[domain], 3, 4, CONFIG2['width'])
+    pred, eng, geom, flat, _ = device_setup(g, mode, dev)
+    eng.pack(flat)
     if domain == 'all_active':
         assert geom.visited_fraction == 1.0 and geom.active_fraction > 0.99        # dense layout, (nearly) every sample live
     else:
         assert geom.visited_fraction < 0.9                                          # point-compacted layout
     return pred, eng, geom
-
-
-def oracle_images(problem, rays, domain='masked'):
-    geo = problem['geo']
-    scale, rmin, rmax, z_width = DOMAINS[domain]
-    # (as a 12 x 8 "image": the reference's squeeze / broadcast conventions, which the oracle keeps, assume no
-    #  singleton spatial axis)
-    sub = lambda v: v.reshape((-1, G))[rays].reshape(12, 8, G).astype(np.float64)
-    coords = np.stack([sub(geo['coords'][i]) for i in range(3)])
-    tree = {'MLP_0': {k: {kk: np.asarray(vv, dtype=np.float64) for kk, vv in v.items()} for k, v in problem['tree']['MLP_0'].items()}}
-    e = onp.predictor_apply(tree, problem['t_frames'], coords, sub(geo['Omega']), 0.0, sub(geo['t_geos']), float(geo['t_injection']),
-                            GM_c3=problem['GM_c3'], scale=scale, rmin=rmin, rmax=rmax, z_width=z_width)
-    return onp.image_plane_prediction(e, 1.0, sub(geo['g']), sub(geo['dtau']), sub(geo['Sigma'])).reshape(B, 96)      # (B, nrays)
 
 
 @pytest.mark.parametrize('mode,tol', [('f32', 1e-5), ('bf16', 1e-2)])
@@ -87,7 +52,7 @@ def test_forward_full_size_against_oracle_on_a_ray_subset_and_both_routes(dev, p
     images = eng.render(geom, problem['tM0'])[:, 0]                                   # (B, R)
     assert images.shape == (B, H * W) and float(images.max()) > 0
     rays = np.random.default_rng(11).choice(H * W, size=96, replace=False)
-    ref = oracle_images(problem, rays, domain)
+    ref = oracle_images(problem, rays, DOMAINS[domain])
     got = images[:, torch.as_tensor(rays, device=dev)].cpu().numpy()
     assert np.abs(got - ref).max() <= tol * np.abs(ref).max(), np.abs(got - ref).max() / np.abs(ref).max()
     # route 2: emission (B,P) from the predictor kernel, integrated by the stand-alone ray-sum kernel
@@ -134,33 +99,21 @@ def test_gradient_full_width_against_oracle_on_a_ray_subset(dev, problem, domain
     """4x256 network, 256 rays of the full geometry x 64 samples x 8 frames: chi^2 gradient vs torch.autograd on the f64 oracle,
     in the parity mode (f32), the throughput mode (bf16) and the opt-in 8-bit-tape mode (bf16_t8: bf16 arithmetic, e4m3 dW
     operands) -- the observed errors are printed."""
-    from bhnerf_amd import network, units
+    from bhnerf_amd import network
     geo = problem['geo']
     scale, rmin, rmax, z_width = DOMAINS[domain]
     rays = np.sort(np.random.default_rng(12).choice(H * W, size=256, replace=False))
-    sub = lambda v: np.ascontiguousarray(v.reshape((-1, G))[rays].reshape(16, 16, G))
-    g = dict(coords=np.stack([sub(geo['coords'][i]) for i in range(3)]), Omega=sub(geo['Omega']), t_geos=sub(geo['t_geos']),
-             g=sub(geo['g']), dtau=sub(geo['dtau']), Sigma=sub(geo['Sigma']))
+    g = ray_subset(geo, rays)
     rng = np.random.default_rng(13)
     target = rng.uniform(0, 1e-2, (B, 16, 16)); sigma = rng.uniform(0.5, 2.0, (B, 16, 16)); offset = np.zeros((B, 16, 16))
-    t64 = lambda x: torch.tensor(np.asarray(x, dtype=np.float64))
-    ks, bs = ot.tree_to_lists(problem['tree'], torch.float64)
-    geom_t = dict(coords=t64(g['coords']), Omega=t64(g['Omega']), t_geos=t64(g['t_geos']), g=t64(g['g']), dtau=t64(g['dtau']),
-                  Sigma=t64(g['Sigma']), J=None, t_start_obs=0.0, t_injection=float(geo['t_injection']))
-    hp = dict(GM_c3=problem['GM_c3'], scale=scale, rmin=rmin, rmax=rmax, z_width=z_width, posenc_deg=3, net_depth=4)
-    tr = ot.CpuTrainer(ks, bs, geom_t, hp)
+    tr = ot.CpuTrainer(*oracle_inputs_of(problem['tree'], g, geo['t_injection'], DOMAINS[domain], 3, 4, GM_c3=problem['GM_c3']))
     loss_ref, _, grads_ref = tr.loss_and_grad(t64(problem['t_frames']), t64(target), t64(sigma), t64(offset), 1.0, 'full')
-    n = len(tr.k)
-    gref = np.concatenate([np.concatenate([grads_ref[i].numpy().ravel(), grads_ref[n + i].numpy().ravel()]) for i in range(n)])
+    gref = flat_grad(grads_ref)
     for mode, l2tol in (('f32', 2e-5), ('bf16', 2e-2), ('bf16_t8', 2.5e-2)):
         pred = network.NeRF_Predictor(scale, rmin, rmax, z_width, net_depth=4, net_width=256, mode=mode, device=dev)
-        params = pred.engine().flatten(problem['tree']).requires_grad_(True)
-        tree = network.ParamTree()
-        tree.flat = params
-        loss, _ = network.loss_fn_image(tree, pred.apply, target, sigma, offset, problem['t_frames'], g['coords'], g['Omega'], 1.0,
-                                        g['g'], g['dtau'], g['Sigma'], 0.0, g['t_geos'], float(geo['t_injection']), 1.0, units.hr, 'full')
-        loss.backward()
-        gdev = params.grad.cpu().numpy().astype(np.float64)
+        rt = dict(g, J=1.0, t_start_obs=0.0, t_injection=float(geo['t_injection']))
+        loss, _, gdev = chi2_step(pred, pred.engine().flatten(problem['tree']), rt, problem['t_frames'], target, sigma, offset)
+        gdev = gdev.astype(np.float64)
         assert abs(loss.item() - loss_ref.item()) <= (1e-5 if mode == 'f32' else 2e-2) * abs(loss_ref.item())
         err = float(np.linalg.norm(gdev - gref) / np.linalg.norm(gref))
         with capsys.disabled():

@@ -13,57 +13,28 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import chi2_step, dev, device_setup, problem_of  # noqa: F401
+from mlp_problems import (STOKES_CONFIGS as CONFIGS, config_tree, flat_grad, oracle_images, oracle_inputs_of, ray_subset, rays_through_domain,
+                          stokes_domain, stokes_problem, t64)
 from oracle import oracle_np as onp
+from oracle import oracle_torch as ot
 
 pytestmark = pytest.mark.gpu
 B = 8
-CONFIGS = {
-    'config3': dict(H=256, W=256, G=128, width=256, fov=40.0, inc=60.0, spin=0.94, rmin=2.024, rmax=20.0, z_width=4.0),
-    'config5': dict(H=64, W=64, G=100, width=128, fov=40.0, inc=12.0, spin=0.0, rmin=6.0, rmax=20.0, z_width=4.0),
-}
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
 
 
 def make_problem(name, dev):
-    from bhnerf_amd import constants, engine, synthetic
-    c = CONFIGS[name]
-    geo = synthetic.synthetic_geodesics(c['H'], c['W'], c['G'], fov_M=c['fov'], inc_deg=c['inc'], spin=c['spin'], S=3, seed=3)
-    t_frames = np.linspace(0.0, 1.7, 128)[:B]
-    rng = np.random.default_rng(21)
-    tree = onp.he_uniform_params(rng, 4, c['width'], 21, dtype=np.float32)
-    for i in range(5):
-        d = tree['MLP_0']['Dense_%d' % i]
-        d['bias'] = rng.uniform(-0.05, 0.05, d['bias'].shape).astype(np.float32)
-    tree['MLP_0']['Dense_4']['bias'] = tree['MLP_0']['Dense_4']['bias'] + 9.0
-    tM0 = engine.frame_offsets(t_frames, 0.0, geo['t_injection'], constants.GM_c3('hr'), dev)
-    return dict(c=c, geo=geo, t_frames=t_frames, tree=tree, tM0=tM0, GM_c3=constants.GM_c3('hr'))
+    from bhnerf_amd import engine
+    p = stokes_problem(name)
+    return dict(p, tM0=engine.frame_offsets(p['t_frames'], 0.0, p['geo']['t_injection'], p['GM_c3'], dev))
 
 
 def setup(p, mode, dev):
-    from bhnerf_amd import network
     c, geo = p['c'], p['geo']
-    pred = network.NeRF_Predictor(c['rmax'], c['rmin'], c['rmax'], c['z_width'], net_depth=4, net_width=c['width'], mode=mode, device=dev)
-    eng = pred.engine()
-    geom = pred.geometry(geo['coords'], geo['Omega'], geo['t_geos'], geo['J'], geo['g'], geo['dtau'], geo['Sigma'])
-    eng.pack(eng.flatten(p['tree']))
+    g = problem_of(p['tree'], geo, p['t_frames'], geo['t_injection'], stokes_domain(c), 3, 4, c['width'])
+    pred, eng, geom, flat, _ = device_setup(g, mode, dev)
+    eng.pack(flat)
     return pred, eng, geom
-
-
-def oracle_images(p, rays):
-    c, geo = p['c'], p['geo']
-    G = c['G']
-    sub = lambda v: v.reshape((-1, G))[rays].reshape(12, 8, G).astype(np.float64)
-    coords = np.stack([sub(geo['coords'][i]) for i in range(3)])
-    J = np.stack([sub(geo['J'][s]) for s in range(3)])
-    tree = {'MLP_0': {k: {kk: np.asarray(vv, dtype=np.float64) for kk, vv in v.items()} for k, v in p['tree']['MLP_0'].items()}}
-    e = onp.predictor_apply(tree, p['t_frames'], coords, sub(geo['Omega']), 0.0, sub(geo['t_geos']), float(geo['t_injection']),
-                            GM_c3=p['GM_c3'], scale=c['rmax'], rmin=c['rmin'], rmax=c['rmax'], z_width=c['z_width'])
-    return onp.image_plane_prediction(e, J, sub(geo['g']), sub(geo['dtau']), sub(geo['Sigma'])).reshape(B, 3, 96)
 
 
 @pytest.mark.parametrize('name', ['config5', 'config3'])
@@ -71,7 +42,7 @@ def test_polarised_forward_against_oracle_on_a_ray_subset(dev, name):
     p = make_problem(name, dev)
     c = p['c']
     rays = np.random.default_rng(31).choice(c['H'] * c['W'], size=96, replace=False)
-    ref = oracle_images(p, rays)
+    ref = oracle_images(p, rays, stokes_domain(c), stokes=True)
     assert np.abs(ref).max() > 0
     # bf16: 1e-2 of the image maximum for Stokes I; Q and U are signed sums (cancellation along the ray), observed 1.05e-2
     for mode, tol in (('f32', 1e-5), ('bf16', 2e-2)):
@@ -156,11 +127,7 @@ def test_config3_render_with_reference_pinned_J(dev):
     t_inj = -float(geos.r_o + fov / 4)
     GM = constants.GM_c3('hr')
     rng = np.random.default_rng(33)
-    tree = onp.he_uniform_params(rng, 4, 256, 21, dtype=np.float32)
-    for i in range(5):
-        d = tree['MLP_0']['Dense_%d' % i]
-        d['bias'] = rng.uniform(-0.05, 0.05, d['bias'].shape).astype(np.float32)
-    tree['MLP_0']['Dense_4']['bias'] = tree['MLP_0']['Dense_4']['bias'] + 9.0
+    tree = config_tree(rng, 256)
     rmin, rmax, zw = 2.024, fov / 2, 4.0
     rays = np.random.default_rng(34).choice(NA * NA, size=96, replace=False)
     sub = lambda v: v.reshape((-1, NG))[rays].reshape(12, 8, NG).astype(np.float64)
@@ -198,25 +165,12 @@ def test_polarised_lightcurve_gradient_against_oracle_on_a_ray_subset(dev, name,
     light curves are sums of signed pixels that cancel to a few per cent of the I light curve, and chi^2's gradient is proportional
     to the residual of every light curve: a 2e-7 error of the pixels is a 1e-5 error of lc_Q.  The test prints that figure
     (`lc rel diff`); the float32 reference has the same pixels."""
-    from oracle import oracle_torch as ot
-    from bhnerf_amd import network, units
+    from bhnerf_amd import network
     p = make_problem(name, dev)
     c, geo = p['c'], p['geo']
-    G, HW = c['G'], c['H'] * c['W']
     # 256 rays drawn among those that cross the recovery domain (most rays of the 40 M field of view miss |z| <= 4, r <= 20)
-    r2 = (geo['coords'] ** 2).sum(0).reshape(HW, G)
-    inside = ((r2 >= c['rmin'] ** 2) & (r2 <= c['rmax'] ** 2) & (np.abs(geo['coords'][2].reshape(HW, G)) <= c['z_width'])).sum(1)
-    cand = np.nonzero(inside >= 4)[0]
-    rays = np.sort(np.random.default_rng(41).choice(cand, size=256, replace=False))
-    sub = lambda v: np.ascontiguousarray(v.reshape((-1, G))[rays].reshape(16, 16, G))
-    g = dict(coords=np.stack([sub(geo['coords'][i]) for i in range(3)]), Omega=sub(geo['Omega']), t_geos=sub(geo['t_geos']),
-             g=sub(geo['g']), dtau=sub(geo['dtau']), Sigma=sub(geo['Sigma']), J=np.stack([sub(geo['J'][s]) for s in range(3)]))
-    t64 = lambda x: torch.tensor(np.asarray(x, dtype=np.float64))
-    ks, bs = ot.tree_to_lists(p['tree'], torch.float64)
-    geom_t = dict(coords=t64(g['coords']), Omega=t64(g['Omega']), t_geos=t64(g['t_geos']), g=t64(g['g']), dtau=t64(g['dtau']),
-                  Sigma=t64(g['Sigma']), J=t64(g['J']), t_start_obs=0.0, t_injection=float(geo['t_injection']))
-    hp = dict(GM_c3=p['GM_c3'], scale=c['rmax'], rmin=c['rmin'], rmax=c['rmax'], z_width=c['z_width'], posenc_deg=3, net_depth=4)
-    tr = ot.CpuTrainer(ks, bs, geom_t, hp)
+    g = ray_subset(geo, rays_through_domain(geo, c, 41), stokes=True)
+    tr = ot.CpuTrainer(*oracle_inputs_of(p['tree'], g, geo['t_injection'], stokes_domain(c), 3, 4, GM_c3=p['GM_c3']))
     with torch.no_grad():
         lc0 = tr.forward(t64(p['t_frames'])).sum(dim=(-1, -2)).numpy()                    # (B, 3) light curves of the subset
     assert np.abs(lc0[:, 0]).max() > 0
@@ -231,22 +185,17 @@ def test_polarised_lightcurve_gradient_against_oracle_on_a_ray_subset(dev, name,
     sigma = np.abs(lc0[:, :1]).mean() * rng.uniform(0.05, 0.2, lc0.shape)
     offset = np.zeros_like(lc0)
     loss_ref, _, grads_ref = tr.loss_and_grad(t64(p['t_frames']), t64(target), t64(sigma), t64(offset), 1.0, 'lc')
-    n = len(tr.k)
-    gref = np.concatenate([np.concatenate([grads_ref[i].numpy().ravel(), grads_ref[n + i].numpy().ravel()]) for i in range(n)])
+    gref = flat_grad(grads_ref)
     assert np.linalg.norm(gref) > 0
     for mode, l2tol in (('f32', 2e-5), ('bf16', 3e-2)):
         pred = network.NeRF_Predictor(c['rmax'], c['rmin'], c['rmax'], c['z_width'], net_depth=4, net_width=c['width'], mode=mode, device=dev)
         gm = pred.geometry(g['coords'], g['Omega'], g['t_geos'], g['J'], g['g'], g['dtau'], g['Sigma'])
         assert gm.compact is not None and gm.S == 3                                       # the point-compacted layout, three Stokes planes
-        params = pred.engine().flatten(p['tree']).requires_grad_(True)
-        tree = network.ParamTree()
-        tree.flat = params
-        loss, [images] = network.loss_fn_image(tree, pred.apply, target, sigma, offset, p['t_frames'], g['coords'], g['Omega'], g['J'],
-                                               g['g'], g['dtau'], g['Sigma'], 0.0, g['t_geos'], float(geo['t_injection']), 1.0, units.hr, 'lc')
-        loss.backward()
-        lc_dev = images.detach().double().sum(dim=(-1, -2)).cpu().numpy()                   # the device's float32 pixels, summed in double
+        rt = dict(g, t_start_obs=0.0, t_injection=float(geo['t_injection']))
+        loss, images, gdev = chi2_step(pred, pred.engine().flatten(p['tree']), rt, p['t_frames'], target, sigma, offset, dt='lc')
+        lc_dev = images.double().sum(dim=(-1, -2)).cpu().numpy()                            # the device's float32 pixels, summed in double
         lc_diff = np.abs(lc_dev - lc0).max(axis=0) / np.abs(lc0).max(axis=0)               # per Stokes parameter
-        gdev = params.grad.cpu().numpy().astype(np.float64)
+        gdev = gdev.astype(np.float64)
         lerr = abs(loss.item() - loss_ref.item()) / abs(loss_ref.item())
         err = float(np.linalg.norm(gdev - gref) / np.linalg.norm(gref))
         emax = float(np.abs(gdev - gref).max() / np.abs(gref).max())
@@ -266,33 +215,22 @@ def test_polarised_gradient_on_the_full_geometry_against_oracle(dev, name, capsy
     run at their real sizes.  `config5` is BASELINE config 5 (64 x 64 rays x 100 samples: 8-group tiles); `config5_128sq` the same
     geometry on 128 x 128 rays -- more than 3,072 in-domain groups per frame, so the forward pair runs on 12-wave workgroups
     (PolBF16X) in front of bwd128_kernel.  Tolerances: f32 2e-5, bf16 3e-2 relative L2 (observed values are printed)."""
-    from oracle import oracle_torch as ot
-    from bhnerf_amd import constants, engine, network, synthetic, units
+    from bhnerf_amd import network, synthetic
     c = dict(CONFIGS['config5'])
     if name == 'config5_128sq':
         c.update(H=128, W=128)
     geo = synthetic.synthetic_geodesics(c['H'], c['W'], c['G'], fov_M=c['fov'], inc_deg=c['inc'], spin=c['spin'], S=3, seed=3)
     p = make_problem('config5', dev)                                                    # (weights and frames of the 'config5' problem)
-    G, HW = c['G'], c['H'] * c['W']
-    r2 = (geo['coords'] ** 2).sum(0).reshape(HW, G)
-    inside = ((r2 >= c['rmin'] ** 2) & (r2 <= c['rmax'] ** 2) & (np.abs(geo['coords'][2].reshape(HW, G)) <= c['z_width'])).sum(1)
-    rays = np.sort(np.random.default_rng(43).choice(np.nonzero(inside >= 4)[0], size=256, replace=False))
-    sub = lambda v: np.ascontiguousarray(v.reshape((-1, G))[rays].reshape(16, 16, G))
-    t64 = lambda x: torch.tensor(np.asarray(x, dtype=np.float64))
-    ks, bs = ot.tree_to_lists(p['tree'], torch.float64)
-    geom_t = dict(coords=t64(np.stack([sub(geo['coords'][i]) for i in range(3)])), Omega=t64(sub(geo['Omega'])), t_geos=t64(sub(geo['t_geos'])),
-                  g=t64(sub(geo['g'])), dtau=t64(sub(geo['dtau'])), Sigma=t64(sub(geo['Sigma'])), J=t64(np.stack([sub(geo['J'][s]) for s in range(3)])),
-                  t_start_obs=0.0, t_injection=float(geo['t_injection']))
-    hp = dict(GM_c3=p['GM_c3'], scale=c['rmax'], rmin=c['rmin'], rmax=c['rmax'], z_width=c['z_width'], posenc_deg=3, net_depth=4)
-    tr = ot.CpuTrainer(ks, bs, geom_t, hp)
+    HW = c['H'] * c['W']
+    rays = rays_through_domain(geo, c, 43)
+    tr = ot.CpuTrainer(*oracle_inputs_of(p['tree'], ray_subset(geo, rays, stokes=True), geo['t_injection'], stokes_domain(c), 3, 4, GM_c3=p['GM_c3']))
     with torch.no_grad():
         img0 = tr.forward(t64(p['t_frames'])).numpy()                                     # (B, 3, 16, 16)
     rng = np.random.default_rng(44)
     tgt_s = img0 * rng.uniform(0.3, 0.6, img0.shape)
     sig_s = np.abs(img0[:, :1]).mean() * rng.uniform(0.05, 0.2, img0.shape)
     loss_ref, _, grads_ref = tr.loss_and_grad(t64(p['t_frames']), t64(tgt_s), t64(sig_s), t64(np.zeros_like(img0)), 1.0, 'full')
-    n = len(tr.k)
-    gref = np.concatenate([np.concatenate([grads_ref[i].numpy().ravel(), grads_ref[n + i].numpy().ravel()]) for i in range(n)])
+    gref = flat_grad(grads_ref)
     assert np.linalg.norm(gref) > 0
     # the same loss on the full image plane: target 0 and sigma = inf wherever the oracle has no ray
     target = np.zeros((B, 3, HW), dtype=np.float32); sigma = np.full((B, 3, HW), np.inf, dtype=np.float32)
@@ -304,14 +242,9 @@ def test_polarised_gradient_on_the_full_geometry_against_oracle(dev, name, capsy
         assert gm.compact is not None and gm.S == 3 and gm.compact['ray_span'] in (1, 2)
         groups = (gm.P_eff + 31) // 32
         assert (groups >= 3072) == (name == 'config5_128sq')                              # the 12-wave tiles of the fused 4x128 forward pair
-        params = pred.engine().flatten(p['tree']).requires_grad_(True)
-        tree = network.ParamTree()
-        tree.flat = params
-        loss, _ = network.loss_fn_image(tree, pred.apply, target.reshape(shp), sigma.reshape(shp), np.zeros(shp, dtype=np.float32), p['t_frames'],
-                                        geo['coords'], geo['Omega'], geo['J'], geo['g'], geo['dtau'], geo['Sigma'], 0.0, geo['t_geos'],
-                                        float(geo['t_injection']), 1.0, units.hr, 'full')
-        loss.backward()
-        gdev = params.grad.cpu().numpy().astype(np.float64)
+        loss, _, gdev = chi2_step(pred, pred.engine().flatten(p['tree']), dict(geo, t_start_obs=0.0), p['t_frames'], target.reshape(shp),
+                                  sigma.reshape(shp), np.zeros(shp, dtype=np.float32))
+        gdev = gdev.astype(np.float64)
         assert np.isfinite(gdev).all()
         lerr = abs(loss.item() - loss_ref.item()) / abs(loss_ref.item())
         err = float(np.linalg.norm(gdev - gref) / np.linalg.norm(gref))
@@ -320,5 +253,5 @@ def test_polarised_gradient_on_the_full_geometry_against_oracle(dev, name, capsy
                   % (name, mode, groups, gm.compact['ray_span'], err, lerr))
         assert lerr <= (1e-5 if mode == 'f32' else 3e-2)
         assert err < l2tol, (mode, err)
-        del pred, gm, params, tree, loss
+        del pred, gm, loss
         torch.cuda.empty_cache()

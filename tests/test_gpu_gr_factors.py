@@ -20,15 +20,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gr_factor_cases as gc                                           # noqa: E402
 from guarded import Guarded                                            # noqa: E402
+from gpu_support import dev                                           # noqa: E402,F401
 from bhnerf_amd import _hip, kgeo                                      # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
 
 
 _CASES = {}

@@ -7,16 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import dev  # noqa: F401
 from oracle import oracle_np as onp
 from oracle import oracle_torch as ot
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
 
 
 def setup(g, dev):

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from bhnerf_amd import geodesics as G
+from gpu_support import dev  # noqa: F401
 from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
@@ -36,12 +37,6 @@ CASES = {
     'flat space': (0.0, np.deg2rad(50.0), (2.0, 6.0), (-5.0, -3.0), 2, 2, 30, 200.0, 1e-9, 0),
     'edge on': (0.8, 0.5 * np.pi, (-6.0, 6.0), (-5.0, 5.0), 3, 2, 25, 1000.0, 1.0, 0),               # inclination exactly pi / 2
 }
-
-
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
 
 
 def geos_kw(case):

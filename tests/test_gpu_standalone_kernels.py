@@ -15,71 +15,22 @@ branch it is for, and tests/test_standalone_refs_cpu.py proves on the CPU that e
   * prints `observed / bound` per output.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_support
 import standalone_cases as sc
+from gpu_support import dev, lib, place, ptr, stream_ptr as _stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BHN_OK, BHN_EINVAL = 0, 1
 
 
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from bhnerf_amd import _hip
-    return _hip.lib()
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def place(arr, dev, shift=0):
-    """`arr` on the device as a contiguous view that starts `shift` elements into a fresh allocation: shift 1 is a 4-byte
-    aligned float view, shift 2 an 8-byte aligned one."""
-    a = np.ascontiguousarray(arr)
-    if a.dtype == np.complex64:
-        a = a.view(np.float32)
-    buf = torch.zeros(a.size + shift + 8, dtype=torch.from_numpy(a.reshape(-1)[:1]).dtype, device=dev)
-    assert buf.data_ptr() % 256 == 0
-    view = buf[shift:shift + a.size]
-    view.copy_(torch.from_numpy(a.reshape(-1)))
-    assert view.is_contiguous() and view.data_ptr() % 16 == (shift * a.itemsize) % 16
-    return view
-
-
-class Out:
-    """An output of n elements inside a sentinel-filled buffer: GUARD elements before, GUARD after."""
-
-    def __init__(self, n, dev, shift=0, dtype=torch.float32, init=None):
-        self.n, self.lo = int(n), sc.GUARD + shift
-        self.fill = 0xA5 if dtype == torch.uint8 else sc.SENTINEL
-        self.buf = torch.full((self.lo + self.n + sc.GUARD,), self.fill, dtype=dtype, device=dev)
-        self.view = self.buf[self.lo:self.lo + self.n]
-        if init is not None:
-            self.view.copy_(torch.from_numpy(np.ascontiguousarray(init).reshape(-1)))
-        assert self.view.data_ptr() % 16 == (shift * self.buf.element_size()) % 16
-
-    def numpy(self):
-        before, after = self.buf[:self.lo], self.buf[self.lo + self.n:]
-        assert bool((before == self.fill).all()) and bool((after == self.fill).all()), 'a store landed outside the output'
-        return self.view.cpu().numpy().copy()
-
-    def untouched(self):
-        return bool((self.buf == self.fill).all())
+Out = functools.partial(gpu_support.Out, guard=sc.GUARD, sentinel=sc.SENTINEL)
 
 
 def twice(run):

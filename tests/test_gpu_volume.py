@@ -6,63 +6,22 @@ goes through the C ABI twice into fresh outputs with sentinel guard bands: bitwi
 restatement of the float32-rounded arrays (the view is double on both sides).  `observed / bound` is printed per case.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_support
 import volume_cases as vc
+from gpu_support import dev, lib, place, ptr, stream_ptr as _stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BHN_OK, BHN_EINVAL = 0, 1
 
 
-@pytest.fixture(scope='module')
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from bhnerf_amd import _hip
-    return _hip.lib()
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def place(arr, dev, shift=0):
-    """`arr` on the device as a contiguous float view that starts `shift` elements into a fresh allocation."""
-    a = np.ascontiguousarray(arr, dtype=np.float32)
-    buf = torch.zeros(a.size + shift + 8, dtype=torch.float32, device=dev)
-    view = buf[shift:shift + a.size]
-    view.copy_(torch.from_numpy(a.reshape(-1)))
-    assert view.data_ptr() % 16 == (shift * 4) % 16
-    return view
-
-
-class Out:
-    """An output of n floats inside a sentinel-filled buffer: GUARD elements before, GUARD after."""
-
-    def __init__(self, n, dev, shift=0):
-        self.n, self.lo = int(n), vc.GUARD + shift
-        self.buf = torch.full((self.lo + self.n + vc.GUARD,), vc.SENTINEL, dtype=torch.float32, device=dev)
-        self.view = self.buf[self.lo:self.lo + self.n]
-
-    def numpy(self):
-        before, after = self.buf[:self.lo], self.buf[self.lo + self.n:]
-        assert bool((before == vc.SENTINEL).all()) and bool((after == vc.SENTINEL).all()), 'a store landed outside the output'
-        return self.view.cpu().numpy().copy()
-
-    def untouched(self):
-        return bool((self.buf == vc.SENTINEL).all())
+Out = functools.partial(gpu_support.Out, guard=vc.GUARD, sentinel=vc.SENTINEL)
 
 
 def make_view(inp):

@@ -6,7 +6,7 @@
 * with the rounding switched off, every recipe IS the float64 model of oracle_torch (forward, loss and autograd gradient to
   1e-12): the W_out fold and the fused 4x128 output row sum_k K G + b g are algebraically the plain backward;
 * the mutants of the emulator (one 32-point group dropped from every dW, the output bias gradient scaled by 1 + 2^-8,
-  activations truncated instead of rounded, dout not rounded) that test_gpu_bf16_faithful.required_mutants names move the goldens
+  activations truncated instead of rounded, dout not rounded) that mlp_bounds.required_mutants names move the goldens
   and the random / general-path problems of the GPU tests by at least 5x each case's GPU bound (the fused 4x128 and config 2 / 5
   cases check theirs in the GPU test itself);
 * the largest GPU errors are what float32 accumulation alone does to those problems (accum32), not a missing rounding point.
@@ -15,9 +15,10 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import golden_tree
+from mlp_bounds import (GENERAL_SHAPES, OBSERVED, RANDOM_SHAPES, bounds, check_mutants, expected_recipe, kernel_width, mutant_ratios,
+                        problem_class)
+from mlp_problems import golden_problem, random_problem_emulator_args, small_problem
 from oracle import oracle_bf16 as ob
-from oracle import oracle_np as onp
 from oracle import oracle_torch as ot
 
 PRED = ['a', 'b', 'c', 'd', 'e', 'f']
@@ -91,47 +92,6 @@ def test_relu_rounds_then_clamps():
 # --------------------------------------------------------------------------------------------------------------------------
 # problems
 # --------------------------------------------------------------------------------------------------------------------------
-def golden_problem(g, dt):
-    hp = g['hparams']
-    t = lambda x: torch.tensor(x, dtype=torch.float64)
-    ks, bs = ot.tree_to_lists(golden_tree(g))
-    geom = dict(coords=t(g['coords']), Omega=t(g['Omega']), t_geos=t(g['t_geos']), g=t(g['g']), dtau=t(g['dtau']), Sigma=t(g['Sigma']),
-                J=(t(g['J']) if g['J'].ndim else None), t_start_obs=float(g['t_start_obs']), t_injection=float(g['t_injection']))
-    hpd = dict(GM_c3=onp.GM_C3_SGRA_HR, scale=hp[0], rmin=hp[1], rmax=hp[2], z_width=hp[3], posenc_deg=int(hp[4]), net_depth=int(hp[5]))
-    S = g['J'].shape[0] if g['J'].ndim else None
-    b, sp = len(g['t_frames']), g['coords'].shape[1:3]
-    shape = ((b, S) + sp if S else (b,) + sp) if dt == 'full' else ((b, S) if S else (b,))
-    tg = [t(g[k + '_' + dt].reshape(shape)) for k in ('target', 'sigma', 'offset')]
-    return ks, bs, geom, hpd, t(g['t_frames']), tg, float(hp[7])
-
-
-def small_problem(depth, width, S, do_skip, deg=3, seed=0):
-    """A small random problem (6 x 5 rays x 40 samples, 2 frames, masked domain) for the identity tests."""
-    rng = np.random.default_rng(seed + 10 * depth + S)
-    H, Wd, G, B = 6, 5, 40, 2
-    alpha, beta = np.meshgrid(np.linspace(-7, 7, H), np.linspace(-7, 7, Wd), indexing='ij')
-    s = np.linspace(-9.0, 9.0, G)
-    coords = np.stack([alpha[..., None] * np.ones(G), beta[..., None] * 0.5 + s * 0.8, -beta[..., None] * 0.8 + s * 0.5])
-    r = np.sqrt((coords ** 2).sum(0)) + 0.3
-    f32r = lambda v: torch.tensor(np.asarray(v, dtype=np.float32).astype(np.float64))
-    geom = dict(coords=f32r(coords), Omega=f32r(1.0 / (r ** 1.5 + 0.1)), t_geos=f32r(-(1000.0 - (s + 9.0)) * np.ones_like(r)),
-                g=f32r(rng.uniform(0.6, 1.4, r.shape)), Sigma=f32r(r ** 2), dtau=f32r((s[1] - s[0]) / r ** 2), t_start_obs=0.0,
-                t_injection=-(1000.0 - 3.0), J=None)
-    if S:
-        I = rng.uniform(0.5, 1.5, r.shape); chi = rng.uniform(0, np.pi, r.shape)
-        geom['J'] = f32r(np.stack([I, 0.85 * I * np.cos(2 * chi), 0.85 * I * np.sin(2 * chi)])[:S])
-    tree = onp.he_uniform_params(rng, depth, width, 3 + 6 * deg, do_skip=do_skip, dtype=np.float32)
-    for i in range(depth + 1):
-        d = tree['MLP_0']['Dense_%d' % i]
-        d['bias'] = rng.uniform(-0.1, 0.1, d['bias'].shape).astype(np.float32)
-    tree['MLP_0']['Dense_%d' % depth]['bias'] = tree['MLP_0']['Dense_%d' % depth]['bias'] + 9.0
-    ks, bs = ot.tree_to_lists(tree)
-    hp = dict(GM_c3=onp.GM_C3_SGRA_HR, scale=8.0, rmin=2.0, rmax=8.0, z_width=4.0, posenc_deg=deg, net_depth=depth, do_skip=do_skip)
-    shape = (B, S, H, Wd) if S else (B, H, Wd)
-    tg = [torch.tensor(rng.uniform(0, 1e-2, shape)), torch.tensor(rng.uniform(0.5, 2.0, shape)), torch.zeros(shape, dtype=torch.float64)]
-    return ks, bs, geom, hp, torch.tensor(np.linspace(0.1, 0.7, B)), tg
-
-
 def identity_check(ks, bs, geom, hp, tf, tg, scale, dt):
     l0, i0, g0 = ot.CpuTrainer(ks, bs, geom, hp).loss_and_grad(tf, *tg, scale, dt)
     g0 = torch.cat([g.reshape(-1) for g in g0]).numpy()
@@ -180,19 +140,9 @@ def test_recipe_selection_names_every_path():
 # --------------------------------------------------------------------------------------------------------------------------
 # mutants: distances on the GPU tests' problems
 # --------------------------------------------------------------------------------------------------------------------------
-def gpu_problem_from_random(width, depth, S, deg):
-    """test_gpu_bf16_faithful's random problems (= test_gpu_backward.random_problem) in the emulator's terms."""
-    from test_gpu_backward import random_problem, oracle_trainer
-    prob = random_problem(width, depth, S, deg)
-    tr, t = oracle_trainer(prob['g'])
-    tg = [t(prob[k]) for k in ('target', 'sigma', 'offset')]
-    return tr.k, tr.b, tr.geom, tr.hp, t(prob['t_frames']), tg
-
-
 def gpu_cases(golden):
     """(name, bound class, posenc degree, emulator arguments, recipe) of the goldens and the random / general-path problems of
     test_gpu_bf16_faithful (its fused 4x128 and config 2 / 5 cases check their mutants themselves: check_case(mutant_cls=...))."""
-    from test_gpu_bf16_faithful import RANDOM_SHAPES, GENERAL_SHAPES, expected_recipe, kernel_width, problem_class
     for tag in PRED:
         g = golden('g5_predict_' + tag)
         for dt in ('full', 'lc'):
@@ -200,16 +150,15 @@ def gpu_cases(golden):
             yield ('g5_%s %s' % (tag, dt), 'golden', hp['posenc_deg'], (ks, bs, geom, hp, tf, tg, scale, dt),
                    expected_recipe(hp['net_depth'], kernel_width(int(g['hparams'][6])), False))
     for (w, d, S, deg) in RANDOM_SHAPES + GENERAL_SHAPES:
-        ks, bs, geom, hp, tf, tg = gpu_problem_from_random(w, d, S, deg)
+        ks, bs, geom, hp, tf, tg = random_problem_emulator_args(w, d, S, deg)
         yield ('%dx%d S%d deg%d' % (d, w, S, deg), problem_class(d, w), deg, (ks, bs, geom, hp, tf, tg, 1.0, 'full'),
                expected_recipe(d, kernel_width(w), w > 256 or deg > 4))
 
 
 def test_mutants_are_visible_to_the_gpu_bounds(golden):
-    """On every golden and random / general-path problem of the GPU tests the mutants test_gpu_bf16_faithful.required_mutants names
+    """On every golden and random / general-path problem of the GPU tests the mutants mlp_bounds.required_mutants names
     move the problem by >= 5x that case's GPU bound in at least one bounded figure (gradient L2, one tensor, images); every
     distance is printed.  (bias_scale and dout_unrounded are required on the goldens only: see test_gpu_bf16_faithful.)"""
-    from test_gpu_bf16_faithful import bounds, mutant_ratios, check_mutants
     for name, cls, deg, (ks, bs, geom, hp, tf, tg, scale, dt), recipe in gpu_cases(golden):
         variants = ob.Bf16Trainer(ks, bs, geom, hp, recipe).loss_and_grad_variants(tf, *tg, scale, dt)
         cuts = np.cumsum([0] + [t.numel() for k, b in zip(ks, bs) for t in (k, b)])
@@ -225,9 +174,8 @@ def test_accumulation_noise_explains_the_largest_errors():
     of float64 accumulation (accum32 -- same rounding points, another accumulation) moves each of them by >= 1/8 of what the GPU is
     observed at (OBSERVED), and by >= 10x what it moves the quiet 4x256 S0 problem of the same path; its per-layer profile grows
     towards layer 0 as the GPU's does (printed)."""
-    from test_gpu_bf16_faithful import OBSERVED, expected_recipe, kernel_width
     def acc32(w, d, S, deg):
-        ks, bs, geom, hp, tf, tg = gpu_problem_from_random(w, d, S, deg)
+        ks, bs, geom, hp, tf, tg = random_problem_emulator_args(w, d, S, deg)
         recipe = expected_recipe(d, kernel_width(w), w > 256 or deg > 4)
         _, _, g0 = ob.Bf16Trainer(ks, bs, geom, hp, recipe).loss_and_grad(tf, *tg, 1.0, 'full')
         _, _, g1 = ob.Bf16Trainer(ks, bs, geom, hp, recipe, accum32=True).loss_and_grad(tf, *tg, 1.0, 'full')

@@ -7,6 +7,7 @@ import torch
 from oracle import oracle_np as onp
 from oracle import oracle_torch as ot
 from conftest import golden_tree
+from mlp_problems import oracle_trainer
 
 PRED = ['a', 'b', 'c', 'd', 'e', 'f']
 
@@ -84,22 +85,10 @@ def test_predictor_and_render_numpy(golden, tag):
     assert (g['emission'] == 0).mean() > 0.1 and (g['emission'] > 0).mean() > 0.05
 
 
-def _torch_trainer(g, dtype=torch.float64):
-    hp = g['hparams']
-    ks, bs = ot.tree_to_lists(golden_tree(g), dtype)
-    t = lambda x: torch.tensor(x, dtype=dtype)
-    geom = dict(coords=t(g['coords']), Omega=t(g['Omega']), t_geos=t(g['t_geos']), g=t(g['g']), dtau=t(g['dtau']),
-                Sigma=t(g['Sigma']), J=(t(g['J']) if g['J'].ndim else None), t_start_obs=float(g['t_start_obs']),
-                t_injection=float(g['t_injection']))
-    hpd = dict(GM_c3=onp.GM_C3_SGRA_HR, scale=hp[0], rmin=hp[1], rmax=hp[2], z_width=hp[3], posenc_deg=int(hp[4]),
-               net_depth=int(hp[5]))
-    return ot.CpuTrainer(ks, bs, geom, hpd), t
-
-
 @pytest.mark.parametrize('tag', PRED)
 def test_predictor_and_gradient_torch(golden, tag):
     g = golden('g5_predict_' + tag)
-    tr, t = _torch_trainer(g)
+    tr, t = oracle_trainer(g)
     S = g['J'].shape[0] if g['J'].ndim else None
     b = len(g['t_frames'])
     shape = (b, S) + g['coords'].shape[1:3] if S else (b,) + g['coords'].shape[1:3]

@@ -65,7 +65,7 @@ def test_eht_split_rule_gives_each_case_its_intended_RS():
 # ---------------------------------------------------------------------------------------------------------------
 # 1. references against each other, scipy and the goldens
 # ---------------------------------------------------------------------------------------------------------------
-def _autograd_eht(images, A, target, sigma, scale, dtype):          # tests/test_gpu_eht.py::_ref_loss
+def _autograd_eht(images, A, target, sigma, scale, dtype):          # tests/eht_uv_cases.py::dense_ref_loss
     img = torch.tensor(images, dtype=torch.float64, requires_grad=True)
     At, tg, sg = torch.tensor(A).to(torch.complex128), torch.tensor(target), torch.tensor(sigma)
     vec = img.reshape(img.shape[0], -1, 1).to(torch.complex128)

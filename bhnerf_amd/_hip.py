@@ -22,7 +22,7 @@ BHN_F32, BHN_BF16, BHN_BF16_T8 = 0, 1, 2
 BHN_T8_CALIBRATE = 0x100
 BHN_CLK_FWD, BHN_CLK_FWD_TRAIN, BHN_CLK_CHAIN, BHN_CLK_DW, BHN_CLK_SLOTS = 0, 1, 2, 3, 4      # kernel slots of bhn_frames.clock_probe
 BHN_TAPE_INFO_N = 8
-TAPE_FLAGS = {'drop_h1': 1, 'drop_ga': 2, 'ga0_chain': 4, 'fused128': 8, 'drop_hd': 16, 'lbits': 32, 'general': 64}     # lbits: never set by this library
+TAPE_FLAGS = {'drop_h1': 1, 'drop_ga': 2, 'ga0_chain': 4, 'fused128': 8, 'drop_hd': 16, 'lbits': 32, 'general': 64}     # lbits: reserved, never set
 MODES = {'f32': BHN_F32, 'fp32': BHN_F32, 'float32': BHN_F32, 'bf16': BHN_BF16, 'bfloat16': BHN_BF16,
          'bf16_t8': BHN_BF16_T8}            # bf16 arithmetic, 8-bit (e4m3) backward tape: include/bhnerf_hip.h
 

@@ -38,9 +38,8 @@ struct TapeLayout {
     // h = relu(a) = relu'(a) a and a = K^T h_{depth-1} + b give  dW_out[f] = sum_k K[k][f] G[k][f] + b[f] g[f]  with G, g the
     // (un-folded) weight and bias gradients of layer depth-1 (fused_bwd128.hip: reduce128_kernel).
     int drop_hd;
-    // generic bf16 path (round 5, never set: tape_layout): the dW job of layer depth-1 reads the relu-bit words instead of the h_depth
-    // tiles and makes the output layer's row at its flush (dw_body2 LBITS)
-    int lbits;
+    // reserved, always 0, read by nothing: it keeps the kernel-argument offsets of every member behind it (tools/README.md)
+    int reserved0;
     long long maskd_off, scratch_off;          // scratch: [5][128] f32 partial sums of that product (per input tile)
 };
 

@@ -1217,18 +1217,13 @@ DEVI void dw_body(const BwdArgs &A, int job, char *smem) {
 // layer depth-1 (LAST) makes the output layer's row and bias with v_dot2c / adds from the h_depth fragments and the f32
 // dout it already holds (no dout tile on the tape, no 1-row MFMAs, 32 accumulator registers fewer).
 // ---------------------------------------------------------------------------------------------
-// LBITS (round 5, TapeLayout::lbits): the LAST job takes relu'(a_{depth-1}) from the relu-bit words the forward records anyway
-// (1 KiB per group instead of the MT h_depth tiles: 16) and does not make the output layer's row from h_depth at all -- at the
-// flush it forms  sum_k K[k][f] G[k][f] + b[f] g[f]  from its own (un-folded) accumulators, which IS that row because
-// h_depth = relu(a) = relu'(a) a and a = K^T h_{depth-1} + b (bwd_common.h, drop_hd).
-template <int W, class Pol, int JT, bool LAST = false, bool OUTENC = false, bool LBITS = false>     // OUTENC: the output layer riding on LAST takes concat[h, enc]
+template <int W, class Pol, int JT, bool LAST = false, bool OUTENC = false>     // OUTENC: the output layer riding on LAST takes concat[h, enc]
 DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     using BG = BwdGeom<W, Pol>;
     using frag = typename Pol::frag;
     static_assert(Pol::ELEM_BYTES == 2 && JT != JT_OUT && JT != JT_OUTSKIP, "bf16 jobs of layers 0 .. depth-1");
     static_assert(!LAST || JT == JT_HIDDEN || JT == JT_SKIP, "LAST: hidden / skip job");
     static_assert(!OUTENC || LAST, "OUTENC: a LAST job");
-    static_assert(!LBITS || (LAST && !Pol::TAPE8 && JT == JT_HIDDEN), "LBITS: the bf16 LAST job of a plain hidden layer");
     static_assert(BG::NBUF == 4, "ring of four group buffers");
     constexpr int MT = BG::MT, TB = BG::TILE_BYTES, TT = BG::TAPE_TILE;
     constexpr bool T8 = Pol::TAPE8;                                    // 8-bit h / gA tape tiles (tr8_read / tr8_widen)
@@ -1267,9 +1262,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     const int nwg = A.wg_begin[job + 1] - A.wg_begin[job];
     const int kb = blockIdx.x - A.wg_begin[job];
     const long long q0 = uniform64(A.t.NQ * kb / nwg), q1 = uniform64(A.t.NQ * (kb + 1) / nwg);
-    constexpr int MWB = ((MT + 1) / 2) * 256;                           // bytes of one layer's relu-bit words of a group
-    const char *srcA = LBITS ? A.tape + A.t.mask_off + (long long)(A.f.depth - 1) * MWB
-                             : LAST ? A.tape + A.t.h_off[job + 1] : A.tape + A.t.ga_off[job];
+    const char *srcA = LAST ? A.tape + A.t.h_off[job + 1] : A.tape + A.t.ga_off[job];
     const char *srcD = A.tape + A.t.dout_off;
     const char *srcH = has_h ? A.tape + A.t.h_off[job] : nullptr;
     const char *srcE = A.tape + (make_h ? A.t.encp_off : A.t.enc_off);
@@ -1329,15 +1322,6 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
         const int n = nbase + ni;
         boff[ni] = has_h ? OFF_H + (n < nH ? n : 0) * (F8 ? TT : TB) : OFF_E;        // a column share that ends early repeats tile 0 (dropped at the flush)
     }
-    // LBITS: where this lane's feature (row lane & 31 of A tile T) sits in the forward's relu-bit words
-    int lb_word[MPW];
-    unsigned lb_pos[MPW];
-#pragma unroll
-    for (int mi = 0; mi < MPW; ++mi) {
-        const int T = wr * MPW + mi, i = lane & 31, hf = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3);
-        lb_word[mi] = (T >> 1) * 64 + 32 * hf + 4 * (lane >> 5);
-        lb_pos[mi] = 16u * (T & 1) + ((r & 1) ? 8u + (r >> 1) : (unsigned)(r >> 1));
-    }
     const bool bias_rows = wc == 0;                                    // this wave sums the bias column of its A tiles
     const bool out_bias_wave = LAST && wr == 0 && wc == 0;             // ... and this one the output layer's bias
     f32x16 acc[MPW][NPW], acc_e[ME];
@@ -1377,19 +1361,6 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
                         const Raw8 raw = tr8_read(gp + (wr * MPW) * TT, s2, tr8);
                         st.af[s2][0] = __builtin_bit_cast(frag, (u32x4){raw.lo[0], raw.lo[1], raw.hi[0], raw.hi[1]});
                     }
-                } else if constexpr (LBITS) {
-                    // the lane's feature i of A tile T was accumulator element r of lane half hf in the forward: bit `lb_pos[mi]` of
-                    // the word [T >> 1][point + 32 hf]; the lane's eight points of k-step s2 are two runs of four words
-                    const unsigned *wp = reinterpret_cast<const unsigned *>(gp) + lb_word[mi] + 16 * s2;
-                    const u32x4 wa = *reinterpret_cast<const u32x4 *>(wp), wb = *reinterpret_cast<const u32x4 *>(wp + 8);
-                    u32x4 on;
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) {
-                        const unsigned we = d < 2 ? wa[2 * d] : wb[2 * d - 4], wo = d < 2 ? wa[2 * d + 1] : wb[2 * d - 3];
-                        const unsigned lo = (unsigned)__builtin_amdgcn_sbfe((int)we, lb_pos[mi], 1u), hi = (unsigned)__builtin_amdgcn_sbfe((int)wo, lb_pos[mi], 1u);
-                        on[d] = (lo & 0xffffu) | (hi & 0xffff0000u);
-                    }
-                    st.af[s2][mi] = __builtin_bit_cast(frag, on);
                 } else st.af[s2][mi] = tr_frag(gp + (wr * MPW + mi) * TB, s2, trl);
             }
             if constexpr (LAST) {
@@ -1473,7 +1444,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
             const u32x4 raw = __builtin_bit_cast(u32x4, rawf);
             u32x4 ga;
             float o = 0.f;
-            const bool my_row = !LBITS && (mi % WCC) == wc;        // (scalar) this wave makes the output layer's row for this A tile
+            const bool my_row = (mi % WCC) == wc;                  // (scalar) this wave makes the output layer's row for this A tile
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const f32x2 dd = {i < 2 ? da[2 * i] : db[2 * i - 4], i < 2 ? da[2 * i + 1] : db[2 * i - 3]};
@@ -1491,12 +1462,9 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
                 // so the A operand is only (h != 0) bf16(dout_p) -- three VALU per two points instead of seven (this job was
                 // VALU-bound: 237 VALU against 20 MFMAs per group) -- and the rows of dW_{depth-1} (and its bias) are scaled
                 // by W_out[f] in f32 at the flush, which is also closer to the exact product than rounding it per point.
-                if constexpr (LBITS) ga[i] = __builtin_bit_cast(unsigned, dpk) & raw[i];      // (a_load left the relu masks of the pair here)
-                else {
-                    const unsigned sgn = raw[i] + 0x7fff7fffu;          // bf16 h >= 0: sets the half's sign bit iff h != 0, no carry
-                    const i16x2 on = __builtin_bit_cast(i16x2, sgn) >> (i16x2){15, 15};
-                    ga[i] = __builtin_bit_cast(unsigned, dpk) & __builtin_bit_cast(unsigned, on);
-                }
+                const unsigned sgn = raw[i] + 0x7fff7fffu;              // bf16 h >= 0: sets the half's sign bit iff h != 0, no carry
+                const i16x2 on = __builtin_bit_cast(i16x2, sgn) >> (i16x2){15, 15};
+                ga[i] = __builtin_bit_cast(unsigned, dpk) & __builtin_bit_cast(unsigned, on);
             }
             st.af[s2][mi] = __builtin_bit_cast(frag, ga);
             if (live && my_row) orow[mi / WCC] += o;
@@ -1587,11 +1555,11 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     };
 
     // ---- the stream: pieces (1 KiB = one wave-wide DMA) this job needs: [A tiles][h tiles][enc tile][f32 dout piece]
-    constexpr int PA = LBITS ? 1 : MT * TT / 1024, PH = (has_h && !make_h) ? MT * TT / 1024 : 0,
+    constexpr int PA = MT * TT / 1024, PH = (has_h && !make_h) ? MT * TT / 1024 : 0,
                   PE = (JT == JT_FIRST || JT == JT_SKIP || make_h || OUTENC) ? TB / 1024 : 0, PD = LAST ? 1 : 0;
     using Stream = TapeStream<Pol::NWAVES, PA, PH, PE, PD, OFF_H, OFF_E, OFF_D32>;
     constexpr int PPW = Stream::PPW;
-    const Stream stream(srcA, LBITS ? (long long)A.f.depth * MWB : (long long)MT * TT, srcH, (long long)MT * TT, srcE, TB, srcD, A.t.dout_stride, wv);
+    const Stream stream(srcA, (long long)MT * TT, srcH, (long long)MT * TT, srcE, TB, srcD, A.t.dout_stride, wv);
     auto issue = [&](long long q, char *buf) { stream.issue(q < q1 ? q : q1 - 1, buf); };
     __syncthreads();                                            // W_0 / b_0 visible (HIDDEN1)
     if (q0 < q1) {
@@ -1693,70 +1661,13 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
         }
         if (enc_extra && (mi % WCC) == wc && m < MT) flush_tile(m, nH, acc_e[mi / WCC], true);
         flush_column0(m, nB, LAST ? bsum[mi] * wout_r[mi] : bsum[mi], bias_rows && m < MT);
-        if constexpr (LAST && !LBITS) {
+        if constexpr (LAST) {
             // the output layer's row: slab row MT, tile m, row 0, column f = lane & 31 (where reduce_kernel reads dW_out[32 m + f])
             float v = orow[mi / WCC] + __shfl_xor(orow[mi / WCC], 32, 64);
             if ((mi % WCC) == wc && m < MT && lane < 32) {
                 float *dst = slab + (long long)(MT * BG::NTMAX + m) * 1024 + lane * 4;
                 if (A.accumulate) v += *dst;
                 *dst = v;
-            }
-        }
-    }
-    if constexpr (LBITS) {
-        // The output layer's row from this workgroup's own sums (see the template comment): every lane weights its accumulator
-        // elements (row f = output unit of layer depth-1, column k = its input unit) with the bf16 weight K[k][f] the forward
-        // used, the 32 columns of a row meet through LDS, the bias term b[f] g[f] joins on wave column 0, and wave column wc leaves
-        // its share in float wc of the row's slot (slab row MT, tile m, float4 of lane f): reduce_kernel adds the four floats.
-        static_assert(WCC <= 8, "one float of the slot (two float4: lanes f and f + 32) per wave column");
-        using PKf = Pack<W, Pol>;
-        __syncthreads();                                            // every wave is out of the group ring
-        float *stg = reinterpret_cast<float *>(smem) + wv * (MPW * 32 * 33);
-        const int col = lane & 31, hh = lane >> 5;
-        if (works) {
-#pragma unroll
-            for (int mi = 0; mi < MPW; ++mi) {
-                const int m = wr * MPW + mi;
-                const char *wimg = A.f.packed + A.f.fwd_off + (size_t)(1 + (job - 1) * MT + (m < MT ? m : 0)) * PKf::CHUNK_BYTES;
-                float sr[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sr[r] = 0.f;
-#pragma unroll
-                for (int ni = 0; ni < NPW; ++ni) {
-                    const int n = nbase + ni, k = 32 * n + col;
-                    if (n < nBr) {
-                        const int fr = k >> 4, ph = k & 15, h2 = (ph >> 2) & 1, jj = (ph & 3) + 4 * (ph >> 3);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int fl = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                            const float wq = (float)reinterpret_cast<const __bf16 *>(wimg + fr * Pol::FRAG_BYTES + (fl + 32 * h2) * 16)[jj];
-                            sr[r] += wq * acc[mi][ni][r];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) stg[(mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh) * 33 + col] = sr[r];
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (the wave reads back what its own lanes wrote)
-#pragma unroll
-        for (int mi = 0; mi < MPW; ++mi) {
-            const int m = wr * MPW + mi;
-            float tot = 0.f;
-            if (works && lane < 32) {
-                for (int c = 0; c < 32; ++c) tot += stg[(mi * 32 + lane) * 33 + c];
-            }
-            const float g = bsum[mi] + __shfl_xor(bsum[mi], 32, 64);           // un-folded bias gradient of feature lane & 31 (wave column 0)
-            if (bias_rows && lane < 32 && m < MT) tot += reinterpret_cast<const float *>(A.f.packed + A.f.bias_off)[job * W + 32 * m + lane] * g;
-            if (works && lane < 32 && m < MT) {
-                float *dst = slab + (long long)(MT * BG::NTMAX + m) * 1024 + (lane + 32 * (wc >> 2)) * 4;
-                if (A.accumulate) tot += dst[wc & 3];
-                dst[wc & 3] = tot;
-                if (wc == 0) {                  // the slots no wave column owns, or whose column has no B tiles (narrow networks)
-#pragma unroll
-                    for (int e = 1; e < (WCC > 4 ? 8 : 4); ++e)
-                        if (e >= WCC || e * NPW >= nBr) slab[(long long)(MT * BG::NTMAX + m) * 1024 + (lane + 32 * (e >> 2)) * 4 + (e & 3)] = 0.f;
-                }
             }
         }
     }
@@ -1790,21 +1701,21 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
         if (job == depth) {                                               // (depth < 3 only)
             if (out_skip) dw_body<W, Pol, JT_OUTSKIP>(A, job, smem);
             else dw_body<W, Pol, JT_OUT>(A, job, smem);
-        } else if (job == 0) dw_body2<W, Pol, JT_FIRST>(A, job, smem); else if (job == depth - 1 && A.t.drop_ga) {
+        } else if (job == depth - 1 && A.t.drop_ga) {
+            // (this arm stands in front of the layer-0 job on purpose: the bodies share one register allocation, and with job 0
+            // tested first the width-256 kernel is 1.4-1.9 % slower -- tools/README.md, profiles/dw_without_lbits_ab.txt)
             if constexpr (Pol::TAPE8) {           // (no skip into the output layer: checked by the host)
                 if ((A.f.skip_mask >> job) & 1) dw_body2<W, Pol, JT_SKIP, true>(A, job, smem);
                 else dw_body2<W, Pol, JT_HIDDEN, true>(A, job, smem);
             } else if ((A.f.skip_mask >> job) & 1) {
                 if (out_skip) dw_body2<W, Pol, JT_SKIP, true, true>(A, job, smem);
                 else dw_body2<W, Pol, JT_SKIP, true>(A, job, smem);
-            } else if (A.t.lbits) {
-                if (out_skip) dw_body2<W, Pol, JT_HIDDEN, true, true, true>(A, job, smem);
-                else dw_body2<W, Pol, JT_HIDDEN, true, false, true>(A, job, smem);
             } else {
                 if (out_skip) dw_body2<W, Pol, JT_HIDDEN, true, true>(A, job, smem);
                 else dw_body2<W, Pol, JT_HIDDEN, true>(A, job, smem);
             }
-        } else if ((A.f.skip_mask >> job) & 1) dw_body2<W, Pol, JT_SKIP>(A, job, smem);
+        } else if (job == 0) dw_body2<W, Pol, JT_FIRST>(A, job, smem);
+        else if ((A.f.skip_mask >> job) & 1) dw_body2<W, Pol, JT_SKIP>(A, job, smem);
         else if (job == 1 && A.t.drop_h1) dw_body2<W, Pol, JT_HIDDEN1>(A, job, smem);
         else dw_body2<W, Pol, JT_HIDDEN>(A, job, smem);
     } else {
@@ -1909,8 +1820,6 @@ __global__ __launch_bounds__(256) void reduce_kernel(BwdArgs A) {
         else if (from_chain && col == 31) is_bias = true;           // slot 31 of the recorded inputs is 1
     }
     else is_bias = col == 0;
-    float lb_tot = (sum[0] + sum[1]) + (sum[2] + sum[3]);
-    if constexpr (BG::WCC > 4) lb_tot += __shfl_xor(lb_tot, 32, 64);      // (wave columns 4 .. 7: the float4 of lane f + 32)
     if (kin < 0 && !is_bias) return;
     const int outw = out ? 1 : WT;
 #pragma unroll
@@ -1918,9 +1827,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(BwdArgs A) {
         const int r = 4 * g4 + e, row = (r & 3) + 4 * hh + 8 * (r >> 2);
         const int o = out ? 0 : (Pol::TAPE8 && !from_chain) ? t8_feature(mi, row) : 32 * mi + row;      // (the chain's dW_0 tiles: bf16 staging, natural rows)
         if (out ? row != 0 : o >= WT) continue;
-        float val = sum[e];
-        if (rides && A.t.lbits && n < nH) val = lb_tot;                 // the shares of the dW job's wave columns (dw_body2 LBITS)
-        A.dparams[is_bias ? A.bias_off[l] + o : A.kernel_off[l] + kin * outw + o] = val;
+        A.dparams[is_bias ? A.bias_off[l] + o : A.kernel_off[l] + kin * outw + o] = sum[e];
     }
 }
 
@@ -2060,13 +1967,13 @@ static void tape_traffic(const MlpShape &s, const TapeLayout &t, int64_t *o) {
             if (l == 0) { if (!t.ga0_chain) dr += MT * TT + TB; continue; }
             if (l == depth) { dr += t.dout_stride + MT * TT + (s.skip_in[l] ? TB : 0); continue; }
             const bool last = l == depth - 1 && t.drop_ga;
-            dr += last ? (t.lbits ? MW * 256 : MT * TT) + 1024 : MT * TT;            // A: gA_l, or h_depth (its relu bits) + the KiB that starts with dout
+            dr += last ? MT * TT + 1024 : MT * TT;                                   // A: gA_l, or h_depth + the KiB that starts with dout
             dr += (l == 1 && t.drop_h1) ? TB : MT * TT;                              // B: h_l (layer 1: the encoded inputs it is recomputed from)
             if (s.skip_in[l] || (last && s.skip_in[depth])) dr += TB;
         }
     }
     o[0] = fw; o[1] = cw; o[2] = cr; o[3] = dr;
-    o[4] = (t.drop_h1 ? 1 : 0) | (t.drop_ga ? 2 : 0) | (t.ga0_chain ? 4 : 0) | (t.fused128 ? 8 : 0) | (t.drop_hd ? 16 : 0) | (t.lbits ? 32 : 0);
+    o[4] = (t.drop_h1 ? 1 : 0) | (t.drop_ga ? 2 : 0) | (t.ga0_chain ? 4 : 0) | (t.fused128 ? 8 : 0) | (t.drop_hd ? 16 : 0);
 }
 
 // ---- the plan: what the backward of one network runs, from its shape and the ray set's size.  Arithmetic only, no HIP call:

@@ -309,7 +309,7 @@ enum { BHN_TAPE_DROP_H1 = 1,     /* h_1 is recomputed from the encoded inputs   
        BHN_TAPE_GA0_CHAIN = 4,   /* dW_0 is accumulated inside the delta chain (no layer-0 dW job, no gA_0)      */
        BHN_TAPE_FUSED128 = 8,    /* fused delta chain + weight gradients (width 128, depth 4, bf16)              */
        BHN_TAPE_DROP_HD = 16,    /* h_depth is not recorded (its relu bits are)                                  */
-       BHN_TAPE_LBITS = 32,      /* never set by this library (an earlier dW job of layer depth-1 on relu bits)  */
+       BHN_TAPE_LBITS = 32,      /* reserved: never set (a removed dW job of layer depth-1 on relu bits had it)  */
        BHN_TAPE_GENERAL = 64 };  /* general path (posenc_deg > 4 or net_width > 256): its own tape, in chunks    */
 BHN_API int bhn_tape_info(const bhn_model *m, int32_t mode, int64_t groups_per_frame, int64_t *info, int32_t n_info);
 

@@ -62,6 +62,10 @@ RANDOM_SHAPES = [(256, 4, 0, 3), (128, 4, 3, 3), (64, 8, 2, 3), (32, 6, 0, 3), (
                  (32, 3, 0, 3), (64, 2, 3, 2), (256, 5, 0, 3), (256, 8, 0, 3), (256, 8, 3, 3), (64, 4, 1, 3), (256, 6, 1, 2),
                  (256, 2, 0, 3)]           # test_random_problem_f32_and_bf16's 21 shapes + 2x256 (no W_out fold at the ga0_chain width)
 GENERAL_SHAPES = [(128, 4, 3, 5), (512, 4, 0, 3), (300, 3, 1, 6), (64, 2, 0, 7), (384, 8, 2, 4), (512, 8, 0, 8), (40, 5, 3, 10)]
+# (depth, width) of the forms of the bf16 dW kernel's layer depth-1 job (fused_bwd.hip dw_kernel) that the shapes above leave out at a
+# kernel width.  With do_skip the form follows from the depth: 3 = skip-concat into layer 2 and into the output layer, 4 = into layer
+# 3, 5 = into the output layer only, 6 = neither.  RANDOM_SHAPES has depth 3 at width 32 only and no depth 5 (or 7) at width 32.
+LAST_JOB_SHAPES = [(3, 64), (3, 128), (3, 256), (5, 32)]
 
 # ---- bounds against the emulator (the f64 bounds of the same cases: 1e-2 images, 6e-2 / 3e-2 / 2e-2 gradient)
 # Observed on the MI355X, per case (image error / maximum, emission relative L2, loss relative error, gradient relative L2 = the worst
@@ -98,6 +102,10 @@ OBSERVED = {
     '8x384 S2 deg4':               (0.00042, 0.0004, 2.3e-06, 0.0016, 0.0055),
     '8x512 S0 deg8':               (0.00076, 0.00089, 1.3e-05, 0.0031, 0.014),
     '5x40 S3 deg10':               (0.00076, 0.00097, 9e-05, 0.00049, 0.0018),
+    '3x64 S2 ragged':              (5.4e-05, 3.8e-05, 2.9e-06, 1.1e-05, 1.4e-05),
+    '3x128 S2 ragged':             (2.1e-05, 6e-05, 3.2e-06, 1.2e-05, 9.2e-05),
+    '3x256 S2 ragged':             (5.6e-05, 6.3e-05, 2.6e-06, 0.00036, 0.00067),
+    '5x32 S2 ragged':              (3.8e-05, 5.7e-05, 6.3e-07, 0.00029, 0.0012),
     'g5_a full':                   (3.7e-07, 3.2e-07, 2.4e-07, 5.1e-08, 2.5e-07),
     'g5_a lc':                     (3.7e-07, 3.2e-07, 2.8e-07, 5.5e-08, 2.7e-07),
     'g5_b full':                   (3.9e-07, 3.7e-07, 1.1e-07, 1.1e-07, 2.8e-06),

@@ -28,8 +28,10 @@ import pytest
 import torch
 
 from conftest import golden_tree
+from buffer_contract_cases import RAY_SETS
+from frame_chunk_cases import build_problem
 from gpu_support import chi2_step, dev, device_setup, problem_of, ray_args  # noqa: F401
-from mlp_bounds import (FIELDS, GENERAL_SHAPES, RANDOM_SHAPES, bounds, check_mutants, expected_recipe, kernel_width, l2err as l2, maxerr as mx,
+from mlp_bounds import (FIELDS, GENERAL_SHAPES, LAST_JOB_SHAPES, RANDOM_SHAPES, bounds, check_mutants, expected_recipe, kernel_width, l2err as l2, maxerr as mx,
                         mutant_ratios, problem_class)
 from mlp_problems import (CONFIG2, CONFIG2_DOMAINS, config_problem, f32r, oracle_inputs_of, random_problem_inputs, ray_subset,
                           rays_through_domain, stokes_domain, stokes_problem, t64, targets, tensor_cuts, without_samples)
@@ -73,7 +75,9 @@ def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, ta
     gref = ob.flat(grads_ref)
     img_ref = img_ref.numpy()
     # (1) the chi^2 step through the reference-shaped API
-    sq = (lambda v: v[:, 0]) if S == 1 else (lambda v: v)
+    def sq(v):          # the reference-shaped API squeezes singleton axes: the plane axis of S = 1, a ray grid of one row or column
+        v = v[:, 0] if S == 1 else v
+        return v.reshape(v.shape[:-2] + tuple(n for n in v.shape[-2:] if n != 1)) if dt == 'full' else v
     loss, images, gdev = chi2_step(pred, flat, ray_args(g), t_frames, sq(target), sq(sigma), sq(offset), loss_scale, dt)
     img = images.cpu().numpy().reshape(img_ref.shape)
     gdev = gdev.astype(np.float64)
@@ -144,6 +148,28 @@ def test_random_problems_against_emulator(dev, width, depth, S, deg):
     check_and_adjudicate(name, problem_class(depth, width), deg, lambda drop: check_case(
         name, dev, tree, geo, prob['t_frames'], prob['t_inj'], tuple(prob['g']['hparams'][:4]), depth, width, deg, prob['target'],
         prob['sigma'], prob['offset'], general=general, compact=True, drop=drop))
+
+
+def last_job_case(depth, width):
+    """(name, check_case's arguments from `tree` to `offset`) of a LAST_JOB_SHAPES problem: buffer_contract_cases' ragged ray set
+    (37 rays x 50 samples = 58 groups, the last one 26 points), three frames, S = 2, posenc degree 3."""
+    H, Wd, G, dom = RAY_SETS['ragged']
+    g = build_problem(depth, width, 'bf16', 2, 3, H, Wd, G, dom, 3)['g']
+    geo = {k: g[k] for k in ('coords', 'Omega', 't_geos', 'g', 'dtau', 'Sigma', 'J')}
+    rng = np.random.default_rng(500 + 7 * width + depth)
+    tshape = (3, 2, H, Wd)
+    target = rng.uniform(0, 1e-3, tshape); sigma = rng.uniform(0.5, 2.0, tshape); offset = np.zeros(tshape)
+    return '%dx%d S2 ragged' % (depth, width), (golden_tree(g), geo, g['t_frames'], float(g['t_injection']), dom, depth, width, 3, target,
+                                                 sigma, offset)
+
+
+@pytest.mark.parametrize('depth,width', LAST_JOB_SHAPES)
+def test_last_job_forms_against_emulator(dev, depth, width):
+    """The forms of the dW kernel's layer depth-1 job (dw_body2 LAST: gA_{depth-1} rebuilt from h_depth, the output layer's row) that
+    no other case runs at their kernel width -- depth 3 (skip-concat into layer 2 and into the output layer) at widths 64, 128, 256 and
+    depth 5 (into the output layer only) at width 32 -- on a dense ragged ray set.  check_case asserts the path: drop_ga, not fused128."""
+    name, args = last_job_case(depth, width)
+    check_and_adjudicate(name, 'random', 3, lambda drop: check_case(name, dev, *args, compact=False, drop=drop))
 
 
 @pytest.mark.parametrize('dt', ['full', 'lc'])

@@ -1,5 +1,5 @@
 """ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
-(include/bhnerf_eht.h) and libbhnerf_grf.so (include/bhnerf_grf.h).
+(include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h) and libbhnerf_eql.so (include/bhnerf_eql.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -129,12 +129,20 @@ GRF_SIGNATURES = {
     'bhn_grf_transport': (C.c_int, [_GG, _P, _P, _P, _P, _D, _D, _D, _P, _P]),
 }
 
-# library name -> (path, signature table, last-error symbol, what bhn_version() must return): the four libraries `make` builds
+# libbhnerf_eql.so (include/bhnerf_eql.h): the equatorial crossings of the image-plane rays, the fifth library
+EQL_LIB_PATH = os.path.join(CSRC, 'libbhnerf_eql.so')
+EQL_SIGNATURES = {
+    'bhn_eql_last_error': (C.c_char_p, []),
+    'bhn_eql_crossings': (C.c_int, [_P, _P, _I64, _D, _D, _D, _D, _D, _D, _I32, _I32, _P, _P, _P, _P]),
+}
+
+# library name -> (path, signature table, last-error symbol, what bhn_version() must return): the five libraries `make` builds
 LIBRARIES = {
     'libbhnerf_hip': (LIB_PATH, SIGNATURES, 'bhn_last_error', ABI_VERSION),
     'libbhnerf_kerr': (KERR_LIB_PATH, KERR_SIGNATURES, 'bhn_kerr_last_error', None),
     'libbhnerf_eht': (EHT_LIB_PATH, EHT_SIGNATURES, 'bhn_eht_last_error', None),
     'libbhnerf_grf': (GRF_LIB_PATH, GRF_SIGNATURES, 'bhn_grf_last_error', None),
+    'libbhnerf_eql': (EQL_LIB_PATH, EQL_SIGNATURES, 'bhn_eql_last_error', None),
 }
 _loaded = {}                 # path -> handle
 
@@ -204,6 +212,11 @@ def grf_lib():
     return _lib('libbhnerf_grf')
 
 
+def eql_lib():
+    """The loaded equatorial-crossings library."""
+    return _lib('libbhnerf_eql')
+
+
 def check(rc):
     _check('libbhnerf_hip', rc)
 
@@ -218,6 +231,10 @@ def eht_check(rc):
 
 def grf_check(rc):
     _check('libbhnerf_grf', rc)
+
+
+def eql_check(rc):
+    _check('libbhnerf_eql', rc)
 
 
 def stream_ptr(device=None):

@@ -154,51 +154,89 @@ KT_HD void kt_store(double *dst, int64_t stride, double mino, const KtState &y) 
     dst[4 * stride] = y.t; dst[5 * stride] = y.vr; dst[6 * stride] = y.vth;
 }
 
-// One ray, both passes.  samples (7, n, ngeo) or NULL with ngeo = 0, end (7, n), status (n); this call writes column i of each.
-KT_HD void kt_trace_ray(const KtParams &p, double alpha, double beta, int64_t i, int64_t n, double *samples, double *end,
-                        int32_t *status) {
+// Constants of the ray that arrives at (alpha, beta) on the observer's screen.
+KT_HD KtRay kt_make_ray(const KtParams &p, double alpha, double beta) {
     KtRay k;
     k.a = p.a; k.M = p.M; k.a2 = p.a * p.a;
     k.lam = -alpha * p.sin_i;
     k.eta = (alpha * alpha - k.a2) * (p.cos_i * p.cos_i) + beta * beta;
     k.lam2 = k.lam * k.lam;
     k.q = k.eta + (k.lam - k.a) * (k.lam - k.a);
-    const double vth_scale = 1e-2 * (k.eta + k.a2 + k.lam2);
+    return k;
+}
+
+KT_HD double kt_vth_scale(const KtRay &k) { return 1e-2 * (k.eta + k.a2 + k.lam2); }
+
+// geodesics._initial_state: at the observer, inwards and back in time
+KT_HD KtState kt_initial_state(const KtParams &p, const KtRay &k, double beta) {
+    KtState y;
+    y.r = p.distance; y.th = p.inc; y.ph = 0.0; y.t = 0.0;
+    y.vr = -sqrt(kt_clip0(kt_radial_potential(k, y.r)));
+    const double root = sqrt(kt_clip0(kt_angular_potential(k, y.th)));
+    y.vth = -(beta > 0.0 ? root : (beta < 0.0 ? -root : (beta == 0.0 ? 0.0 : beta)));
+    return y;
+}
+
+// One RK4 step of geodesics._integrate from y: the state after it (velocities re-derived from the potentials away from the turning
+// points), with the step length in *dl and the right-hand side at y in *k1 (the Hermite weights of a sample inside the step need
+// both).  Shared by bhn_kerr_trace and bhn_eql_crossings (equatorial.h): whether the step is taken is the caller's rule.
+KT_HD KtState kt_rk4_step(const KtParams &p, const KtRay &k, double vth_scale, const KtState &y, KtState *k1_out, double *dl_out) {
+    double s, c;
+    kt_sincos(y.th, &s, &c);
+    const double sq = (s / 0.25) * (s / 0.25);
+    const double dl = p.h * (1.0 + y.r / p.r_c) / (y.r * y.r) * (sq < 0.05 ? 0.05 : (sq > 1.0 ? 1.0 : sq));
+    const KtState k1 = kt_rhs_sc(k, y, s, c);
+    KtState f = kt_rhs(k, kt_axpy(y, 0.5 * dl, k1));
+    KtState acc = kt_add2(k1, f);
+    f = kt_rhs(k, kt_axpy(y, 0.5 * dl, f));
+    acc = kt_add2(acc, f);
+    f = kt_rhs(k, kt_axpy(y, dl, f));
+    acc = kt_add(acc, f);
+    KtState yn = kt_axpy(y, dl / 6.0, acc);
+    const double Rn = kt_radial_potential(k, yn.r);
+    const double r2 = yn.r * yn.r;
+    if (Rn > 1e-2 * (r2 * r2)) yn.vr = kt_signed_root(yn.vr, Rn);
+    const double Tn = kt_angular_potential(k, yn.th);
+    if (Tn > vth_scale) yn.vth = kt_signed_root(yn.vth, Tn);
+    *k1_out = k1;
+    *dl_out = dl;
+    return yn;
+}
+
+// The cubic Hermite combination of the two ends of a step at w in [0, 1] of it: all six components.
+KT_HD KtState kt_hermite_state(double w, double dl, const KtState &y, const KtState &k1, const KtState &yn, const KtState &fn) {
+    const double w2 = w * w, w3 = w * w * w;
+    const double c0 = 2 * w3 - 3 * w2 + 1, c1 = (w3 - 2 * w2 + w) * dl, c2 = 3 * w2 - 2 * w3, c3 = (w3 - w2) * dl;
+    KtState o;
+    o.r = kt_hermite(c0, c1, c2, c3, y.r, k1.r, yn.r, fn.r);
+    o.th = kt_hermite(c0, c1, c2, c3, y.th, k1.th, yn.th, fn.th);
+    o.ph = kt_hermite(c0, c1, c2, c3, y.ph, k1.ph, yn.ph, fn.ph);
+    o.t = kt_hermite(c0, c1, c2, c3, y.t, k1.t, yn.t, fn.t);
+    o.vr = kt_hermite(c0, c1, c2, c3, y.vr, k1.vr, yn.vr, fn.vr);
+    o.vth = kt_hermite(c0, c1, c2, c3, y.vth, k1.vth, yn.vth, fn.vth);
+    return o;
+}
+
+// One ray, both passes.  samples (7, n, ngeo) or NULL with ngeo = 0, end (7, n), status (n); this call writes column i of each.
+KT_HD void kt_trace_ray(const KtParams &p, double alpha, double beta, int64_t i, int64_t n, double *samples, double *end,
+                        int32_t *status) {
+    const KtRay k = kt_make_ray(p, alpha, beta);
+    const double vth_scale = kt_vth_scale(k);
     const int32_t ngeo = p.ngeo;
     double *const smp = ngeo > 0 ? samples + i * (int64_t)ngeo : nullptr;      // row stride n * ngeo
     const int64_t row = n * (int64_t)ngeo;
     const int passes = ngeo > 0 ? 2 : 1;
     double total = 0.0;
     for (int pass = 0; pass < passes; ++pass) {
-        KtState y;
-        y.r = p.distance; y.th = p.inc; y.ph = 0.0; y.t = 0.0;
-        y.vr = -sqrt(kt_clip0(kt_radial_potential(k, y.r)));                   // inwards, back in time
-        {
-            const double root = sqrt(kt_clip0(kt_angular_potential(k, y.th)));
-            y.vth = -(beta > 0.0 ? root : (beta < 0.0 ? -root : (beta == 0.0 ? 0.0 : beta)));
-        }
+        KtState y = kt_initial_state(p, k, beta);
         double mino = 0.0;
         int32_t nxt = 0, step = 0;
         bool done = false;
         while (step < p.max_steps && !done) {
             ++step;
-            double s, c;
-            kt_sincos(y.th, &s, &c);
-            const double sq = (s / 0.25) * (s / 0.25);
-            const double dl = p.h * (1.0 + y.r / p.r_c) / (y.r * y.r) * (sq < 0.05 ? 0.05 : (sq > 1.0 ? 1.0 : sq));
-            const KtState k1 = kt_rhs_sc(k, y, s, c);
-            KtState f = kt_rhs(k, kt_axpy(y, 0.5 * dl, k1));
-            KtState acc = kt_add2(k1, f);
-            f = kt_rhs(k, kt_axpy(y, 0.5 * dl, f));
-            acc = kt_add2(acc, f);
-            f = kt_rhs(k, kt_axpy(y, dl, f));
-            acc = kt_add(acc, f);
-            KtState yn = kt_axpy(y, dl / 6.0, acc);
-            const double Rn = kt_radial_potential(k, yn.r);
-            const double r2 = yn.r * yn.r;
-            if (Rn > 1e-2 * (r2 * r2)) yn.vr = kt_signed_root(yn.vr, Rn);
-            const double Tn = kt_angular_potential(k, yn.th);
-            if (Tn > vth_scale) yn.vth = kt_signed_root(yn.vth, Tn);
+            KtState k1;
+            double dl;
+            const KtState yn = kt_rk4_step(p, k, vth_scale, y, &k1, &dl);
             const bool captured = !(yn.r > p.r_cap);                           // (also a NaN): the step is not taken
             const double mino_new = mino + dl;
             if (pass == 1 && !captured && nxt < ngeo) {
@@ -207,16 +245,7 @@ KT_HD void kt_trace_ray(const KtParams &p, double alpha, double beta, int64_t i,
                     const KtState fn = kt_rhs(k, yn);
                     const double dlw = dl > 0.0 ? dl : 1.0;
                     do {
-                        const double w = (tgt - mino) / dlw, w2 = w * w, w3 = w * w * w;
-                        const double c0 = 2 * w3 - 3 * w2 + 1, c1 = (w3 - 2 * w2 + w) * dl, c2 = 3 * w2 - 2 * w3, c3 = (w3 - w2) * dl;
-                        KtState o;
-                        o.r = kt_hermite(c0, c1, c2, c3, y.r, k1.r, yn.r, fn.r);
-                        o.th = kt_hermite(c0, c1, c2, c3, y.th, k1.th, yn.th, fn.th);
-                        o.ph = kt_hermite(c0, c1, c2, c3, y.ph, k1.ph, yn.ph, fn.ph);
-                        o.t = kt_hermite(c0, c1, c2, c3, y.t, k1.t, yn.t, fn.t);
-                        o.vr = kt_hermite(c0, c1, c2, c3, y.vr, k1.vr, yn.vr, fn.vr);
-                        o.vth = kt_hermite(c0, c1, c2, c3, y.vth, k1.vth, yn.vth, fn.vth);
-                        kt_store(smp + nxt, row, tgt, o);
+                        kt_store(smp + nxt, row, tgt, kt_hermite_state((tgt - mino) / dlw, dl, y, k1, yn, fn));
                         ++nxt;
                         tgt = ((double)(nxt + 1) / (double)ngeo) * total;
                     } while (nxt < ngeo && tgt <= mino_new);

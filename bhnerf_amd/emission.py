@@ -226,6 +226,29 @@ def generate_tube_xr(resolution, rot_axis, phi_start, phi_end, orbit_radius, std
     return out
 
 
+def equatorial_ring(geos, mbar, backend='numpy', device=None):
+    """Equatorial ring of emission (emission.py:119-141): an array shaped like ``geos.mino`` with 1.0 at the ONE sample of every
+    ray whose Mino time is nearest the ray's ``(mbar+1)``-th meeting with the equatorial plane (``mbar``: order of the photon
+    ring, direct emission = 0) and 0 elsewhere.  ``geos``: a record of ``image_plane_geos`` or of ``ray_geos``.  The crossing's
+    Mino time is ``kgeo.equatorial_lensing.r_equatorial(...)[1]`` as in the reference, for all rays in one call, on the host
+    (``backend='numpy'``) or on the GPU (``'hip'``).  A ray without such a crossing -- it falls into the hole or leaves before --
+    gets all zeros; the reference would fail there (its ``argmin`` over NaNs)."""
+    from . import equatorial_lensing
+    mino = np.asarray(geos.mino, dtype=np.float64)
+    rays = mino.reshape(-1, mino.shape[-1])
+    alpha = np.asarray(geos.alpha, dtype=np.float64).ravel()
+    beta = np.asarray(geos.beta, dtype=np.float64).ravel()
+    if alpha.size != rays.shape[0] or beta.size != rays.shape[0]:
+        raise ValueError('geos.alpha / geos.beta must hold one value per ray of geos.mino')
+    mino_x = equatorial_lensing.r_equatorial(float(geos.spin), float(geos.r_o), float(geos.inc), mbar, alpha, beta,
+                                             backend=backend, device=device)[1]
+    has = np.isfinite(mino_x)
+    nearest = np.abs(rays - np.where(has, mino_x, 0.0)[:, None]).argmin(axis=1)
+    out = np.zeros_like(rays)
+    out[np.nonzero(has)[0], nearest[has]] = 1.0
+    return out.reshape(mino.shape)
+
+
 def propogate_flatspace_emission(emission_0, Omega_3D, t_frames, t_start_obs=None, rot_axis=[0, 0, 1], M=None):
     """3-D movie of an initial emission sheared by the velocity field on its own grid -- no ray tracing, no light
     travel time (emission.py:305-341): warp of the grid points, then trilinear sampling of ``emission_0``."""

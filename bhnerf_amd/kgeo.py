@@ -81,7 +81,8 @@ radiative_transfer = radiative_trasfer
 # ---------------------------------------------------------------------------------------------------------------
 # GR pre-compute on NumPy arrays
 # ---------------------------------------------------------------------------------------------------------------
-from .geodesics import Geodesics, image_plane_geos, kerr_functions  # noqa: E402,F401
+from .geodesics import Geodesics, image_plane_geos, kerr_functions, ray_geos  # noqa: E402,F401
+from . import equatorial_lensing  # noqa: E402,F401  (kgeo.equatorial_lensing.r_equatorial / rho_of_req, as the reference spells them)
 
 
 def _f(geos, name):

@@ -104,33 +104,40 @@ def check_table():
 _REFS = {}
 
 
-def reference(name, recipe=None, drop=None, want_ties=False):
+def reference(name, recipe=None, drop=None, want_ties=False, prob=None, accum32=False):
     """dict(emission (B, H*W*G), images (B, Sx, R), grad: the flat gradient of sum(images * dimg) in flax tree order), float64 arrays --
     `recipe` None: oracle_torch in float64, else oracle_bf16's emulator of that recipe.  `drop` (H, W, G) bool: the problem without those
     ray samples (Doppler weight 0: the ReLU-tie adjudication of test_gpu_frame_chunks).  want_ties: instead the (H, W, G) bool of the
-    ray samples that reach the image and have a ReLU tie on the reference's own forward."""
+    ray samples that reach the image and have a ReLU tie on the reference's own forward.  `prob`: the problem of another case table
+    (general_path_cases; `name` must not be one of CASES), which may hold do_skip = False; accum32: the emulator accumulating in float32."""
     from conftest import relu_tie_count
     from frame_chunk_cases import T_INJ
     from mlp_problems import oracle_inputs, t64, without_samples
     from oracle import oracle_bf16 as ob, oracle_torch as ot
-    key = (name, recipe, drop is not None, want_ties)
+    key = (name, recipe, drop is not None, want_ties, accum32)
     if key in _REFS:
         return _REFS[key]
-    prob = problem(name)
+    assert prob is None or name not in CASES
+    prob = problem(name) if prob is None else prob
     g, S, dom = without_samples(prob['g'], drop), prob['S'], prob['dom']
     ks, bs, geom_t, hp = oracle_inputs(g)
+    do_skip = prob.get('do_skip', True)
+    hp = hp if do_skip else dict(hp, do_skip=False)
     tf = t64(g['t_frames'])
     d_em = prob['dimg'].reshape((prob['B'], max(S, 1)) + prob['spatial'])
     d_em = d_em if S else d_em[:, 0]
-    em = None if recipe is None else ob.Bf16Trainer(ks, bs, geom_t, hp, recipe)
+    em = None if recipe is None else ob.Bf16Trainer(ks, bs, geom_t, hp, recipe, accum32=accum32)
     if want_ties:
-        ties = relu_tie_count(g, return_points=True)[1] if em is None else em.relu_tie_points(tf)
+        if em is None and not do_skip:         # (relu_tie_count walks the skip network: its criterion on the float64 model without the skips)
+            ties = ob.Bf16Trainer(ks, bs, geom_t, hp, rounding=False).relu_tie_points(tf)
+        else:
+            ties = relu_tie_count(g, return_points=True)[1] if em is None else em.relu_tie_points(tf)
         out = ties & (g['g'] != 0)
         out.setflags(write=False)
     else:
         if em is None:
             e = ot.predictor(ks, bs, tf, geom_t['coords'], geom_t['Omega'], 0.0, geom_t['t_geos'], T_INJ, hp['GM_c3'], dom[0], dom[1], dom[2],
-                             dom[3], posenc_deg=prob['deg'], net_depth=prob['depth'])
+                             dom[3], posenc_deg=prob['deg'], net_depth=prob['depth'], do_skip=do_skip)
             grads = ot.grad_linear(ks, bs, geom_t, hp, tf, d_em)
         else:
             e = em.emission(tf)

@@ -44,15 +44,17 @@ def problem(name):
     return _PROBLEMS[name]
 
 
-def build_problem(depth, width, mode, S, deg, H, Wd, G, dom, B):
+def build_problem(depth, width, mode, S, deg, H, Wd, G, dom, B, do_skip=True, reseed=0, jitter=(0.0, 0.0, 0.0)):
     """The builder behind problem(): a network (depth x width, posenc degree `deg`; `mode` does not enter the problem) on H x Wd rays
-    x G samples in the domain `dom`, B frames.  tests/buffer_contract_cases.py builds its ray sets with it; the draws and their order
-    are those of the frame-chunk cases (pinned by tests/test_buffer_contract_cases_cpu.py)."""
-    rng = np.random.default_rng(1000 + 7 * width + depth + 31 * S)
-    geo, r = tilted_ray_grid(H, Wd, G)
+    x G samples in the domain `dom`, B frames.  tests/buffer_contract_cases.py and tests/general_path_cases.py build their ray sets
+    with it; the draws and their order are those of the frame-chunk cases (pinned by tests/test_buffer_contract_cases_cpu.py).
+    do_skip False: the network without skip connections (general_path_cases); reseed: another draw of the same case; jitter:
+    tilted_ray_grid's offsets, for the grids that otherwise put a sample on a mask boundary; B = 1: one frame, pre-injection samples in it."""
+    rng = np.random.default_rng(1000 + 7 * width + depth + 31 * S + 100003 * reseed)
+    geo, r = tilted_ray_grid(H, Wd, G, jitter)
     g = {k: f32r(v) for k, v in dict(geo, g=rng.uniform(0.6, 1.4, r.shape)).items()}
     g['J'] = f32r(stokes_factors(rng, r.shape, S)) if S else np.array(1.0)
-    tree = onp.he_uniform_params(rng, depth, width, 3 + 6 * deg, dtype=np.float32)
+    tree = onp.he_uniform_params(rng, depth, width, 3 + 6 * deg, do_skip=do_skip, dtype=np.float32)
     for i in range(depth + 1):
         g['kernel%d' % i] = tree['MLP_0']['Dense_%d' % i]['kernel'].astype(np.float64)
         g['bias%d' % i] = f32r(rng.uniform(-0.1, 0.1, tree['MLP_0']['Dense_%d' % i]['bias'].shape))
@@ -62,7 +64,7 @@ def build_problem(depth, width, mode, S, deg, H, Wd, G, dom, B):
     assert not mask_tie_points(g).any()
     tM = g['t_frames'].reshape(-1, 1, 1, 1) / onp.GM_C3_SGRA_HR + g['t_geos'] - T_INJ
     pre = (tM < 0).sum(axis=(1, 2, 3))
-    assert len(set(T_FRAMES[:B])) == B and 0 < pre[0] < tM[0].size and pre[-1] < pre[0]
+    assert len(set(T_FRAMES[:B])) == B and 0 < pre[0] < tM[0].size and (B == 1 or pre[-1] < pre[0])
     gen = torch.Generator().manual_seed(width + depth + S)
     dimg = (torch.rand((B, max(S, 1), H * Wd), generator=gen, dtype=torch.float64) - 0.4).float().double()
     return dict(g=g, dimg=dimg, dom=dom, depth=depth, width=width, S=S, B=B, spatial=(H, Wd))

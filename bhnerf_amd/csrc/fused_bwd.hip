@@ -555,11 +555,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
             for (int i = 0; i < MW; ++i) c.mtop[i] = __builtin_nontemporal_load(mg + ((a.depth - 1) * MW + i) * 64 + lane);
             tile_point<Pol::NWAVES>(a, tile, wv, pl, c.b, c.p, c.inb);
             if (h == 0) c.e = (reinterpret_cast<const float *>(A.tape + A.t.e_off) + (tile * Pol::NWAVES + wvu) * 32)[pl];
-            if (h == 0 && c.inb) {
-                const long long ray = a.ray_idx ? (long long)a.ray_idx[c.p] : (long long)a.fd_G.div((unsigned)c.p);
-                for (int s = 0; s < a.Sx; ++s)
-                    c.dE += a.dimages[((long long)c.b * a.Sx + s) * a.R + ray] * a.w[(long long)s * a.P + c.p];
-            }
+            if (h == 0 && c.inb) c.dE = point_dE(a, a.dimages, c.b, c.p);
         }
         return c;
     };

@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256) void dout128_kernel(BwdArgs A) {
         const float e = eg[i];
         float d = 0.f;
         if (inb && e != 0.f) {
-            const long long ray = a.ray_idx ? (long long)a.ray_idx[p] : (long long)a.fd_G.div((unsigned)p);
+            const long long ray = point_ray(a, p);
             float dE = 0.f;
             for (int s = 0; s < a.Sx; ++s) dE += a.dimages[((long long)b * a.Sx + s) * a.R + ray] * a.w[(long long)s * a.P + p];
             d = dE * e * (1.f - e);

@@ -388,6 +388,50 @@ DEVI PointIn load_point(const FusedArgs &a, long long tile, int gslot, int pl) {
     return q;
 }
 
+// Velocity warp and validity rule of one point (the general kernels, general_mlp.hip): u = the warped, scaled coordinates (0 where
+// invalid), live = the point contributes.  FAST: hardware sin / cos of the revolution fraction and a multiply by 1 / scale (the bf16
+// kernels); else sincosf of the angle and the division itself (the f32 kernels).
+// (point_prologue below keeps its own copy of these lines: calling this there changes the instruction streams of fused_fwd_kernel and chain_kernel)
+template <bool FAST>
+DEVI void warp_point(const FusedArgs &a, const PointIn &in, float (&u)[3], bool &live) {
+    const double tM = in.tM0d + (double)in.tg;                  // in double: see point_prologue
+    const bool pre = tM < 0.0;                                  // emission.py:204-205 -> NaN
+    const double rev_d = tM * (double)in.om * 0.15915494309189535; // theta / (2 pi)
+    const double fr = rev_d - floor(rev_d);
+    float s, c;
+    if (FAST) {
+        s = __builtin_amdgcn_sinf((float)fr);
+        c = __builtin_amdgcn_cosf((float)fr);
+    } else {
+        sincosf((float)(fr * 6.283185307179586), &s, &c);
+    }
+    // rot_z(-theta) (utils.py:126-132 with angle=-theta): x' = c x + s y, y' = -s x + c y, z' = z, the fused multiply-adds written out: left to
+    // the compiler (as in point_prologue) the bits depend on whether it pairs the two products into a packed multiply first
+    u[0] = __builtin_fmaf(c, in.x, s * in.y);
+    u[1] = __builtin_fmaf(c, in.y, -(s * in.x));
+    u[2] = in.z;
+    const bool finite_theta = !pre && (fr == fr);
+    bool valid[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        valid[k] = finite_theta && isfinite(u[k]);               // network.py:226
+        u[k] = valid[k] ? (FAST ? u[k] * a.inv_scale : u[k] / a.scale) : 0.f;     // network.py:227,229 (f32 mode: the division itself)
+    }
+    live = in.inb && in.dom && valid[0];                         // emission.py:370-373, network.py:232
+}
+
+// the ray (pixel) of point p, and dE = d loss / d e of that point: sum_s dimages[b, s, ray] w[s, p] (network.py:417 backwards)
+// (dout128_kernel, fused_bwd128.hip, takes its ray from point_ray but keeps its own dE loop: with point_dE its instruction stream changes)
+DEVI long long point_ray(const FusedArgs &a, long long p) {
+    return a.ray_idx ? (long long)a.ray_idx[p] : (long long)a.fd_G.div((unsigned)p);
+}
+DEVI float point_dE(const FusedArgs &a, const float *dimages, int b, long long p) {
+    const long long ray = point_ray(a, p);
+    float dE = 0.f;
+    for (int s = 0; s < a.Sx; ++s) dE += dimages[((long long)b * a.Sx + s) * a.R + ray] * a.w[(long long)s * a.P + p];
+    return dE;
+}
+
 template <class Pol, int DEG>
 DEVI void point_prologue(const FusedArgs &a, const PointIn &in, typename Pol::frag (&enc)[2], bool &live) {
     const int lane = threadIdx.x & 63;
@@ -1018,7 +1062,7 @@ struct RaySum {
     }
     static DEVI void direct(const FusedArgs &a, int b, long long p, bool inb, float e, float w0, bool have_w0) {
         const int lane = threadIdx.x & 63, h = lane >> 5;
-        const long long ray = inb ? (a.ray_idx ? (long long)a.ray_idx[p] : (long long)a.fd_G.div((unsigned)p)) : -1;
+        const long long ray = inb ? point_ray(a, p) : -1;
         float we[SMAX];
         weighted(a, p, h == 0 && inb, e, w0, have_w0, we);
         unsigned long long rem = __ballot(h == 0 && inb);
@@ -1042,7 +1086,7 @@ struct RaySum {
         int *seg_ray = reinterpret_cast<int *>(lds);                                  // [NW][32]
         float *seg_val = reinterpret_cast<float *>(lds + NW * 32 * 4);                // [NW][Sx][32]
         int *seg_n = reinterpret_cast<int *>(lds + NW * 32 * 4 + NW * a.Sx * 32 * 4); // [NW]
-        const long long ray = inb ? (a.ray_idx ? (long long)a.ray_idx[p] : (long long)a.fd_G.div((unsigned)p)) : -1;
+        const long long ray = inb ? point_ray(a, p) : -1;
         float we[SMAX];
         weighted(a, p, h == 0 && inb, e, w0, have_w0, we);
         unsigned long long rem = __ballot(h == 0 && inb);

@@ -19,6 +19,9 @@
 //                                      128-column block of one layer over one share of the chunk's groups, into its own slab
 //                                      (the bias is the job whose input tile is a row of ones);
 //   gen_reduce_kernel                  slabs summed in split order -> flat gradient (deterministic).
+// The bf16 family (gen_mlp16_kernel<MODE, NG>, gen_dw16_kernel) shares with it, each written once: the warp of a point (warp_point<FAST>, fused_common.h),
+// the octave (gen_octave<FAST>), the mode flags (GenMode), the weight-gradient job, its groups and its slab flush (GenDwJob, gen_dw_*), the LDS
+// layouts (GenLds, GenLds16: one function for kernels and host rules), the launcher (gen_launch<K>) and the workspace split (gen_workspace).
 //
 // Packed image (bhn_pack_weights; BHN_BF16 adds its bf16 fragment images behind it, Gen16): per layer K_l zero-padded to [hrows | erows][outp] (hrows = width padded to 32
 // for l > 0, erows = encoded inputs padded to 32 for layer 0 and the skip layers, network.py:59-61; outp = padded width, 32
@@ -54,11 +57,11 @@ struct GenArgs {
     FusedArgs f;
     Gen16 g16;
     int bf16;                          // 1: the bf16 kernels (mode BHN_BF16)
-    char *tape16;
     GenLayer L[BHN_MAX_LAYERS];
     int D, Wp, Ep, F;
     const float *pk;                   // packed image
-    float *tape;                       // [group of this chunk][tape_tile floats]: enc | h_1 .. h_D | gA_0 .. gA_{D-1} | gA_D (32 rows) | e (32)
+    // [group of this chunk][one group's tape] -- f32: tape_tile floats, enc | h_1 .. h_D | gA_0 .. gA_{D-1} | gA_D (32 rows) | e (32); bf16: g16.bytes bytes
+    char *tape;
     long long tape_tile;
     long long tile0, ntiles;           // the chunk, in tiles of GEN_TG groups
     const float *dimages;
@@ -75,6 +78,41 @@ struct GenArgs {
 DEVI long long tape_h(const GenArgs &A, int l) { return (long long)A.Ep * 32 + (long long)(l - 1) * A.Wp * 32; }        // l = 1..D
 DEVI long long tape_ga(const GenArgs &A, int l) { return (long long)A.Ep * 32 + (long long)(A.D + l) * A.Wp * 32; }     // l = 0..D
 DEVI long long tape_e(const GenArgs &A) { return A.tape_tile - 32; }
+
+// ---- what the f32 and the bf16 kernels share (the warp and dE of a point are fused_common.h's warp_point and point_dE) ----
+template <int MODE>
+struct GenMode {        // FWD: runs the forward; REC: writes the layer inputs to the tape; IMG: adds the ray sums to the images; BWD: dout and the delta chain
+    static constexpr bool FWD = MODE != GEN_CHAIN_TAPE, REC = MODE == GEN_RECORD || MODE == GEN_CHAIN;
+    static constexpr bool IMG = MODE == GEN_RENDER || MODE == GEN_RECORD, BWD = MODE == GEN_CHAIN || MODE == GEN_CHAIN_TAPE;
+};
+
+// sin and cos of octave i of a warped coordinate (network.py:118-122), each family's own expression: sincosf of 2^i u (f32 kernels),
+// hardware sin / cos of the revolution fraction of 2^i u / (2 pi) (bf16 kernels; the fused prologue scales u first: another rounding)
+template <bool FAST>
+DEVI void gen_octave(float u, int i, float &s, float &c) {
+    if (!FAST) { sincosf(u * (float)(1 << i), &s, &c); return; }
+    const float rev = __builtin_amdgcn_fractf(u * (float)(1 << i) * 0.15915494309189535f);
+    s = __builtin_amdgcn_sinf(rev); c = __builtin_amdgcn_cosf(rev);
+}
+
+// LDS of the MLP kernels as byte offsets: the kernels take their pointers, the host rules (gen_ng16, gen_grid, the launcher) `total`
+constexpr int GEN_THREADS = 512, GEN_PARTS = GEN_THREADS / 32;      // the largest workgroup and its 32-thread parts
+// f32: two activation images [Wp][32], encoded inputs [Ep][32], the output layer's partial sums [GEN_PARTS][32], dout and live [32], RaySum<GEN_TG> scratch
+struct GenLds { unsigned buf0, buf1, enc, red, dout, live, seg, total; };
+__host__ __device__ inline GenLds gen_lds(int Wp, int Ep, int Sx) {
+    GenLds L;
+    L.buf0 = 0; L.buf1 = L.buf0 + Wp * 32 * 4; L.enc = L.buf1 + Wp * 32 * 4; L.red = L.enc + Ep * 32 * 4;
+    L.dout = L.red + GEN_PARTS * 32 * 4; L.live = L.dout + 32 * 4; L.seg = L.live + 32 * 4; L.total = L.seg + RaySum<GEN_TG>::bytes(Sx);
+    return L;
+}
+// bf16: group g of ng at g * slot -- two activation images of `buf` bytes, its encoded inputs at `enc` (B fragments) --, then e, dout, live [ng][32], the scratch
+struct GenLds16 { unsigned buf, enc, slot, e, dout, live, seg, total; };
+__host__ __device__ inline GenLds16 gen_lds16(int Wp, int Ep, int Sx, int ng) {
+    GenLds16 L;
+    L.buf = Wp * 64; L.enc = 2 * L.buf; L.slot = L.enc + Ep * 64; L.e = ng * L.slot;
+    L.dout = L.e + ng * 32 * 4; L.live = L.dout + ng * 32 * 4; L.seg = L.live + ng * 32 * 4; L.total = L.seg + RaySum<GEN_TG>::bytes(Sx);
+    return L;
+}
 
 // acc (features 32 m .. 32 m + 31 x the 32 points) += sum_k K[k][32 m + i] in[k][point]: K rows `rows` (a multiple of 32)
 // of `stride` floats, `in` an LDS image [row][32].  Lane (i, h) feeds k = 2 t + h of every pair.
@@ -105,20 +143,52 @@ DEVI f32x16 gen_rows(f32x16 acc, const float *__restrict__ K, int stride, int m,
 // accumulator element r of lane (i, h) is feature 32 m + gen_row(r, h) of point i
 DEVI int gen_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// ---- the weight-gradient kernels' jobs: blockIdx.x -> one 32-row x 128-column block of one layer's gradient (gen_layout counts them): layer, input
+// tile, output strip and its 32-column tiles; the layer's input tiles: hidden, then encoded, then the bias (a row of ones) ----
+struct GenDwJob { int l, mi, strip, nt, htiles, etiles; bool bias_job, valid; };
+DEVI GenDwJob gen_dw_job(const GenArgs &A, int job) {
+    GenDwJob J = {};
+    for (J.l = 0; J.l <= A.D; ++J.l) {
+        const int nin = ((A.L[J.l].hrows + A.L[J.l].erows) >> 5) + 1, nst = ((A.L[J.l].outp >> 5) + 3) >> 2;
+        if (job < nin * nst) { J.mi = job / nst; J.strip = job - J.mi * nst; break; }
+        job -= nin * nst;
+    }
+    J.valid = J.l <= A.D;
+    if (!J.valid) return J;
+    J.nt = min(4, (A.L[J.l].outp >> 5) - 4 * J.strip);
+    J.htiles = A.L[J.l].hrows >> 5; J.etiles = A.L[J.l].erows >> 5;
+    J.bias_job = J.mi == J.htiles + J.etiles;
+    return J;
+}
+DEVI void gen_dw_groups(const GenArgs &A, long long &t0, long long &t1) {      // the groups [t0, t1) of the chunk that split blockIdx.y sums
+    const long long ngr = A.ntiles * GEN_TG;
+    t0 = ngr * blockIdx.y / A.nsplit; t1 = ngr * (blockIdx.y + 1) / A.nsplit;
+}
+DEVI void gen_dw_flush(const GenArgs &A, const GenDwJob &J, const f32x16 (&acc)[4], int lane) {      // into (first chunk of a call) or onto the split's slab
+    const int i = lane & 31, h = lane >> 5, outp = A.L[J.l].outp;
+    float *slab = A.slabs + (long long)blockIdx.y * A.slab_floats + A.L[J.l].slab_off;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < J.nt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float *d = slab + (long long)(32 * J.mi + gen_row(r, h)) * outp + 128 * J.strip + 32 * j + i;
+                *d = A.accumulate ? *d + acc[j][r] : acc[j][r];
+            }
+        }
+}
+
 template <int MODE>
-__global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
-    constexpr bool FWD = MODE != GEN_CHAIN_TAPE;                             // runs the forward
-    constexpr bool REC = MODE == GEN_RECORD || MODE == GEN_CHAIN;            // writes the layer inputs to the tape
-    constexpr bool IMG = MODE == GEN_RENDER || MODE == GEN_RECORD;           // adds the ray sums to the images
-    constexpr bool BWD = MODE == GEN_CHAIN || MODE == GEN_CHAIN_TAPE;        // dout and the delta chain
+__global__ __launch_bounds__(GEN_THREADS) void gen_mlp_kernel(GenArgs A) {
+    using M = GenMode<MODE>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const FusedArgs &a = A.f;
     const int Wp = A.Wp, Ep = A.Ep, D = A.D, MTp = Wp >> 5;
-    float *buf0 = reinterpret_cast<float *>(smem), *buf1 = buf0 + Wp * 32, *encS = buf1 + Wp * 32;
-    float *red = encS + Ep * 32;                       // [16][32] partial sums of the output layer
-    float *doutv = red + 16 * 32;                      // [32]
-    int *livev = reinterpret_cast<int *>(doutv + 32);  // [32]
-    char *seg = reinterpret_cast<char *>(livev + 32);  // RaySum<GEN_TG> scratch
+    const GenLds lds = gen_lds(Wp, Ep, a.Sx);
+    auto at = [&](unsigned off) { return reinterpret_cast<float *>(smem + off); };
+    float *buf0 = at(lds.buf0), *buf1 = at(lds.buf1), *encS = at(lds.enc), *red = at(lds.red), *doutv = at(lds.dout);
+    int *livev = reinterpret_cast<int *>(smem + lds.live);
+    char *seg = smem + lds.seg;
     const int tid = threadIdx.x, lane = tid & 63, pl = tid & 31, part = tid >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = (int)(blockDim.x >> 6), NP = (int)(blockDim.x >> 5), NT = (int)blockDim.x;
     const int li = lane & 31, lh = lane >> 5;
@@ -126,37 +196,23 @@ __global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
     for (long long tile = A.tile0 + blockIdx.x; tile < A.tile0 + A.ntiles; tile += gridDim.x) {
       int tile_b = 0;
       for (int g = 0; g < GEN_TG; ++g) {
-        float *tp = (REC || BWD) ? A.tape + ((tile - A.tile0) * GEN_TG + g) * A.tape_tile : nullptr;
+        float *tp = (M::REC || M::BWD) ? reinterpret_cast<float *>(A.tape) + ((tile - A.tile0) * GEN_TG + g) * A.tape_tile : nullptr;
         // ---- velocity warp + positional encoding of the group's 32 points (every 32-thread part holds all of them) ----
         const PointIn q = load_point<GEN_TG>(a, tile, g, pl);
         tile_b = q.b;
         float *in = buf0, *out = buf1;
         float e = 0.f;
-        if constexpr (FWD) {
+        if constexpr (M::FWD) {
         bool live;
         {
-            const double tM = q.tM0d + (double)q.tg;                       // emission.py:200-201 (t_M in double)
-            const bool pre = tM < 0.0;                                     // emission.py:204-205
-            const double rev_d = tM * (double)q.om * 0.15915494309189535;
-            const double fr = rev_d - floor(rev_d);
-            float s, c;
-            sincosf((float)(fr * 6.283185307179586), &s, &c);
-            float u[3] = {c * q.x + s * q.y, c * q.y - s * q.x, q.z};      // rot_z(-theta), utils.py:126-132
-            const bool finite_theta = !pre && (fr == fr);
-            bool valid0 = false;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const bool v = finite_theta && isfinite(u[k]);              // network.py:226
-                if (k == 0) valid0 = v;
-                u[k] = v ? u[k] / a.scale : 0.f;                            // network.py:227, 229
-            }
-            live = q.inb && q.dom && valid0;
+            float u[3];
+            warp_point<false>(a, q, u, live);
             // features in the reference's order [u | sin(2^i u_k) at 3 + 3 i + k | cos(...) at 3 + 3 deg + 3 i + k]
             for (int i = part; i < a.deg; i += NP)
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     float sv, cv;
-                    sincosf(u[k] * (float)(1 << i), &sv, &cv);
+                    gen_octave<false>(u[k], i, sv, cv);
                     encS[(3 + 3 * i + k) * 32 + pl] = sv;
                     encS[(3 + 3 * a.deg + 3 * i + k) * 32 + pl] = cv;
                 }
@@ -168,7 +224,7 @@ __global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
             for (int r = A.F + part; r < Ep; r += NP) encS[r * 32 + pl] = 0.f;
         }
         __syncthreads();
-        if (REC)
+        if (M::REC)
             for (int idx = tid; idx < Ep * 32; idx += NT) tp[idx] = encS[idx];
         // ---- hidden layers ----
         for (int l = 0; l < D; ++l) {
@@ -184,7 +240,7 @@ __global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
                     const float v = acc[r] > 0.f ? acc[r] : 0.f;
                     const int o = (32 * m + gen_row(r, lh)) * 32 + li;
                     out[o] = v;
-                    if (REC) tp[tape_h(A, l + 1) + o] = v;
+                    if (M::REC) tp[tape_h(A, l + 1) + o] = v;
                 }
             }
             __syncthreads();
@@ -203,7 +259,7 @@ __global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
                 float o = A.pk[Lo.b_off];
                 for (int p2 = 0; p2 < NP; ++p2) o += red[p2 * 32 + pl];
                 if (live) e = 1.f / (1.f + expf(10.f - o));                      // network.py:231-233
-                if (REC) tp[tape_e(A) + pl] = e;
+                if (M::REC) tp[tape_e(A) + pl] = e;
             }
         }
         } else {
@@ -215,18 +271,18 @@ __global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
         if (MODE == GEN_PREDICT) {
             if (tid < 32 && q.inb) a.emission[(long long)q.b * a.P + q.p] = e;
         }
-        if constexpr (IMG) {
+        if constexpr (M::IMG) {
             // the group's ray segments: straight to the pixels where that is order-independent already (ray_direct), else to the
             // tile's scratch (combined behind the eighth group)
             if (wv == 0) RaySum<GEN_TG>::put(a, seg, g, q.p, q.inb, e, 0.f, false, q.b);
         }
-        if constexpr (BWD) {
+        if constexpr (M::BWD) {
             const GenLayer Lo = A.L[D];
-            // ---- dout = d loss / d (pre-sigmoid output): dE e (1 - e), dE = sum_s dimages[b, s, ray] w[s, p] ----
+            // ---- dout = d loss / d (pre-sigmoid output): dE e (1 - e), dE = sum_s dimages[b, s, ray] w[s, p] (not point_dE: <GEN_CHAIN_TAPE> runs 1 % slower with it) ----
             if (tid < 32) {
                 float d = 0.f;
                 if (q.inb && e != 0.f) {
-                    const long long ray = a.ray_idx ? (long long)a.ray_idx[q.p] : (long long)a.fd_G.div((unsigned)q.p);
+                    const long long ray = point_ray(a, q.p);
                     float dE = 0.f;
                     for (int s = 0; s < a.Sx; ++s) dE += A.dimages[((long long)q.b * a.Sx + s) * a.R + ray] * a.w[(long long)s * a.P + q.p];
                     d = dE * e * (1.f - e);
@@ -266,7 +322,7 @@ __global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
         }
         __syncthreads();
       }
-      if constexpr (IMG) {
+      if constexpr (M::IMG) {
           // the tile's ray segments -> pixels: every ray of the tile gets ONE atomic, its segments added in group order
           if (!a.ray_direct) {
               for (int vw = wv; vw < GEN_TG; vw += nwv) RaySum<GEN_TG>::combine(a, seg, vw, tile_b);
@@ -279,30 +335,21 @@ __global__ __launch_bounds__(512) void gen_mlp_kernel(GenArgs A) {
 // dK_l[in rows 32 mi ..][out columns 128 strip ..] += sum over the split's groups of in_l^T gA_l (the bias: in = a row of ones)
 __global__ __launch_bounds__(64) void gen_dw_kernel(GenArgs A) {
     const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
-    // job -> (layer, input tile, output strip)
-    int job = blockIdx.x, l = 0, mi = 0, strip = 0;
-    for (l = 0; l <= A.D; ++l) {
-        const int nin = ((A.L[l].hrows + A.L[l].erows) >> 5) + 1, nst = ((A.L[l].outp >> 5) + 3) >> 2;
-        if (job < nin * nst) { mi = job / nst; strip = job - mi * nst; break; }
-        job -= nin * nst;
-    }
-    if (l > A.D) return;
-    const GenLayer Lr = A.L[l];
-    const int nt = min(4, (Lr.outp >> 5) - 4 * strip);                     // 32-column tiles of this strip
-    const int htiles = Lr.hrows >> 5, etiles = Lr.erows >> 5;
-    const bool bias_job = mi == htiles + etiles;
+    const GenDwJob J = gen_dw_job(A, blockIdx.x);
+    if (!J.valid) return;
+    const int nt = J.nt; const bool bias_job = J.bias_job;
     // this lane's 16 points of a group: 16 h .. 16 h + 15 (any pairing of points with k-steps serves a sum over points)
     long long a_off = 0;
-    if (mi < htiles) a_off = tape_h(A, l) + (long long)(32 * mi + i) * 32 + 16 * h;
-    else if (!bias_job) a_off = (long long)(32 * (mi - htiles) + i) * 32 + 16 * h;
-    const long long b_off = tape_ga(A, l) + (long long)(128 * strip + i) * 32 + 16 * h;
+    if (J.mi < J.htiles) a_off = tape_h(A, J.l) + (long long)(32 * J.mi + i) * 32 + 16 * h;
+    else if (!bias_job) a_off = (long long)(32 * (J.mi - J.htiles) + i) * 32 + 16 * h;
+    const long long b_off = tape_ga(A, J.l) + (long long)(128 * J.strip + i) * 32 + 16 * h;
     f32x16 acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { const f32x16 z = {}; acc[j] = z; }
-    const long long ngr = A.ntiles * GEN_TG;                              // groups of the chunk
-    const long long t0 = ngr * blockIdx.y / A.nsplit, t1 = ngr * (blockIdx.y + 1) / A.nsplit;
+    long long t0, t1;
+    gen_dw_groups(A, t0, t1);
     for (long long t = t0; t < t1; ++t) {
-        const float *tp = A.tape + t * A.tape_tile;
+        const float *tp = reinterpret_cast<const float *>(A.tape) + t * A.tape_tile;
         f32x4 av[4], bv[4][4];
         if (bias_job) {
 #pragma unroll
@@ -324,16 +371,7 @@ __global__ __launch_bounds__(64) void gen_dw_kernel(GenArgs A) {
                 for (int k = 0; k < 16; ++k) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[k >> 2][k & 3], bv[j][k >> 2][k & 3], acc[j], 0, 0, 0);
             }
     }
-    float *slab = A.slabs + (long long)blockIdx.y * A.slab_floats + Lr.slab_off;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j < nt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float *d = slab + (long long)(32 * mi + gen_row(r, h)) * Lr.outp + 128 * strip + 32 * j + i;
-                *d = A.accumulate ? *d + acc[j][r] : acc[j][r];
-            }
-        }
+    gen_dw_flush(A, J, acc, lane);
 }
 
 __global__ void gen_reduce_kernel(GenArgs A) {
@@ -415,6 +453,11 @@ DEVI void g16_store_T(char *tile, const g16frag &f0, const g16frag &f1, const g1
         *reinterpret_cast<g16frag *>(tile + s * 1024 + lane * 16) = o;
     }
 }
+// a finished tile m of a layer, as its two B fragments, into the activation image `img`: k-steps 2 m, 2 m + 1 of the next GEMM
+DEVI void g16_put_act(char *img, int m, const g16frag &f0, const g16frag &f1, int lane) {
+    *reinterpret_cast<g16frag *>(img + (2 * m) * 1024 + lane * 16) = f0;
+    *reinterpret_cast<g16frag *>(img + (2 * m + 1) * 1024 + lane * 16) = f1;
+}
 // the point a T-tile fragment element stands for
 DEVI int g16_point(int s, int j, int h) { return (j & 3) + 8 * (j >> 2) + 16 * s + 4 * h; }
 
@@ -465,19 +508,18 @@ DEVI void g16_ksteps(f32x16 (&acc)[NG], const char *afrag, const char *bbase, in
 }
 
 template <int MODE, int NG>
-__global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
-    constexpr bool FWD = MODE != GEN_CHAIN_TAPE, REC = MODE == GEN_RECORD || MODE == GEN_CHAIN;
-    constexpr bool IMG = MODE == GEN_RENDER || MODE == GEN_RECORD, BWD = MODE == GEN_CHAIN || MODE == GEN_CHAIN_TAPE;
+__global__ __launch_bounds__(GEN_THREADS) void gen_mlp16_kernel(GenArgs A) {
+    using M = GenMode<MODE>;
     static_assert(GEN_TG % NG == 0, "a tile is a whole number of rounds");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const FusedArgs &a = A.f;
     const Gen16 &G = A.g16;
     const int Wp = A.Wp, Ep = A.Ep, D = A.D, MTp = Wp >> 5;
-    const int BUF = Wp * 64, SLOT = 2 * BUF + Ep * 64;                    // per group: two activation images + the encoded inputs (B fragments)
-    float *ev = reinterpret_cast<float *>(smem + NG * SLOT);              // [NG][32]
-    float *doutv = ev + NG * 32;
-    int *livev = reinterpret_cast<int *>(doutv + NG * 32);
-    char *seg = reinterpret_cast<char *>(livev + NG * 32);                // RaySum<GEN_TG> scratch
+    const GenLds16 lds = gen_lds16(Wp, Ep, a.Sx, NG);
+    const int BUF = lds.buf, ENC = lds.enc, SLOT = lds.slot;              // per group: two activation images + the encoded inputs (B fragments)
+    float *ev = reinterpret_cast<float *>(smem + lds.e), *doutv = reinterpret_cast<float *>(smem + lds.dout);      // [NG][32]
+    int *livev = reinterpret_cast<int *>(smem + lds.live);
+    char *seg = smem + lds.seg;
     const int tid = threadIdx.x, lane = tid & 63, pl = tid & 31, part = tid >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = (int)(blockDim.x >> 6), NP = (int)(blockDim.x >> 5), NT = (int)blockDim.x;
     const int li = lane & 31, lh = lane >> 5;
@@ -486,7 +528,7 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
     // the unused slots of the encoded-input images stay zero for the whole launch
     for (int idx = tid; idx < NG * Ep * 16; idx += NT) {
         const int g = idx / (Ep * 16), w = idx - g * (Ep * 16);
-        reinterpret_cast<unsigned *>(smem + g * SLOT + 2 * BUF)[w] = 0u;
+        reinterpret_cast<unsigned *>(smem + g * SLOT + ENC)[w] = 0u;
     }
     __syncthreads();
     auto enc_put = [&](char *encb, int q, int pt, float v) {             // feature q of point pt -> its place in the B fragments
@@ -496,48 +538,38 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
 
     for (long long tile = A.tile0 + blockIdx.x; tile < A.tile0 + A.ntiles; tile += gridDim.x) {
       for (int g0 = 0; g0 < GEN_TG; g0 += NG) {
-        char *tp0 = (REC || BWD) ? A.tape16 + ((tile - A.tile0) * GEN_TG + g0) * G.bytes : nullptr;      // group g0 + g: + g * G.bytes
+        char *tp0 = (M::REC || M::BWD) ? A.tape + ((tile - A.tile0) * GEN_TG + g0) * G.bytes : nullptr;      // group g0 + g: + g * G.bytes
         int cur = 0;                                                       // which activation image holds the running layer's input
-        if constexpr (FWD) {
+        if constexpr (M::FWD) {
             // ---- velocity warp + positional encoding: 32-thread part (gsel, sub) does group gsel's octaves sub, sub + nsub, ... ----
             {
                 const int gsel = part % NG, sub = part / NG, nsub = NP / NG;
                 const PointIn q = load_point<GEN_TG>(a, tile, g0 + gsel, pl);
-                const double tM = q.tM0d + (double)q.tg;                   // emission.py:200-201 (t_M in double)
-                const bool pre = tM < 0.0;                                 // emission.py:204-205
-                const double rev_d = tM * (double)q.om * 0.15915494309189535;
-                const double fr = rev_d - floor(rev_d);
-                const float s0 = __builtin_amdgcn_sinf((float)fr), c0 = __builtin_amdgcn_cosf((float)fr);
-                float u[3] = {c0 * q.x + s0 * q.y, c0 * q.y - s0 * q.x, q.z};    // rot_z(-theta), utils.py:126-132
-                const bool finite_theta = !pre && (fr == fr);
-                bool valid0 = false;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const bool v = finite_theta && isfinite(u[k]);          // network.py:226
-                    if (k == 0) valid0 = v;
-                    u[k] = v ? u[k] * a.inv_scale : 0.f;                    // network.py:227, 229
-                }
-                char *encb = smem + gsel * SLOT + 2 * BUF;
+                float u[3];
+                bool live;
+                warp_point<true>(a, q, u, live);
+                char *encb = smem + gsel * SLOT + ENC;
                 if (sub < nsub) {
                     for (int i = sub; i < a.deg; i += nsub)
 #pragma unroll
                         for (int k = 0; k < 3; ++k) {
-                            const float rev = __builtin_amdgcn_fractf(u[k] * (float)(1 << i) * 0.15915494309189535f);
-                            enc_put(encb, 3 + 3 * i + k, pl, __builtin_amdgcn_sinf(rev));
-                            enc_put(encb, 3 + 3 * a.deg + 3 * i + k, pl, __builtin_amdgcn_cosf(rev));
+                            float sv, cv;
+                            gen_octave<true>(u[k], i, sv, cv);
+                            enc_put(encb, 3 + 3 * i + k, pl, sv);
+                            enc_put(encb, 3 + 3 * a.deg + 3 * i + k, pl, cv);
                         }
                     if (sub == 0) {
 #pragma unroll
                         for (int k = 0; k < 3; ++k) enc_put(encb, k, pl, u[k]);
-                        livev[gsel * 32 + pl] = (q.inb && q.dom && valid0) ? 1 : 0;
+                        livev[gsel * 32 + pl] = live ? 1 : 0;
                     }
                 }
             }
             __syncthreads();
-            if constexpr (REC) {                                            // the encoded inputs as T tiles (dW_0 and the skip layer)
+            if constexpr (M::REC) {                                         // the encoded inputs as T tiles (dW_0 and the skip layer)
                 for (int it = wv; it < NG * (Ep >> 5); it += nwv) {
                     const int g = it % NG, eb = it / NG;
-                    const char *encb = smem + g * SLOT + 2 * BUF;
+                    const char *encb = smem + g * SLOT + ENC;
                     const g16frag f0 = *reinterpret_cast<const g16frag *>(encb + (2 * eb) * 1024 + lane * 16);
                     const g16frag f1 = *reinterpret_cast<const g16frag *>(encb + (2 * eb + 1) * 1024 + lane * 16);
                     g16_store_T(tp0 + g * G.bytes + G.encT + eb * 2048, f0, f1, id, lane);
@@ -557,7 +589,7 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
                     }
                     const char *af = pk16 + G.f_off[l] + (long long)m * G.ksf[l] * 1024;
                     if (hks) g16_ksteps<NG>(acc, af, smem + cur * BUF, SLOT, hks, lane);
-                    if (eks) g16_ksteps<NG>(acc, af + (long long)hks * 1024, smem + 2 * BUF, SLOT, eks, lane);
+                    if (eks) g16_ksteps<NG>(acc, af + (long long)hks * 1024, smem + ENC, SLOT, eks, lane);
 #pragma unroll
                     for (int g = 0; g < NG; ++g) {
                         g16frag f[2];
@@ -568,10 +600,8 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
                             f[r >> 3][r & 7] = (__bf16)(on ? acc[g][r] : 0.f);
                             mask |= (on ? 1u : 0u) << r;
                         }
-                        char *ob = smem + g * SLOT + (cur ^ 1) * BUF;
-                        *reinterpret_cast<g16frag *>(ob + (2 * m) * 1024 + lane * 16) = f[0];
-                        *reinterpret_cast<g16frag *>(ob + (2 * m + 1) * 1024 + lane * 16) = f[1];
-                        if constexpr (REC) {
+                        g16_put_act(smem + g * SLOT + (cur ^ 1) * BUF, m, f[0], f[1], lane);
+                        if constexpr (M::REC) {
                             char *tg = tp0 + g * G.bytes;
                             g16_store_T(tg + G.hT + ((long long)l * MTp + m) * 2048, f[0], f[1], id, lane);
                             *reinterpret_cast<unsigned *>(tg + G.bits + ((long long)l * MTp + m) * 256 + lane * 4) = mask;
@@ -591,12 +621,12 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
                     for (int r = 0; r < 16; ++r) acc1[0][r] = 0.f;
                     const char *af = pk16 + G.f_off[D];
                     g16_ksteps<1>(acc1, af, smem + g * SLOT + cur * BUF, 0, hks, lane);
-                    if (eks) g16_ksteps<1>(acc1, af + (long long)hks * 1024, smem + g * SLOT + 2 * BUF, 0, eks, lane);
+                    if (eks) g16_ksteps<1>(acc1, af + (long long)hks * 1024, smem + g * SLOT + ENC, 0, eks, lane);
                     if (lh == 0) {
                         float e = 0.f;
                         if (livev[g * 32 + li]) e = 1.f / (1.f + __expf(10.f - (acc1[0][0] + A.pk[Lo.b_off])));
                         ev[g * 32 + li] = e;
-                        if constexpr (REC) *reinterpret_cast<float *>(tp0 + g * G.bytes + G.e + li * 4) = e;
+                        if constexpr (M::REC) *reinterpret_cast<float *>(tp0 + g * G.bytes + G.e + li * 4) = e;
                     }
                 }
             }
@@ -611,19 +641,13 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
             const PointIn q = load_point<GEN_TG>(a, tile, g0 + g, pl);
             const float e = ev[g * 32 + pl];
             if (MODE == GEN_PREDICT) { if (q.inb) a.emission[(long long)q.b * a.P + q.p] = e; }
-            if constexpr (BWD) {
-                float d = 0.f;
-                if (q.inb && e != 0.f) {
-                    const long long ray = a.ray_idx ? (long long)a.ray_idx[q.p] : (long long)a.fd_G.div((unsigned)q.p);
-                    float dE = 0.f;
-                    for (int s = 0; s < a.Sx; ++s) dE += A.dimages[((long long)q.b * a.Sx + s) * a.R + ray] * a.w[(long long)s * a.P + q.p];
-                    d = dE * e * (1.f - e);
-                }
+            if constexpr (M::BWD) {
+                const float d = (q.inb && e != 0.f) ? point_dE(a, A.dimages, q.b, q.p) * e * (1.f - e) : 0.f;
                 doutv[g * 32 + pl] = d;
                 *reinterpret_cast<float *>(tp0 + g * G.bytes + G.dout + pl * 4) = d;
             }
         }
-        if constexpr (IMG) {
+        if constexpr (M::IMG) {
             if (wv == 0) {
                 for (int g = 0; g < NG; ++g) {
                     const PointIn q = load_point<GEN_TG>(a, tile, g0 + g, li);
@@ -631,7 +655,7 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
                 }
             }
         }
-        if constexpr (BWD) {
+        if constexpr (M::BWD) {
             __syncthreads();
             // ---- gA_{D-1} = relu'(h_D) (.) K_out dout as B fragments, from the recorded relu bits ----
             const GenLayer Lo = A.L[D];
@@ -647,9 +671,7 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
                     g16frag f[2];
 #pragma unroll
                     for (int r = 0; r < 16; ++r) f[r >> 3][r & 7] = (__bf16)(((mask >> r) & 1u) ? kf[r] * dv : 0.f);
-                    char *ob = smem + g * SLOT + (cur ^ 1) * BUF;
-                    *reinterpret_cast<g16frag *>(ob + (2 * m) * 1024 + lane * 16) = f[0];
-                    *reinterpret_cast<g16frag *>(ob + (2 * m + 1) * 1024 + lane * 16) = f[1];
+                    g16_put_act(smem + g * SLOT + (cur ^ 1) * BUF, m, f[0], f[1], lane);
                     g16_store_T(tg + G.gaT + ((long long)(D - 1) * MTp + m) * 2048, f[0], f[1], id, lane);
                 }
             }
@@ -671,9 +693,7 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
                         g16frag f[2];
 #pragma unroll
                         for (int r = 0; r < 16; ++r) f[r >> 3][r & 7] = (__bf16)(((mask >> r) & 1u) ? acc[g][r] : 0.f);
-                        char *ob = smem + g * SLOT + (cur ^ 1) * BUF;
-                        *reinterpret_cast<g16frag *>(ob + (2 * m) * 1024 + lane * 16) = f[0];
-                        *reinterpret_cast<g16frag *>(ob + (2 * m + 1) * 1024 + lane * 16) = f[1];
+                        g16_put_act(smem + g * SLOT + (cur ^ 1) * BUF, m, f[0], f[1], lane);
                         g16_store_T(tg + G.gaT + ((long long)(l - 1) * MTp + m) * 2048, f[0], f[1], id, lane);
                     }
                 }
@@ -683,7 +703,7 @@ __global__ __launch_bounds__(512) void gen_mlp16_kernel(GenArgs A) {
         }
         __syncthreads();
       }
-      if constexpr (IMG) {
+      if constexpr (M::IMG) {
           if (!a.ray_direct) {
               for (int vw = wv; vw < GEN_TG; vw += nwv) RaySum<GEN_TG>::combine(a, seg, vw, (int)a.fd_tpf.div((unsigned)tile));
               __syncthreads();
@@ -697,33 +717,25 @@ __global__ __launch_bounds__(64) void gen_dw16_kernel(GenArgs A) {
     const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
     const Gen16 &G = A.g16;
     const int MTp = A.Wp >> 5;
-    int job = blockIdx.x, l = 0, mi = 0, strip = 0;
-    for (l = 0; l <= A.D; ++l) {
-        const int nin = ((A.L[l].hrows + A.L[l].erows) >> 5) + 1, nst = ((A.L[l].outp >> 5) + 3) >> 2;
-        if (job < nin * nst) { mi = job / nst; strip = job - mi * nst; break; }
-        job -= nin * nst;
-    }
-    if (l > A.D) return;
-    const GenLayer Lr = A.L[l];
-    const int nt = min(4, (Lr.outp >> 5) - 4 * strip);                     // 32-column tiles of this strip
-    const int htiles = Lr.hrows >> 5, etiles = Lr.erows >> 5;
-    const bool bias_job = mi == htiles + etiles, out_job = l == A.D;
+    const GenDwJob J = gen_dw_job(A, blockIdx.x);
+    if (!J.valid) return;
+    const int nt = J.nt; const bool bias_job = J.bias_job, out_job = J.l == A.D;
     long long a_off = 0;                                                   // the input tile: h_l tile mi, or encoded-input tile mi - htiles
-    if (mi < htiles) a_off = G.hT + ((long long)(l - 1) * MTp + mi) * 2048;
-    else if (!bias_job) a_off = G.encT + (long long)(mi - htiles) * 2048;
-    const long long b_off = out_job ? G.dout : G.gaT + ((long long)l * MTp + 4 * strip) * 2048;
+    if (J.mi < J.htiles) a_off = G.hT + ((long long)(J.l - 1) * MTp + J.mi) * 2048;
+    else if (!bias_job) a_off = G.encT + (long long)(J.mi - J.htiles) * 2048;
+    const long long b_off = out_job ? G.dout : G.gaT + ((long long)J.l * MTp + 4 * J.strip) * 2048;
     g16frag ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (i == 0) ? (__bf16)1.f : (__bf16)0.f;
     f32x16 acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { const f32x16 z = {}; acc[j] = z; }
-    const long long ngr = A.ntiles * GEN_TG;
-    const long long t0 = ngr * blockIdx.y / A.nsplit, t1 = ngr * (blockIdx.y + 1) / A.nsplit;
+    long long t0, t1;
+    gen_dw_groups(A, t0, t1);
     struct Ops { g16frag a[2], b[4][2]; };
     auto load = [&](long long t) {
         Ops o;
-        const char *tp = A.tape16 + t * G.bytes;
+        const char *tp = A.tape + t * G.bytes;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             o.a[s] = bias_job ? ones : *reinterpret_cast<const g16frag *>(tp + a_off + s * 1024 + lane * 16);
@@ -751,16 +763,7 @@ __global__ __launch_bounds__(64) void gen_dw16_kernel(GenArgs A) {
                     if (j < nt) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c.a[s], c.b[j][s], acc[j], 0, 0, 0);
         }
     }
-    float *slab = A.slabs + (long long)blockIdx.y * A.slab_floats + Lr.slab_off;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j < nt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float *d = slab + (long long)(32 * mi + gen_row(r, h)) * Lr.outp + 128 * strip + 32 * j + i;
-                *d = A.accumulate ? *d + acc[j][r] : acc[j][r];
-            }
-        }
+    gen_dw_flush(A, J, acc, lane);
 }
 
 // layer tables + sizes of the packed image / a gradient slab / a tape tile
@@ -808,37 +811,32 @@ void gen_layout(const MlpShape &s, GenArgs *A) {
     g.e = g.bits + s.depth * mt * 256; g.dout = g.e + 128; g.bytes = g.dout + 128;
 }
 
-size_t gen_lds_bytes(const GenArgs &A, int Sx) { return (size_t)(2 * A.Wp + A.Ep) * 32 * 4 + (16 * 32 + 64) * 4 + RaySum<GEN_TG>::bytes(Sx); }
-int gen_block(const GenArgs &A) { const int mt = A.Wp / 32; return mt >= 8 ? 512 : mt >= 4 ? 256 : 128; }
-
+constexpr size_t GEN_LDS_MAX = 160 * 1024;       // LDS of a compute unit: the most one workgroup may ask for
+int gen_block(const GenArgs &A) { const int mt = A.Wp / 32; return mt >= 8 ? GEN_THREADS : mt >= 4 ? 256 : 128; }
+size_t gen_lds_bytes(const GenArgs &A) { return gen_lds(A.Wp, A.Ep, A.f.Sx).total; }
 // bf16 kernels: groups a workgroup runs side by side (4 when their LDS images fit, else 2) and the LDS bytes of that choice
-size_t gen_lds16_bytes(const GenArgs &A, int Sx, int ng) { return (size_t)ng * (2 * A.Wp * 64 + A.Ep * 64) + (size_t)ng * 32 * 4 * 3 + RaySum<GEN_TG>::bytes(Sx); }
-int gen_ng16(const GenArgs &A, int Sx) { return gen_lds16_bytes(A, Sx, 4) <= 160 * 1024 ? 4 : 2; }
+size_t gen_lds16_bytes(const GenArgs &A, int ng) { return gen_lds16(A.Wp, A.Ep, A.f.Sx, ng).total; }
+int gen_ng16(const GenArgs &A) { return gen_lds16_bytes(A, 4) <= GEN_LDS_MAX ? 4 : 2; }
+size_t gen_mlp_lds(const GenArgs &A) { return A.bf16 ? gen_lds16_bytes(A, gen_ng16(A)) : gen_lds_bytes(A); }      // of the MLP kernel a call launches
 
-template <int MODE, int NG>
-int gen_launch_mlp16(const GenArgs &A, int grid, hipStream_t st) {
-    const size_t lds = gen_lds16_bytes(A, A.f.Sx, NG);
-    BHN_CHECK_ARG(lds <= 160 * 1024, "internal: general bf16 path needs %zu bytes of LDS", lds);
+// one launcher for every MLP kernel: K is the kernel, so each one has its own per-device DeviceOnce
+template <auto K>
+int gen_launch(const GenArgs &A, int grid, size_t lds, hipStream_t st) {
+    BHN_CHECK_ARG(lds <= GEN_LDS_MAX, "internal: general path needs %zu bytes of LDS", lds);
     static DeviceOnce once;
     int dev = 0;
     BHN_HIP(hipGetDevice(&dev));
-    BHN_HIP(once.run(dev, [&](int &) { return hipFuncSetAttribute((const void *)gen_mlp16_kernel<MODE, NG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }));
-    hipLaunchKernelGGL((gen_mlp16_kernel<MODE, NG>), dim3(grid), dim3(gen_block(A)), lds, st, A);
+    BHN_HIP(once.run(dev, [&](int &) { return hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEN_LDS_MAX); }));
+    hipLaunchKernelGGL(K, dim3(grid), dim3(gen_block(A)), lds, st, A);
     BHN_HIP(hipGetLastError());
     return BHN_OK;
 }
 
 template <int MODE>
 int gen_launch_mlp(const GenArgs &A, int grid, hipStream_t st) {
-    if (A.bf16) return gen_ng16(A, A.f.Sx) == 4 ? gen_launch_mlp16<MODE, 4>(A, grid, st) : gen_launch_mlp16<MODE, 2>(A, grid, st);
-    const size_t lds = gen_lds_bytes(A, A.f.Sx);
-    static DeviceOnce once;
-    int dev = 0;
-    BHN_HIP(hipGetDevice(&dev));
-    BHN_HIP(once.run(dev, [&](int &) { return hipFuncSetAttribute((const void *)gen_mlp_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }));
-    hipLaunchKernelGGL(gen_mlp_kernel<MODE>, dim3(grid), dim3(gen_block(A)), lds, st, A);
-    BHN_HIP(hipGetLastError());
-    return BHN_OK;
+    const size_t lds = gen_mlp_lds(A);
+    if (!A.bf16) return gen_launch<gen_mlp_kernel<MODE>>(A, grid, lds, st);
+    return gen_ng16(A) == 4 ? gen_launch<gen_mlp16_kernel<MODE, 4>>(A, grid, lds, st) : gen_launch<gen_mlp16_kernel<MODE, 2>>(A, grid, lds, st);
 }
 
 }  // namespace
@@ -879,15 +877,16 @@ static int gen_fill(const bhn_model *m, int32_t mode, const void *packed, const 
     return BHN_OK;
 }
 
-static size_t gen_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static int gen_grid(const GenArgs &A, long long ntiles, int dev) {
-    const size_t lds = A.bf16 ? gen_lds16_bytes(A, A.f.Sx, gen_ng16(A, A.f.Sx)) : gen_lds_bytes(A, A.f.Sx);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(160 * 1024 / lds, 2048 / gen_block(A)));
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(GEN_LDS_MAX / gen_mlp_lds(A), 2048 / gen_block(A)));
     return (int)bhn_balanced_grid(ntiles, (long long)bhn_num_cus(dev) * per_cu);
 }
-// bytes of the gradient slabs / of the tape of ALL tiles of a call
-static size_t gen_slab_bytes(const GenArgs &A) { return gen_align((size_t)A.nsplit * A.slab_floats * 4); }
-static size_t gen_tape_bytes(const GenArgs &A, long long tiles) { return (size_t)tiles * GEN_TG * (A.bf16 ? (size_t)A.g16.bytes : (size_t)A.tape_tile * 4); }
+static size_t gen_tape_bytes(const GenArgs &A, long long tiles) { return (size_t)tiles * GEN_TG * (A.bf16 ? (size_t)A.g16.bytes : (size_t)A.tape_tile * 4); }    // of `tiles` tiles
+struct GenWorkspace { size_t slab_bytes; char *tape; };      // a workspace: the gradient slabs (256-byte aligned), then the tape (no workspace: the bytes alone)
+static GenWorkspace gen_workspace(const GenArgs &A, void *workspace) {
+    const size_t slab_bytes = ((size_t)A.nsplit * A.slab_floats * 4 + 255) & ~(size_t)255;
+    return {slab_bytes, workspace ? reinterpret_cast<char *>(workspace) + slab_bytes : nullptr};
+}
 
 // bhn_predict_fwd / bhn_render_fwd; with a workspace that holds the whole tape (bhn_render_fwd_train): the render that records it
 int gen_forward(bool render, const bhn_model *m, int32_t mode, const void *packed, const bhn_geom *geom, const bhn_frames *fr,
@@ -907,14 +906,14 @@ int gen_forward(bool render, const bhn_model *m, int32_t mode, const void *packe
         // that cannot hold slabs + that tape is refused, as on the fused paths -- a plain render here would leave the tape pair
         // nothing to read (callers check engine.fits_tape first; with less workspace the gradient comes from bhn_render_bwd)
         if (workspace) {
-            const size_t need = gen_slab_bytes(A) + gen_tape_bytes(A, A.ntiles);
+            const GenWorkspace ws = gen_workspace(A, workspace);
+            const size_t need = ws.slab_bytes + gen_tape_bytes(A, A.ntiles);
             if (workspace_bytes < need) {
                 bhn_set_error("workspace too small for the training forward's tape: %zu bytes given, %zu needed (slabs %zu + tape %zu)",
-                              workspace_bytes, need, gen_slab_bytes(A), gen_tape_bytes(A, A.ntiles));
+                              workspace_bytes, need, ws.slab_bytes, gen_tape_bytes(A, A.ntiles));
                 return BHN_EWORKSPACE;
             }
-            A.tape = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + gen_slab_bytes(A));
-            A.tape16 = reinterpret_cast<char *>(A.tape);
+            A.tape = ws.tape;
             return gen_launch_mlp<GEN_RECORD>(A, grid, st);
         }
         return gen_launch_mlp<GEN_RENDER>(A, grid, st);
@@ -935,7 +934,7 @@ size_t gen_bwd_workspace_bytes(const MlpShape &s, int32_t mode, int32_t B, int64
     gen_layout(s, &A);
     A.bf16 = mode == BHN_BF16 ? 1 : 0;
     const long long tiles = ((P + 31) / 32 + GEN_TG - 1) / GEN_TG * B;
-    return gen_slab_bytes(A) + gen_tape_bytes(A, tiles);
+    return gen_workspace(A, nullptr).slab_bytes + gen_tape_bytes(A, tiles);
 }
 
 // tape_only: bhn_render_bwd_tape (the tape of the whole call was recorded by gen_forward); else bhn_render_bwd (recompute, chunks)
@@ -949,7 +948,8 @@ int gen_backward(bool tape_only, const bhn_model *m, int32_t mode, const void *p
     int dev = 0;
     BHN_HIP(hipGetDevice(&dev));
     BHN_CHECK_DEVICE(dev);
-    const size_t slab_bytes = gen_slab_bytes(A);
+    const GenWorkspace ws = gen_workspace(A, workspace);
+    const size_t slab_bytes = ws.slab_bytes;
     const long long min_tiles = tape_only ? A.f.total_tiles : std::min<long long>(A.f.total_tiles, GEN_MIN_CHUNK_TILES);
     if (workspace_bytes < slab_bytes + gen_tape_bytes(A, min_tiles)) {
         bhn_set_error(tape_only ? "the recorded-tape path needs a workspace for the whole tape (%zu bytes given, need >= %zu: slabs %zu + %lld groups of tape); "
@@ -959,8 +959,7 @@ int gen_backward(bool tape_only, const bhn_model *m, int32_t mode, const void *p
         return BHN_EWORKSPACE;
     }
     A.slabs = reinterpret_cast<float *>(workspace);
-    A.tape = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + slab_bytes);
-    A.tape16 = reinterpret_cast<char *>(A.tape);
+    A.tape = ws.tape;
     A.dimages = dimages;
     A.dparams = dparams;
     const long long chunk = std::min<long long>(A.f.total_tiles, (long long)((workspace_bytes - slab_bytes) / gen_tape_bytes(A, 1)));

@@ -462,7 +462,10 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     const int nbias = a.depth * W + 32;                               // (the output layer's tile is read as one 32-row tile:
     float *zero_lds = bias_lds + nbias;                               //  a full W row for it put the f32 8x256 kernel over 160 KB)
     float *wout_lds = zero_lds + 32;
-    char *id_lds = reinterpret_cast<char *>(wout_lds + W);
+    // the zero row and W_out are the delta chain's: the training forward neither fills nor reads them and keeps no room for them
+    // (host: chain_rows_bytes; with them the bf16 8x256 training forward is 288 bytes over 160 KB at four Stokes planes)
+    constexpr bool CHAIN_ROWS = MODE == MODE_CHAIN;
+    char *id_lds = reinterpret_cast<char *>(CHAIN_ROWS ? wout_lds + W : zero_lds);
     char *seg_lds = id_lds + (Pol::ELEM_BYTES == 2 ? 0 : 2 * Pol::FRAG_BYTES);   // RaySum scratch (bf16 has no identity table)
     // 8-bit tape, delta chain (no RaySum there): 8 layer scales, then one |gA|max slot per layer and wave
     float *t8_lds = reinterpret_cast<float *>(seg_lds);
@@ -496,8 +499,10 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
     em.init(id_lds);
     for (int i = tid; i < nbias; i += Pol::NTHREADS)
         bias_lds[i] = reinterpret_cast<const float *>(a.packed + a.bias_off)[i];
-    if (tid < 32) zero_lds[tid] = 0.f;
-    for (int i = tid; i < W; i += Pol::NTHREADS) wout_lds[i] = reinterpret_cast<const float *>(a.packed + a.wout_off)[i];
+    if constexpr (CHAIN_ROWS) {
+        if (tid < 32) zero_lds[tid] = 0.f;
+        for (int i = tid; i < W; i += Pol::NTHREADS) wout_lds[i] = reinterpret_cast<const float *>(a.packed + a.wout_off)[i];
+    }
     if constexpr (ENCR) EB::fill(encblk, a.packed + a.fwd_off, a.depth, a.skip_mask);
     if constexpr (T8 && MODE == MODE_CHAIN) {
         if (tid < 8) {
@@ -2086,7 +2091,10 @@ static void bwd_plan(const MlpShape &s, long long groups_per_frame, int ncu, int
     p->rch = CAN_RES && res_chn <= 160 * 1024;
     // (x12: the resident image + the ray-sum scratch of 12 groups: 154 KB at four Stokes planes)
     const size_t res_fwd_x = p->res_fwd - RaySum<Pol::NWAVES>::bytes(Sx) + RaySum<FPol::NWAVES>::bytes(Sx);
-    p->lds_fwd = p->x12 ? res_fwd_x : p->rf ? p->res_fwd : (EncBlock<W, Pol>::ON ? lds_fwd_encr : p->lds_taped);
+    // the training forward keeps no zero row and no W_out (chain_kernel CHAIN_ROWS): its launch asks for that much less than the
+    // sums above, which go on deciding rf -- bf16 8x256 at four Stokes planes: 164,128 bytes with them, 162,976 without
+    const size_t chain_rows_bytes = 128 + (size_t)W * 4;
+    p->lds_fwd = (p->x12 ? res_fwd_x : p->rf ? p->res_fwd : (EncBlock<W, Pol>::ON ? lds_fwd_encr : p->lds_taped)) - chain_rows_bytes;
     // ga0_chain: a ring of GA0C_DIST + 1 buffers of the KS fragments the chain streams, the fixed part, 4 staging images of one tile per wave
     const size_t lds_ga0c = (size_t)(GA0C_DIST + 1) * PK::KS * Pol::FRAG_BYTES + p->lds_fixed + (size_t)4 * Pol::NWAVES * BG::TILE_BYTES;
     p->lds_chn = p->ga0c ? lds_ga0c : p->rch ? res_chn : p->lds_taped;
@@ -2273,7 +2281,8 @@ static int bwd_launch(int what, const bhn_model *m, int32_t mode, const void *pa
         }
         return hipSuccess;
     }));
-    BHN_CHECK_ARG(p.lds_taped <= 160 * 1024 && p.lds_dw <= 160 * 1024 && p.lds_chn <= 160 * 1024, "LDS budget exceeded (chain %zu / %zu, dw %zu)", p.lds_taped, p.lds_chn, p.lds_dw);
+    BHN_CHECK_ARG(p.lds_taped <= 160 * 1024 && p.lds_dw <= 160 * 1024 && p.lds_chn <= 160 * 1024 && p.lds_fwd <= 160 * 1024,
+                  "LDS budget exceeded (chain %zu / %zu, dw %zu, training forward %zu)", p.lds_taped, p.lds_chn, p.lds_dw, p.lds_fwd);
     const bool t8_cal = Pol::TAPE8 && (mode & BHN_T8_CALIBRATE);
     if (what != RUN_FWD_TRAIN) {
         rc = t8_scales<Pol>(A, t8_cal, dimages, depth, st);

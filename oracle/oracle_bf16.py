@@ -289,6 +289,16 @@ class Bf16Trainer:
         e = st['e'].clone().requires_grad_(True)
         images = ot.render(e, G.get('J'), G['g'], G['dtau'], G['Sigma'])
         dE, = torch.autograd.grad((images * dimages).sum(), e)
+        return self.grad_emission(st, dE)
+
+    def state(self, t_frames):
+        """The forward state grad_emission takes; its 'e' is the emission (b, *sp).  The ray sum and the loss carry no bf16 rounding,
+        so several upstream gradients (tests/stokes4_cases.py: one per mutant of the Stokes planes) can share one forward."""
+        return self._forward(t_frames)
+
+    def grad_emission(self, st, dE):
+        """The backward from dE = d loss / d emission (b, *sp) on the forward `st` -> [dK_0..dK_D, db_0..db_D]: grad_linear's
+        arithmetic from its dE on."""
         e = st['e']
         dout = torch.where(e != 0, dE * e * (1.0 - e), torch.zeros_like(e)).reshape(-1)
         grads_k, grads_b = self._backward(st, round_f32(dout, self.rounding))

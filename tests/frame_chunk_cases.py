@@ -26,6 +26,7 @@ CASES = {
     '4x256 f32 S3 dense 144':    (4, 256, 'f32', 3, 'dense 144', 3, (2,)),
     '4x64 f32 S0 dense 96':      (4, 64, 'f32', 0, 'dense 96', 3, (1,)),
     '8x32 f32 S0 dense 96':      (8, 32, 'f32', 0, 'dense 96', 3, (1,)),
+    '4x256 f32 S4 dense 96':     (4, 256, 'f32', 4, 'dense 96', 3, (2,)),           # four planes: pass 2 reads dimages at 2 * 4 * R
 }
 # the problems of test_gpu_backward.test_frame_group_taped_step_equals_full_step's bf16 cases (three frames, groups of 2 + 1)
 STEP_CASES = {'4x128 S0 dense 96': (4, 128, 'bf16', 0, 'dense 96', 3, ()), '4x256 S0 dense 96': (4, 256, 'bf16', 0, 'dense 96', 3, ())}

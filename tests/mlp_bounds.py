@@ -62,6 +62,8 @@ RANDOM_SHAPES = [(256, 4, 0, 3), (128, 4, 3, 3), (64, 8, 2, 3), (32, 6, 0, 3), (
                  (32, 3, 0, 3), (64, 2, 3, 2), (256, 5, 0, 3), (256, 8, 0, 3), (256, 8, 3, 3), (64, 4, 1, 3), (256, 6, 1, 2),
                  (256, 2, 0, 3)]           # test_random_problem_f32_and_bf16's 21 shapes + 2x256 (no W_out fold at the ga0_chain width)
 GENERAL_SHAPES = [(128, 4, 3, 5), (512, 4, 0, 3), (300, 3, 1, 6), (64, 2, 0, 7), (384, 8, 2, 4), (512, 8, 0, 8), (40, 5, 3, 10)]
+# Four Stokes planes (tests/stokes4_cases.py: what each shape is there for, with the LDS bytes of its tightest kernel at Sx = 4)
+STOKES4_SHAPES = [(128, 4, 4, 3), (256, 4, 4, 3), (256, 8, 4, 3), (64, 6, 4, 3), (32, 3, 4, 3), (256, 2, 4, 3), (288, 4, 4, 3), (512, 4, 4, 6)]
 # (depth, width) of the forms of the bf16 dW kernel's layer depth-1 job (fused_bwd.hip dw_kernel) that the shapes above leave out at a
 # kernel width.  With do_skip the form follows from the depth: 3 = skip-concat into layer 2 and into the output layer, 4 = into layer
 # 3, 5 = into the output layer only, 6 = neither.  RANDOM_SHAPES has depth 3 at width 32 only and no depth 5 (or 7) at width 32.
@@ -133,6 +135,25 @@ OBSERVED = {
     'config 2 subset masked':      (0.00018, 0.00014, 2.6e-07, 6.6e-05, 0.00013),
     'config 2 subset all_active':  (0.00015, 0.00015, 2.6e-06, 3.6e-05, 0.00011),
     'config 5 subset lc S3':       (0.00032, 0.00013, 5.7e-06, 5.6e-05, 0.00011),
+    # four Stokes planes (tests/stokes4_cases.py, test_gpu_stokes4): image, gradient and worst tensor as every case prints them -- the
+    # worst of its routes; emission and loss are not taken there (None)
+    '4x128 S4 deg3':               (0.000128, None, None, 3.80e-05, 8.64e-05),
+    '4x256 S4 deg3':               (0.000323, None, None, 4.43e-05, 7.83e-05),
+    '8x256 S4 deg3':               (0.000248, None, None, 0.000125, 0.00034),
+    '6x64 S4 deg3':                (0.000216, None, None, 7.82e-05, 0.000254),
+    '3x32 S4 deg3':                (6.49e-07, None, None, 1.29e-07, 1.78e-07),
+    '2x256 S4 deg3':               (6.36e-05, None, None, 1.50e-05, 4.95e-05),
+    '4x288 S4 deg3':               (0.00019, None, None, 0.000478, 0.000923),
+    '4x512 S4 deg6':               (0.00016, None, None, 0.00188, 0.00263),
+    '4x128 S4 deg3 lc':            (0.000128, None, None, 6.15e-06, 1.27e-05),
+    '4x128 S4 dense 96':           (0.000149, None, None, 7.97e-05, 0.000297),
+    '4x128 S4 compacted':          (0.000123, None, None, 0.000121, 0.000245),
+    '4x128 S4 span2':              (0.000302, None, None, 6.15e-05, 0.000139),
+    '4x128 S4 x12':                (8.25e-05, None, None, 3.75e-05, 8.47e-05),
+    '4x256 S4 ragged':             (0.00014, None, None, 7.27e-05, 0.000137),
+    '8x256 S4 ragged':             (0.000334, None, None, 0.0012, 0.0026),
+    '6x64 S4 ragged':              (9.03e-05, None, None, 2.96e-05, 4.27e-05),
+    '4x288 S4 ragged':             (0.00016, None, None, 0.000105, 0.000286),
 }
 FIELDS = ('image', 'emission', 'loss', 'grad', 'tensor')
 # required bounds (20x under the float64 comparisons' 1e-2 images / 6e-2 and 2e-2 gradient L2); 'deep' (8 hidden layers at width

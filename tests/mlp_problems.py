@@ -45,9 +45,18 @@ def tilted_ray_grid(H, W, G, jitter=(0.0, 0.0, 0.0)):
 
 
 def stokes_factors(rng, shape, S):
-    """J (S, *shape) from two draws, I and chi, whatever S > 0 is."""
+    """J (S, *shape), 0 < S <= 4 (bhn_geom.S <= 4; anything else raises): I and chi are drawn whatever S is, so the draws that follow
+    do not depend on S <= 3; the circular row V = I U(-0.5, 0.5) is drawn after them and only for S = 4.  Linear fraction 0.85:
+    Q^2 + U^2 + V^2 <= (0.85^2 + 0.5^2) I^2 = 0.9725 I^2."""
+    if not 0 < S <= 4:
+        raise ValueError('stokes_factors: S = %r, the kernels take 1 .. 4 Stokes planes' % (S,))
     I = rng.uniform(0.5, 1.5, shape); chi = rng.uniform(0, np.pi, shape)
-    return np.stack([I, 0.85 * I * np.cos(2 * chi), 0.85 * I * np.sin(2 * chi)])[:S]
+    rows = [I, 0.85 * I * np.cos(2 * chi), 0.85 * I * np.sin(2 * chi)][:S]
+    if S == 4:
+        rows.append(I * rng.uniform(-0.5, 0.5, shape))
+    J = np.stack(rows)
+    assert J.shape[0] == S
+    return J
 
 
 def oracle_inputs_of(tree, geo, t_injection, dom, deg, depth, do_skip=None, t_start_obs=0.0, GM_c3=onp.GM_C3_SGRA_HR, dtype=torch.float64):

@@ -28,6 +28,7 @@ PINNED = {
     '4x256 f32 S3 dense 144': '708830c8f2085e65',
     '4x64 f32 S0 dense 96': '77501f7952377b39',
     '8x32 f32 S0 dense 96': '7481d6f9bbeedf53',
+    '4x256 f32 S4 dense 96': 'ab1775e35b924085',       # (added with its V row; it has no earlier draw)
     '4x128 S0 dense 96': '380f785ce029706e',
     '4x256 S0 dense 96': 'f5a037d7b2511d6f',
 }

@@ -8,7 +8,7 @@ import hashlib
 import numpy as np
 import pytest
 
-from mlp_bounds import GENERAL_SHAPES, RANDOM_SHAPES
+from mlp_bounds import GENERAL_SHAPES, RANDOM_SHAPES, STOKES4_SHAPES
 from mlp_problems import random_problem_inputs, small_problem
 
 # (width, depth, S, posenc degree): sha256, first 16 hex digits
@@ -42,6 +42,17 @@ RANDOM_PINS = {
     (384, 8, 2, 4): 'dc05eaa8bf54e2cf',
     (512, 8, 0, 8): 'b4637d3d6fdcdcc1',
     (40, 5, 3, 10): 'd4c6d83affe3353a',
+}
+# four Stokes planes (mlp_bounds.STOKES4_SHAPES): the V row is drawn behind I and chi, so the pins above did not move when it came
+STOKES4_PINS = {
+    (128, 4, 4, 3): 'e29278871998b27a',
+    (256, 4, 4, 3): '9a4e0c18744d3474',
+    (256, 8, 4, 3): 'a41ab502b08cd0bf',
+    (64, 6, 4, 3): '19b91bf313a4d472',
+    (32, 3, 4, 3): '751874b9adbeeaf4',
+    (256, 2, 4, 3): 'a309f539718ae4d2',
+    (288, 4, 4, 3): 'daab2b97ed5026ca',
+    (512, 4, 4, 6): 'fef090c9a24001ce',
 }
 # the tie adjudications: the tied ray samples dropped (Doppler weight 0), every weight nudged by a relative 1e-4
 VARIANT_PINS = {
@@ -88,11 +99,14 @@ def small_checksum(ks, bs, geom, hp, tf, tg):
 
 def test_pins_cover_the_suite():
     assert list(RANDOM_PINS) == RANDOM_SHAPES + GENERAL_SHAPES
+    assert list(STOKES4_PINS) == STOKES4_SHAPES and all(s[2] == 4 for s in STOKES4_SHAPES)
 
 
-@pytest.mark.parametrize('shape', list(RANDOM_PINS), ids=lambda s: '%dx%d-S%d-deg%d' % (s[1], s[0], s[2], s[3]))
+@pytest.mark.parametrize('shape', list(RANDOM_PINS) + list(STOKES4_PINS), ids=lambda s: '%dx%d-S%d-deg%d' % (s[1], s[0], s[2], s[3]))
 def test_random_problem_is_drawn_bit_for_bit(shape):
-    assert random_checksum(random_problem_inputs(*shape)) == RANDOM_PINS[shape]
+    prob = random_problem_inputs(*shape)
+    assert prob['g']['J'].shape[:1] == (shape[2],) if shape[2] else not prob['g']['J'].ndim
+    assert random_checksum(prob) == {**RANDOM_PINS, **STOKES4_PINS}[shape]
 
 
 def test_tie_adjudication_variants_are_drawn_bit_for_bit():

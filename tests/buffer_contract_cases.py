@@ -16,6 +16,7 @@ Frames: three (frame_chunk_cases.T_FRAMES / T_INJ), pre-injection samples in fra
 import numpy as np
 
 from frame_chunk_cases import DENSE, SHELL, RAY_SETS as FC_RAY_SETS, build_problem
+from mlp_reference import linear_reference
 
 B = 3
 # name: (rays H, rays W, samples, domain)
@@ -59,12 +60,6 @@ def problem(name):
     return _PROBLEMS[name]
 
 
-def expected_flags(recipe):
-    """The engine.tape_info flags of a case's path (CASES' recipe column)."""
-    return dict(general=recipe.startswith('general'), fused128=recipe == 'fused128', ga0_chain=recipe == 'ga0_chain',
-                drop_ga=recipe in ('fold', 'ga0_chain', 't8'))
-
-
 def domain_mask(prob):
     """(H, W, G) bool: the samples inside the recovery domain (emission.py:370-373 on the un-warped coordinates)."""
     c, (_, rmin, rmax, zw) = prob['g']['coords'], prob['dom']
@@ -100,51 +95,6 @@ def check_table():
     assert RAGGED['tiny'][1] < 8 and RAGGED['x12'][1] % 12 != 0 and RAGGED['x12'][1] >= 3072
 
 
-# ---- references (computed once per case, left unchanged): the float64 oracle, or the bf16 emulator of the path that runs
-_REFS = {}
-
-
-def reference(name, recipe=None, drop=None, want_ties=False, prob=None, accum32=False):
-    """dict(emission (B, H*W*G), images (B, Sx, R), grad: the flat gradient of sum(images * dimg) in flax tree order), float64 arrays --
-    `recipe` None: oracle_torch in float64, else oracle_bf16's emulator of that recipe.  `drop` (H, W, G) bool: the problem without those
-    ray samples (Doppler weight 0: the ReLU-tie adjudication of test_gpu_frame_chunks).  want_ties: instead the (H, W, G) bool of the
-    ray samples that reach the image and have a ReLU tie on the reference's own forward.  `prob`: the problem of another case table
-    (general_path_cases; `name` must not be one of CASES), which may hold do_skip = False; accum32: the emulator accumulating in float32."""
-    from conftest import relu_tie_count
-    from frame_chunk_cases import T_INJ
-    from mlp_problems import oracle_inputs, t64, without_samples
-    from oracle import oracle_bf16 as ob, oracle_torch as ot
-    key = (name, recipe, drop is not None, want_ties, accum32)
-    if key in _REFS:
-        return _REFS[key]
-    assert prob is None or name not in CASES
-    prob = problem(name) if prob is None else prob
-    g, S, dom = without_samples(prob['g'], drop), prob['S'], prob['dom']
-    ks, bs, geom_t, hp = oracle_inputs(g)
-    do_skip = prob.get('do_skip', True)
-    hp = hp if do_skip else dict(hp, do_skip=False)
-    tf = t64(g['t_frames'])
-    d_em = prob['dimg'].reshape((prob['B'], max(S, 1)) + prob['spatial'])
-    d_em = d_em if S else d_em[:, 0]
-    em = None if recipe is None else ob.Bf16Trainer(ks, bs, geom_t, hp, recipe, accum32=accum32)
-    if want_ties:
-        if em is None and not do_skip:         # (relu_tie_count walks the skip network: its criterion on the float64 model without the skips)
-            ties = ob.Bf16Trainer(ks, bs, geom_t, hp, rounding=False).relu_tie_points(tf)
-        else:
-            ties = relu_tie_count(g, return_points=True)[1] if em is None else em.relu_tie_points(tf)
-        out = ties & (g['g'] != 0)
-        out.setflags(write=False)
-    else:
-        if em is None:
-            e = ot.predictor(ks, bs, tf, geom_t['coords'], geom_t['Omega'], 0.0, geom_t['t_geos'], T_INJ, hp['GM_c3'], dom[0], dom[1], dom[2],
-                             dom[3], posenc_deg=prob['deg'], net_depth=prob['depth'], do_skip=do_skip)
-            grads = ot.grad_linear(ks, bs, geom_t, hp, tf, d_em)
-        else:
-            e = em.emission(tf)
-            grads = em.grad_linear(tf, d_em)
-        img = ot.render(e, geom_t['J'], geom_t['g'], geom_t['dtau'], geom_t['Sigma'])
-        out = dict(emission=e.detach().numpy().reshape(prob['B'], -1), images=img.detach().numpy().reshape(prob['B'], max(S, 1), -1), grad=ob.flat(grads))
-        for v in out.values():
-            v.setflags(write=False)
-    _REFS[key] = out
-    return out
+# ---- references: mlp_reference.linear_reference, the float64 oracle (recipe None) or the bf16 emulator of the path that runs
+def reference(name, recipe=None, drop=None, want_ties=False):
+    return linear_reference('buffer contract', name, problem(name), recipe, drop, want_ties=want_ties)

@@ -19,6 +19,7 @@ import numpy as np
 import buffer_contract_cases as bc
 from frame_chunk_cases import DENSE, SHELL, build_problem
 from mlp_bounds import GTOL, L2TOL, caps_of
+from mlp_reference import linear_reference
 
 RAY_SETS = dict({k: bc.RAY_SETS[k] for k in ('tiny', 'ragged', 'compacted')},
                 **{'direct 64': (7, 5, 64, DENSE), 'direct 33': (11, 5, 33, DENSE), 'long 257': (3, 3, 257, DENSE),
@@ -68,9 +69,8 @@ def problem(name):
 
 
 def reference(name, mode, drop=None, want_ties=False, accum32=False):
-    """buffer_contract_cases.reference of a case: the float64 oracle for mode 'f32', the emulator of the `general` recipe for 'bf16'."""
-    return bc.reference('general path ' + name, None if mode == 'f32' else 'general', drop=drop, want_ties=want_ties, prob=problem(name),
-                        accum32=accum32)
+    """mlp_reference.linear_reference of a case: the float64 oracle for mode 'f32', the emulator of the `general` recipe for 'bf16'."""
+    return linear_reference('general path', name, problem(name), None if mode == 'f32' else 'general', drop, accum32, want_ties)
 
 
 def in_domain(name):

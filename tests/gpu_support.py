@@ -1,5 +1,6 @@
 """What the GPU tests of the MLP and stand-alone kernels share and that needs a device: the `dev` and `lib` fixtures (a test module
-imports them by name), raw buffers for calls through the C ABI (ptr, stream_ptr, place, Out), the one device setup of a problem, and
+imports them by name), raw buffers for calls through the C ABI (ptr, stream_ptr, place, Out), the one device setup of a problem, the
+one check of the path that ran (assert_path: pure Python on engine.tape_info, held to its rules by test_mlp_harness_cpu), and
 the random-problem checks that test_gpu_backward and the fuzzers under tools/ run.  No test here."""
 import ctypes as C
 
@@ -10,6 +11,7 @@ import torch
 from conftest import golden_tree
 from mlp_bounds import GTOL, L2TOL, l2err
 from mlp_problems import RANDOM_PROBLEM_DOMAIN, RANDOM_PROBLEM_JITTER, RANDOM_PROBLEM_SHAPE, f32, random_problem, without_samples
+from oracle import oracle_bf16 as ob
 from oracle import oracle_np as onp
 
 
@@ -97,6 +99,35 @@ def device_setup(g, mode, dev, drop=None, do_skip=None):
     flat = eng.flatten(golden_tree(g))
     tM0 = E.frame_offsets(g['t_frames'], rt['t_start_obs'], rt['t_injection'], onp.GM_C3_SGRA_HR, dev)
     return pred, eng, geom, flat, tM0
+
+
+def expected_flags(recipe):
+    """The engine.tape_info flags of a path: a recipe of oracle_bf16, 't8' (the 8-bit tape: the fold, dW_0 left in the dW kernel),
+    'f32', or 'general' / 'general f32'."""
+    return dict(general=recipe.startswith('general'), fused128=recipe == 'fused128', ga0_chain=recipe == 'ga0_chain',
+                drop_ga=recipe in ('fold', 'ga0_chain', 't8'))
+
+
+def assert_path(name, eng, geom, mode, recipe, general, compact=None, tile_groups=None):
+    """The path that runs is the one the case `name` is listed (and, in the bf16 modes, emulated) for -> (flags, info) of
+    engine.tape_info.  mode 'f32', 'bf16' or 'bf16_t8'; recipe: expected_flags' (ignored in f32; the emulator has no recipe of its own
+    for 't8', which folds W_out as 'fold' does); compact: whether the layout is point-compacted; tile_groups: the 32-point groups per
+    tile of the training forward."""
+    info = eng.tape_info((geom.P_eff + 31) // 32)
+    flags = info['flags']
+    assert flags['general'] == general, (name, flags)
+    if mode == 'f32':
+        assert not (flags['fused128'] or flags['ga0_chain'] or flags['drop_ga']), (name, flags)
+    else:
+        want = expected_flags(recipe)
+        assert want['general'] == general and ob.recipe_for(flags) == ('fold' if recipe == 't8' else recipe), (name, flags, recipe)
+        assert flags['fused128'] == want['fused128'] and flags['ga0_chain'] == want['ga0_chain'], (name, flags, recipe)
+        assert general or flags['drop_ga'] == want['drop_ga'], (name, flags, recipe)      # (fused128: the fold is bwd128_kernel's own)
+    if compact is not None:
+        assert (geom.compact is not None) == compact, (name, 'layout')
+    if tile_groups is not None:
+        assert info['fwd_groups_per_tile'] == tile_groups, (name, info)
+    return flags, info
 
 
 def chi2_step(pred, flat, rt, t_frames, target, sigma, offset, scale=1.0, dt='full'):

@@ -1,7 +1,7 @@
 """The numbers and rules that more than one MLP kernel test reads: the tolerances against the float64 oracle, the figures observed
 against the bf16 emulator and the bound rule built on them, the path the library takes for a network shape, the shape lists, the
-mutant requirements and the error norms.  Plain numpy; no test here.  (The OBSERVED tables of test_gpu_frame_chunks and
-test_gpu_buffer_contract stay in those files: nothing else reads them.)"""
+mutant requirements, the error norms and the ReLU-tie adjudication of the case tables.  Plain numpy; no test here.  (The OBSERVED
+tables of test_gpu_frame_chunks and test_gpu_buffer_contract stay in those files: nothing else reads them.)"""
 import numpy as np
 
 from oracle import oracle_bf16 as ob
@@ -29,6 +29,39 @@ def relerr(a, b):
     """maxerr of anything array-like, taken in float64; an all-zero reference gives inf or 0, not a division by zero."""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+def tensor_l2(grad, ref, cuts, skip_zero):
+    """l2err of every kernel / bias tensor of a flat gradient (cuts: mlp_problems.tensor_cuts); skip_zero: 0 for a tensor whose
+    reference is identically zero, which has no relative error."""
+    return [0.0 if skip_zero and not np.linalg.norm(ref[c0:c1]) > 0 else l2err(grad[c0:c1], ref[c0:c1]) for c0, c1 in zip(cuts[:-1], cuts[1:])]
+
+
+def tensor_label(i):
+    """Tensor i of the flax order as the tests print it: K0, b0, K1, ..."""
+    return ('K%d' if i % 2 == 0 else 'b%d') % (i // 2)
+
+
+def first_difference(a, b):
+    """None when the float32 arrays are bitwise equal, else (flat index, a, b) of the first element that differs."""
+    d = np.nonzero(a.reshape(-1).view(np.uint32) != b.reshape(-1).view(np.uint32))[0]
+    return None if d.size == 0 else (int(d[0]), float(a.reshape(-1)[d[0]]), float(b.reshape(-1)[d[0]]))
+
+
+def held_or_adjudicated(label, first, within, ties, rerun, also=lambda second: True):
+    """The ReLU-tie adjudication of a case table: (whether the case holds, the figures of its second run or None).  It holds when
+    within(first); a miss is excused only if the reference's own forward has tied ray samples (ties(), called on a miss only) and
+    the same case without exactly those samples (rerun(mask): Doppler weight 0 on both sides) meets the same bounds and the
+    site's side conditions `also`.  No device access here: the site's callables do that."""
+    if within(first):
+        return True, None
+    mask = ties()
+    if not mask.any():
+        return False, None
+    second = rerun(mask)
+    ok = bool(within(second) and also(second))
+    print('relu ties (%s): %d tied ray samples taken out: %s' % (label, int(mask.sum()), 'adjudicated' if ok else 'NOT a tie'))
+    return ok, second
 
 
 # ---- the path of a network shape
@@ -198,8 +231,7 @@ def mutant_ratios(variants, b, cuts):
     for m in ob.MUTANTS:
         _, i1, g1 = variants[m]
         g1 = ob.flat(g1)
-        tens = max(l2err(g1[c0:c1], g0[c0:c1]) for c0, c1 in zip(cuts[:-1], cuts[1:]) if np.linalg.norm(g0[c0:c1]) > 0)
-        d = (l2err(g1, g0), tens, maxerr(i1.numpy(), i0))
+        d = (l2err(g1, g0), max(tensor_l2(g1, g0, cuts, True)), maxerr(i1.numpy(), i0))
         out[m] = d + (max(d[0] / b['grad'], d[1] / b['tensor'], d[2] / b['image']),)
     return out
 

@@ -3,6 +3,8 @@ frame_chunk_cases.build_problem, the oracle's inputs from a problem in the layou
 gradient in flax tree order, the tie adjudication's dropped samples, the small problem of the identity tests and the config-scale
 problem of the full-size tests.  CPU only (no CUDA call, at import or later); no test here.  tests/test_mlp_problems_cpu.py pins what
 the builders draw by sha256."""
+import hashlib
+
 import numpy as np
 import torch
 
@@ -113,6 +115,18 @@ def without_samples(g, drop):
     """The g5-layout problem without the ray samples `drop` (H, W, G) bool: Doppler weight 0 on both sides, so they no longer reach the
     image (the ReLU-tie adjudication); `drop` None: the problem itself."""
     return g if drop is None else dict(g, g=np.where(drop, 0.0, g['g']))
+
+
+def problem_checksum(prob):
+    """sha256 (first 16 hex digits) of a frame_chunk_cases.build_problem dict: what the CPU tests of the case tables pin."""
+    h = hashlib.sha256()
+    for k in sorted(prob['g']):
+        a = np.ascontiguousarray(np.asarray(prob['g'][k], dtype=np.float64))
+        h.update(k.encode()); h.update(repr(a.shape).encode()); h.update(a.tobytes())
+    d = prob['dimg'].numpy()
+    h.update(repr((d.shape, prob['dom'], prob['depth'], prob['width'], prob['S'], prob['B'], prob['spatial'])).encode())
+    h.update(np.ascontiguousarray(d).tobytes())
+    return h.hexdigest()[:16]
 
 
 def random_problem_inputs(width, depth, S, deg, nudge=0.0, drop_ties=False, shape=RANDOM_PROBLEM_SHAPE, domain=RANDOM_PROBLEM_DOMAIN,

@@ -1,6 +1,6 @@
 """The cases of the four-Stokes-plane tests (test_gpu_stokes4, and test_stokes4_cases_cpu, which proves on the CPU that their bounds
-see a slip in the fourth plane): the case table, the references with their mutants, the comparator and the bounds.  NumPy and torch on
-the CPU only (no CUDA call, at import or later); no test here.
+see a slip in the fourth plane): the case table, the outputs of mlp_reference.Reference with the mutants built in, the comparator
+and the bounds.  NumPy and torch on the CPU only (no CUDA call, at import or later); no test here.
 
 S sets sizes and offsets in the kernels, and at S = 4 (bhn_geom.S <= 4, RaySum::SMAX) they are at their extremes: the ray-sum scratch
 in LDS is [NW][Sx][32] with the segment counts behind it at an Sx-dependent offset (fused_common.h RaySum::put / combine, shared by
@@ -20,15 +20,14 @@ dimages, so one forward of a reference serves the faithful result and every muta
 import numpy as np
 import torch
 
-from conftest import mask_tie_points, relu_tie_count
+from conftest import mask_tie_points
 from buffer_contract_cases import RAY_SETS as BC_RAY_SETS
 from frame_chunk_cases import RAY_SETS, DENSE, build_problem
 from mlp_bounds import (CAPS, GTOL, IMG_TOL, L2TOL, OBSERVED, STOKES4_SHAPES, capped_bounds, caps_of, expected_recipe, kernel_width, l2err,
-                        maxerr, problem_class)
-from mlp_problems import f32r, flat_grad, oracle_inputs, random_problem_inputs, t64, tensor_cuts, without_samples
-from oracle import oracle_bf16 as ob
+                        maxerr, problem_class, tensor_l2)
+from mlp_problems import f32r, random_problem_inputs, t64, tensor_cuts, without_samples
+from mlp_reference import dropped, point_reference
 from oracle import oracle_np as onp
-from oracle import oracle_torch as ot
 
 S = 4
 
@@ -104,7 +103,7 @@ def case_recipe(name, mode):
 
 
 # ---- the problems
-_PROBLEMS, _REFS = {}, {}
+_PROBLEMS = {}
 
 
 def _span2_problem(c):
@@ -164,81 +163,10 @@ def three_planes(g):
     return dict(g, J=g['J'][:3])
 
 
-def dropped(prob, drop):
-    """The problem without the ray samples `drop` (H, W, G): Doppler weight 0 on both sides (the ReLU-tie adjudication)."""
-    return prob if drop is None else dict(prob, g=without_samples(prob['g'], drop))
-
-
-# ---- the references
-class Reference:
-    """One forward of the float64 oracle (recipe None) or of the bf16 emulator of `recipe` on a problem's g: the emission, from which
-    images(J) and grad(dimages, J) follow for any Stokes weights J (4, H, W, G) -- the render and the loss carry no bf16 rounding.
-    Only the samples inside the recovery domain are evaluated, as points of their own (sp = (N,)): the others have emission 0
-    whatever the parameters are (oracle_torch.predictor's mask), and the shell domains keep 6 to 30 % of the samples."""
-
-    def __init__(self, g, recipe=None):
-        ks, bs, geom, hp = oracle_inputs(g)
-        self.tf = t64(g['t_frames'])
-        self.J = geom['J']
-        self.recipe = recipe
-        c = geom['coords']
-        self.shape = tuple(c.shape[1:])                                  # (H, W, G)
-        r_sq = (c ** 2).sum(0)
-        keep = ~((r_sq < hp['rmin'] ** 2) | (r_sq > hp['rmax'] ** 2) | (c[2].abs() > hp['z_width']))
-        self.idx = torch.nonzero(keep.reshape(-1)).reshape(-1)
-        self.ray = torch.div(self.idx, self.shape[-1], rounding_mode='floor')
-        self.R = self.shape[0] * self.shape[1]
-        take = lambda v: v.reshape(-1)[self.idx]
-        self.w = take(geom['g'] ** 2 * geom['dtau'] * geom['Sigma'])
-        pts = dict(coords=torch.stack([take(c[i]) for i in range(3)]), Omega=take(geom['Omega']), t_geos=take(geom['t_geos']))
-        if recipe is None:
-            self.params = [p.clone().requires_grad_(True) for p in ks + bs]
-            n = len(ks)
-            self.e = ot.predictor(self.params[:n], self.params[n:], self.tf, pts['coords'], pts['Omega'], geom['t_start_obs'], pts['t_geos'],
-                                  geom['t_injection'], hp['GM_c3'], hp['scale'], hp['rmin'], hp['rmax'], hp['z_width'], hp['posenc_deg'],
-                                  hp['net_depth'])
-        else:
-            self.em = ob.Bf16Trainer(ks, bs, dict(pts, t_start_obs=geom['t_start_obs'], t_injection=geom['t_injection']), hp, recipe)
-            self.st = self.em.state(self.tf)
-            self.e = self.st['e']
-        assert tuple(self.e.shape) == (len(self.tf), len(self.idx))
-
-    def _Jw(self, J):
-        J = self.J if J is None else J
-        return J.reshape(J.shape[0], -1)[:, self.idx] * self.w[None]
-
-    def images(self, J=None):
-        """(B, 4, H, W), float64."""
-        Jw = self._Jw(J)
-        out = torch.zeros((len(self.tf), Jw.shape[0], self.R), dtype=torch.float64)
-        out.index_add_(2, self.ray, self.e.detach()[:, None, :] * Jw[None])
-        return out.reshape(out.shape[:2] + self.shape[:2])
-
-    def grad(self, dimages, J=None):
-        """The gradient of sum(images(J) * dimages), flat in flax tree order."""
-        Jw = self._Jw(J)
-        dE = (dimages.reshape(dimages.shape[0], Jw.shape[0], self.R)[:, :, self.ray] * Jw[None]).sum(dim=1)
-        if self.recipe is None:
-            return flat_grad(list(torch.autograd.grad(self.e, self.params, grad_outputs=dE, retain_graph=True)))
-        return ob.flat(self.em.grad_emission(self.st, dE))
-
-    def relu_ties(self, g):
-        """(H, W, G) bool: the ray samples that reach the image and have a ReLU tie on this reference's own forward."""
-        if self.recipe is None:
-            ties = relu_tie_count(g, return_points=True)[1]
-        else:
-            ties = np.zeros(int(np.prod(self.shape)), dtype=bool)
-            ties[self.idx.numpy()] = self.em.relu_tie_points(self.tf)
-            ties = ties.reshape(self.shape)
-        return ties & (np.broadcast_to(g['g'], ties.shape) != 0)
-
-
+# ---- the references (mlp_reference.Reference: the emission once on the in-domain points, images and gradient for any J)
 def reference(name, recipe, drop=None, prob=None):
     """The Reference of a case, made once (`prob`: while problem() builds it)."""
-    key = (name, recipe, drop is not None)
-    if key not in _REFS:
-        _REFS[key] = Reference(dropped(problem(name) if prob is None else prob, drop)['g'], recipe)
-    return _REFS[key]
+    return point_reference('stokes4', name, problem(name) if prob is None else prob, recipe, drop)
 
 
 def stride3(x):
@@ -293,8 +221,8 @@ def figures(out, ref64, ref_abs, cuts, emu=None):
     for a bf16 run, against the emulator `emu` -- em_image (whole image), em_grad, em_tensor (worst kernel / bias tensor)."""
     f = dict(planes=plane_figures(out['images'], ref64['images'], ref_abs), gmax=maxerr(out['grad'], ref64['grad']), grad=l2err(out['grad'], ref64['grad']))
     if emu is not None:
-        tens = [l2err(out['grad'][c0:c1], emu['grad'][c0:c1]) for c0, c1 in zip(cuts[:-1], cuts[1:]) if np.linalg.norm(emu['grad'][c0:c1]) > 0]
-        f.update(em_image=maxerr(out['images'], emu['images']), em_grad=l2err(out['grad'], emu['grad']), em_tensor=max(tens))
+        f.update(em_image=maxerr(out['images'], emu['images']), em_grad=l2err(out['grad'], emu['grad']),
+                 em_tensor=max(tensor_l2(out['grad'], emu['grad'], cuts, True)))
     return f
 
 

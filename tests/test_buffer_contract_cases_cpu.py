@@ -1,8 +1,6 @@
 """CPU checks of what test_gpu_buffer_contract stands on: the case table's ray sets are what it says they are, every case's float64
 reference is non-zero in every tensor, the problem builder factored out of frame_chunk_cases still draws the frame-chunk problems bit
 for bit, the fill bytes decode as the GPU module says, and (host-only bhn_tape_info) every case takes the path it is listed under."""
-import hashlib
-
 import numpy as np
 import pytest
 import torch
@@ -10,11 +8,12 @@ import torch
 import buffer_contract_cases as bc
 import frame_chunk_cases as fc
 from conftest import mask_tie_points
-from mlp_problems import tensor_cuts
+from gpu_support import expected_flags
+from mlp_problems import problem_checksum, tensor_cuts
 from oracle import oracle_np as onp
 
 # sha256 (first 16 hex digits) of every frame_chunk_cases problem as the builder drew it BEFORE build_problem was factored out of
-# problem() (problem_checksum below, run on the parent commit's module)
+# problem() (mlp_problems.problem_checksum, run on the parent commit's module)
 PINNED = {
     '4x128 S0 dense 144': 'c82d0a40658659db',
     '4x128 S3 compacted': '4771f6dfb7cd9de7',
@@ -32,17 +31,6 @@ PINNED = {
     '4x128 S0 dense 96': '380f785ce029706e',
     '4x256 S0 dense 96': 'f5a037d7b2511d6f',
 }
-
-
-def problem_checksum(prob):
-    h = hashlib.sha256()
-    for k in sorted(prob['g']):
-        a = np.ascontiguousarray(np.asarray(prob['g'][k], dtype=np.float64))
-        h.update(k.encode()); h.update(repr(a.shape).encode()); h.update(a.tobytes())
-    d = prob['dimg'].numpy()
-    h.update(repr((d.shape, prob['dom'], prob['depth'], prob['width'], prob['S'], prob['B'], prob['spatial'])).encode())
-    h.update(np.ascontiguousarray(d).tobytes())
-    return h.hexdigest()[:16]
 
 
 def test_builder_reproduces_the_frame_chunk_problems_bit_for_bit():
@@ -113,7 +101,7 @@ def tape_info(depth, width, deg, mode, groups):
 def test_case_takes_the_path_it_is_listed_under(name):
     depth, width, mode, S, deg, rays, recipe, nwf = bc.CASES[name]
     info = tape_info(depth, width, deg, mode, bc.ragged_properties(name)[1])
-    for k, v in bc.expected_flags(recipe).items():
+    for k, v in expected_flags(recipe).items():
         assert info['flags'][k] == v, (name, k, info['flags'])
     assert info['fwd_groups_per_tile'] == nwf, (name, info)
 

@@ -12,8 +12,7 @@ import pytest
 import general_path_cases as gp
 from general_path_cases import CASES, MODES, case_layout, problem, reference
 from mlp_bounds import caps_of, expected_recipe, l2err, maxerr
-from mlp_problems import tensor_cuts
-from test_buffer_contract_cases_cpu import problem_checksum
+from mlp_problems import problem_checksum, tensor_cuts
 
 # sha256 (first 16 hex digits) of every problem as frame_chunk_cases.build_problem drew it when the table was written
 PINNED = {

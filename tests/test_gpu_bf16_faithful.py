@@ -5,7 +5,7 @@ The float64 oracle can only hold the bf16 kernels to the bf16 QUANTISATION noise
 per cent wrong passes it.  The emulator rounds every MFMA operand to bf16 where the kernels round it, per path (its RECIPES:
 generic tape backward, W_out fold / drop_ga, ga0_chain, fused 4x128, general path), so what is left is the kernels' f32
 accumulation order and the rare bf16 rounding that order flips.  Every case checks that the library takes the path whose
-recipe it is compared with (engine.tape_info() flags), then compares images and the chi^2 loss and gradient
+recipe it is compared with (gpu_support.assert_path), then compares images and the chi^2 loss and gradient
 (network.loss_fn_image), the emission (bhn_predict_fwd) and the gradient of a random upstream image gradient through BOTH
 backward routes (render_train + render_bwd_tape, and the recompute route render_bwd).
 
@@ -19,9 +19,9 @@ gradient cap).  Worst observed: goldens
 profile, and the float32-accumulating emulator reproduces the profile and the size on CPU).  Mutants of the emulator: every case
 must see the ones required_mutants names at >= 5x its bounds (the goldens and random problems in tests/test_oracle_bf16_cpu.py,
 the fused 4x128 and config 2 / 5 cases here, sharing the emulator's forward); which ones are not required, and why, is stated there.  ReLU ties are the f32 mode's: bf16 keeps f32's
-exponent range, so a relu decision flips only where the f32 accumulation flips it; they are detected with relu_tie_count's
-criterion on the EMULATOR's forward (the bf16 network's pre-activations, not the float64 one's) and adjudicated as in
-test_gpu_backward, by taking exactly the tied ray samples out (Doppler weight 0 on both sides) and requiring the same bounds.
+exponent range, so a relu decision flips only where the f32 accumulation flips it; they are detected on the EMULATOR's forward
+(mlp_reference.tie_points: the bf16 network's pre-activations, not the float64 one's) and adjudicated by
+mlp_bounds.held_or_adjudicated.
 """
 import numpy as np
 import pytest
@@ -30,11 +30,12 @@ import torch
 from conftest import golden_tree
 from buffer_contract_cases import RAY_SETS
 from frame_chunk_cases import build_problem
-from gpu_support import chi2_step, dev, device_setup, problem_of, ray_args  # noqa: F401
-from mlp_bounds import (FIELDS, GENERAL_SHAPES, LAST_JOB_SHAPES, RANDOM_SHAPES, bounds, check_mutants, expected_recipe, kernel_width, l2err as l2, maxerr as mx,
-                        mutant_ratios, problem_class)
+from gpu_support import assert_path, chi2_step, dev, device_setup, problem_of, ray_args  # noqa: F401
+from mlp_bounds import (FIELDS, GENERAL_SHAPES, LAST_JOB_SHAPES, RANDOM_SHAPES, bounds, check_mutants, expected_recipe, held_or_adjudicated, kernel_width,
+                        l2err as l2, maxerr as mx, mutant_ratios, problem_class, tensor_l2)
 from mlp_problems import (CONFIG2, CONFIG2_DOMAINS, config_problem, f32r, oracle_inputs_of, random_problem_inputs, ray_subset,
                           rays_through_domain, stokes_domain, stokes_problem, t64, targets, tensor_cuts, without_samples)
+from mlp_reference import tie_points
 from oracle import oracle_bf16 as ob
 from oracle import oracle_np as onp
 from oracle import oracle_torch as ot
@@ -55,13 +56,8 @@ def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, ta
     S = 0 if J is None else J.shape[0]
     g = problem_of(tree, geo, t_frames, t_inj, dom, deg, depth, width)
     pred, eng, geom, flat, tM0 = device_setup(g, 'bf16', dev, do_skip=do_skip)
-    if compact is not None:
-        assert (geom.compact is not None) == compact, (name, 'layout')
-    flags = eng.tape_info((geom.P_eff + 31) // 32)['flags']
     recipe = expected_recipe(depth, kernel_width(width), general)
-    assert ob.recipe_for(flags) == recipe, (name, flags, recipe)
-    assert flags['general'] == general and flags['fused128'] == (recipe == 'fused128') and flags['ga0_chain'] == (recipe == 'ga0_chain')
-    assert flags['general'] or flags['drop_ga'] == (recipe in ('fold', 'ga0_chain'))      # (fused128: the fold is bwd128_kernel's own)
+    assert_path(name, eng, geom, 'bf16', recipe, general, compact=compact)
     # the emulator
     ks, bs, geom_t, hp = oracle_inputs_of(tree, geo, t_inj, dom, deg, depth, do_skip=do_skip)
     em = ob.Bf16Trainer(ks, bs, geom_t, hp, recipe)
@@ -97,9 +93,8 @@ def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, ta
         d_em = d_em[:, 0]
     glin = ob.flat(em.grad_linear(t64(t_frames), d_em))
     # per parameter tensor (kernel_l, bias_l in flax order): the largest relative L2 error of any of them on any route
-    tens = max(l2(a[c0:c1], b[c0:c1]) for a, b in ((gdev, gref), (g_tape, glin), (g_rec, glin))
-               for c0, c1 in zip(cuts[:-1], cuts[1:]) if np.linalg.norm(b[c0:c1]) > 0)
-    ties = em.relu_tie_points(t64(t_frames)) & (np.broadcast_to(geo['g'], geo['coords'].shape[1:]) != 0)
+    tens = max(max(tensor_l2(a, b, cuts, True)) for a, b in ((gdev, gref), (g_tape, glin), (g_rec, glin)))
+    ties = tie_points(geo, em, t64(t_frames))
     r = dict(image=mx(img, img_ref), emission=l2(emis, emis_ref), loss=abs(loss.item() - loss_ref.item()) / abs(loss_ref.item()),
              grad=max(l2(gdev, gref), l2(g_tape, glin), l2(g_rec, glin)), tensor=tens)
     print('\n[bf16 vs emulator] %-34s %-9s image %.2e  emission %.2e  loss %.2e  grad L2 %.2e (chi2 %.2e tape %.2e recompute %.2e)  '
@@ -111,23 +106,16 @@ def check_case(name, dev, tree, geo, t_frames, t_inj, dom, depth, width, deg, ta
     return r, recipe, ties
 
 
-def within(r, b):
-    return all(r[k] < b[k] for k in FIELDS)
-
-
 def check_and_adjudicate(name, cls, deg, run):
     """run(drop) -> check_case's result.  Bounds of class `cls`; where they are missed and the emulator's forward has relu ties
     (conftest.relu_tie_count's criterion on the bf16 forward), the same problem without exactly the tied ray samples must meet
     them -- otherwise the difference was not a tie and the test fails."""
     b = bounds(name, cls, deg)
     r, recipe, ties = run(None)
-    if within(r, b):
-        return r
-    assert ties.any(), (name, cls, r, b)
-    r2, _, _ = run(ties)
-    assert within(r2, b), (name, 'NOT a tie: without the %d tied samples' % int(ties.sum()), r2, 'before', r, b)
-    print('relu ties adjudicated (%s): %d tied ray samples taken out' % (name, int(ties.sum())))
-    return r2
+    ok, r2 = held_or_adjudicated(name, r, lambda r: all(r[k] < b[k] for k in FIELDS), lambda: ties, lambda ties: run(ties)[0])
+    assert ok or r2 is not None, (name, cls, r, b)
+    assert ok, (name, 'NOT a tie: without the %d tied samples' % int(ties.sum()), r2, 'before', r, b)
+    return r if r2 is None else r2
 
 
 def random_case(width, depth, S, deg):

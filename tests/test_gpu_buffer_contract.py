@@ -15,15 +15,15 @@ bhn_pack_weights, bhn_predict_fwd, bhn_render_fwd, bhn_render_fwd_train, bhn_ren
 filled workspace of the queried size) and bhn_render_bwd in a workspace of the LEAST size the call accepts (found by bisection over
 multiples of 256 bytes; a refused call returns BHN_EWORKSPACE and launches nothing), where the fused paths run one frame per pass.
 
-Asserted: the path (engine.tape_info flags, groups per tile, the ray set's remainders); every guard byte and every read-only input
+Asserted: the path (gpu_support.assert_path with the groups per tile; the ray set's remainders); every guard byte and every read-only input
 unchanged; emission, both images and all gradients BITWISE equal across the three fills (the kernels are bitwise reproducible; an
-element nobody writes is NaN under 0xFF); and, on the 0x00 run, the results against a reference outside the code under test: f32 against
+element nobody writes is NaN under 0xFF); and, on the 0x00 run, the results against mlp_reference.linear_reference: f32 against
 the float64 oracle (1e-5 of the maximum for emission and images -- times 2^(deg-5) for the images of the posenc-degree-10 case, as
 test_shapes_outside_the_fused_kernels -- and mlp_bounds' GTOL / L2TOL for the gradient against oracle_torch.grad_linear), bf16
 against the oracle_bf16 emulator of the recipe that ran inside 4x the figures observed on the MI355X (OBSERVED), capped at
 mlp_bounds' CAPS['random']; the 8-bit tape against the float64 oracle at test_tape8_mode_gradient's bounds.  ReLU ties are
-adjudicated as in test_gpu_frame_chunks (the same problem without the tied ray samples must meet the same bounds).  The taped and the
-recomputed gradient relate as the older tests hold them: bitwise on every path, the images of the training forward bitwise on the
+adjudicated by mlp_bounds.held_or_adjudicated.  The taped and the recomputed gradient relate as the older tests hold them:
+bitwise on every path, the images of the training forward bitwise on the
 general path and within test_taped_training_path_equals_recompute_path's rtol 1e-6 / atol 1e-7 of the maximum on the fused ones; the
 least-workspace gradient equals the all-at-once one per tensor at test_gpu_frame_chunks' rtol 1e-5 / atol 1e-6 of the tensor's maximum.
 The 8-bit tape's chunked call calibrates on frame 0 only, so it is held to the float64 oracle, not to the all-at-once call (as
@@ -36,12 +36,12 @@ import pytest
 import torch
 
 import buffer_contract_cases as bc
-from buffer_contract_cases import CASES, expected_flags, problem, reference
-from gpu_support import dev, device_setup  # noqa: F401
+from buffer_contract_cases import CASES, problem, reference
+from gpu_support import assert_path, dev, device_setup, expected_flags  # noqa: F401
 from guarded import Guarded
-from mlp_bounds import GTOL, IMG_TOL, L2TOL, TOL, capped_bounds, caps_of, l2err, maxerr as mx
+from mlp_bounds import (GTOL, IMG_TOL, L2TOL, TOL, capped_bounds, caps_of, first_difference, held_or_adjudicated, l2err, maxerr as mx, tensor_l2,
+                        tensor_label)
 from mlp_problems import tensor_cuts
-from oracle import oracle_bf16 as ob
 
 pytestmark = pytest.mark.gpu
 
@@ -177,12 +177,6 @@ def run_sequence(dev, name, fill, su, least):
     return out, bad
 
 
-def first_difference(a, b):
-    """None when the float32 arrays are bitwise equal, else (flat index, a, b) of the first element that differs."""
-    d = np.nonzero(a.reshape(-1).view(np.uint32) != b.reshape(-1).view(np.uint32))[0]
-    return None if d.size == 0 else (int(d[0]), float(a.reshape(-1)[d[0]]), float(b.reshape(-1)[d[0]]))
-
-
 _RUNS = {}
 
 
@@ -200,8 +194,7 @@ def evaluate(dev, name):
     for fill in FILLS:
         runs[fill], b = run_sequence(dev, name, fill, su, least)
         bad += b
-    info = eng.tape_info((su['geom'].P_eff + 31) // 32)
-    _RUNS[name] = dict(su=su, least=least, one=one, q=q, two_refused=two_refused, runs=runs, bad=bad, info=info)
+    _RUNS[name] = dict(su=su, least=least, one=one, q=q, two_refused=two_refused, runs=runs, bad=bad)
     return _RUNS[name]
 
 
@@ -211,16 +204,13 @@ def test_path_and_least_workspace(dev, name):
     accepts is no larger than the one-frame query (general path: it is slabs + 16 groups of tape, whatever a frame holds)."""
     depth, width, mode, S, deg, rays, recipe, nwf = CASES[name]
     r = evaluate(dev, name)
-    su, info, q = r['su'], r['info'], r['q']
-    geom, flags = su['geom'], info['flags']
-    for k, v in expected_flags(recipe).items():
-        assert flags[k] == v, (name, k, flags)
-    if mode == 'bf16':
-        assert ob.recipe_for(flags) == recipe, (name, flags)
-    assert info['fwd_groups_per_tile'] == nwf, (name, info)
+    su, q = r['su'], r['q']
+    geom = su['geom']
     npts, groups, m8, m12, last = bc.RAGGED[rays]
     compact = rays.startswith('compacted')
-    assert (geom.compact is not None) == compact and geom.P_eff == 32 * groups
+    flags, _ = assert_path(name, su['eng'], geom, mode, recipe, recipe.startswith('general'), compact=compact, tile_groups=nwf)
+    assert flags['drop_ga'] == expected_flags(recipe)['drop_ga'], (name, flags)      # (here on the general path too, which assert_path leaves open)
+    assert geom.P_eff == 32 * groups
     assert (geom.compact['n'] if compact else geom.P) == npts and npts % 32 == last % 32
     assert (groups % 8, groups % 12) == (m8, m12)
     assert su['npts'] == (32 * groups if compact else npts)
@@ -259,7 +249,7 @@ def compare(name, out, ref, su):
     cuts = tensor_cuts(prob['g'])
     gref = ref['grad']
     routes = {k: out[k].astype(np.float64) for k in ('grad_tape', 'grad_rec', 'grad_least')}
-    tens = [max(l2err(g[c0:c1], gref[c0:c1]) for g in routes.values()) for c0, c1 in zip(cuts[:-1], cuts[1:])]
+    tens = np.max([tensor_l2(g, gref, cuts, False) for g in routes.values()], axis=0)
     return dict(emission_max=mx(e, e_ref), emission=l2err(e, e_ref),
                 image=max(mx(out[k].reshape(ref['images'].shape).astype(np.float64), ref['images']) for k in ('images', 'images_train')),
                 grad=max(l2err(g, gref) for g in routes.values()), gmax=max(mx(g, gref) for g in routes.values()),
@@ -299,22 +289,19 @@ def test_results_against_reference_and_between_routes(dev, name):
         bnd = bf16_bounds(name)
         ok = lambda f: all(f[key] < bnd[key] for key in FIELDS)
     f = compare(name, out, reference(name, ref_recipe), su)
-    label = lambda i: ('K%d' if i % 2 == 0 else 'b%d') % (i // 2)
     line = lambda f: ('vs %s: image %.2e  emission max %.2e L2 %.2e  gradient L2 %.2e max %.2e  worst tensor %.2e (%s)   least workspace vs all at '
                       'once %.2f of the bound' % ('emulator' if ref_recipe else 'f64 oracle', f['image'], f['emission_max'], f['emission'], f['grad'],
-                                                  f['gmax'], f['tensor'], label(f['worst']), vs_full))
+                                                  f['gmax'], f['tensor'], tensor_label(f['worst']), vs_full))
     print('\n[buffer contract] %-26s %-11s %s' % (name, recipe, line(f)))
     if mode == 'bf16':
         print("    %-28s(%.2e, %.2e, %.2e, %.2e)," % (repr(name) + ':', f['image'], f['emission'], f['grad'], f['tensor']))
-    good = ok(f)
-    if not good:
-        # a ReLU tie only explains it if the same problem without exactly the tied ray samples meets the same bounds
-        ties = reference(name, ref_recipe, want_ties=True)
-        if ties.any():
-            su2 = setup(dev, name, drop=ties)
-            su2['packed0'] = su['packed0']
-            out2, bad2 = run_sequence(dev, name, 0x00, su2, r['least'])
-            f2 = compare(name, out2, reference(name, ref_recipe, drop=ties), su2)
-            good = ok(f2) and not bad2
-            print('relu ties (%s): %d tied ray samples taken out: %s   %s' % (name, int(ties.sum()), 'adjudicated' if good else 'NOT a tie', line(f2)))
+
+    def rerun(ties):
+        su2 = setup(dev, name, drop=ties)
+        su2['packed0'] = su['packed0']
+        out2, bad2 = run_sequence(dev, name, 0x00, su2, r['least'])
+        f2 = compare(name, out2, reference(name, ref_recipe, drop=ties), su2)
+        print('    without the tied ray samples: %s' % line(f2))
+        return dict(f2, bad=bad2)
+    good, _ = held_or_adjudicated(name, f, ok, lambda: reference(name, ref_recipe, want_ties=True), rerun, lambda f2: not f2['bad'])
     assert good, (name, line(f))

@@ -4,11 +4,10 @@ host offsets tM0 and dimages, clamps the later grids to the first pass's, calibr
 slabs once at the end; every kernel flush reads its slab back and adds.  A share that is stored instead of added changes ONE tensor,
 far below the bf16 mode's bounds against the float64 oracle -- so each case here holds the CHUNKED gradient
 
-* to its reference: f32 against the float64 linear-gradient oracle (oracle_torch.grad_linear) inside mlp_bounds' GTOL /
-  L2TOL (2e-5), bf16 against the rounding-faithful emulator of the path that ran (oracle_bf16, the recipe asserted through
-  engine.tape_info) inside 4x the figures observed on the MI355X (OBSERVED; the kernels are bitwise reproducible), capped at
-  mlp_bounds' CAPS['random'] (3e-3 whole gradient, 6e-3 worst tensor); ReLU ties adjudicated as there (the tied ray
-  samples get Doppler weight 0 on both sides, same bounds);
+* to its reference (mlp_reference.linear_reference's gradient): f32 against the float64 oracle inside mlp_bounds' GTOL / L2TOL
+  (2e-5), bf16 against the emulator of the path that ran (gpu_support.assert_path) inside 4x the figures observed on the MI355X
+  (OBSERVED; the kernels are bitwise reproducible), capped at mlp_bounds' CAPS['random'] (3e-3 whole gradient, 6e-3 worst tensor);
+  ReLU ties adjudicated by mlp_bounds.held_or_adjudicated;
 * to the all-at-once call on another predictor, per parameter tensor, rtol 1e-5 / atol 1e-6 of the tensor's largest entry
   (test_workspace_frame_chunking_is_equivalent's bound: the recomputed tape is the same point by point, only the order of the f32
   sums differs);
@@ -23,13 +22,11 @@ in the first frames, dimages differs in every frame and Stokes plane: a wrong fr
 import numpy as np
 import pytest
 
-from conftest import relu_tie_count
 from frame_chunk_cases import CASES, RAY_SETS, problem
-from gpu_support import dev, device_setup  # noqa: F401
-from mlp_bounds import CAPS, GTOL, L2TOL, capped_bounds, expected_recipe, kernel_width, l2err
-from mlp_problems import oracle_inputs, t64, tensor_cuts, without_samples
-from oracle import oracle_bf16 as ob
-from oracle import oracle_torch as ot
+from gpu_support import assert_path, dev, device_setup  # noqa: F401
+from mlp_bounds import CAPS, GTOL, L2TOL, capped_bounds, expected_recipe, held_or_adjudicated, kernel_width, l2err, tensor_l2, tensor_label
+from mlp_problems import tensor_cuts
+from mlp_reference import dropped, linear_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -59,45 +56,16 @@ def bf16_bounds(key):
     return b['grad'], b['tensor']
 
 
-_REFS, _RUNS = {}, {}
+_RUNS = {}
 
 
-def dropped(prob, drop):
-    """The problem without the ray samples `drop` (H, W, G): Doppler weight 0 on both sides (the ReLU-tie adjudication)."""
-    return dict(prob, g=without_samples(prob['g'], drop))
-
-
-def reference(name, recipe, drop=None, want_ties=False):
-    """The reference gradient of a case, computed once and left unchanged: `recipe` None = the float64 oracle, else the bf16 emulator
-    of that path -> flat float64 gradient in flax tree order.  want_ties: instead the boolean (H, W, G) of the ray samples that reach
-    the image and have a ReLU tie (conftest.relu_tie_count's criterion on the reference's own forward)."""
-    key = (name, recipe, drop is not None, want_ties)
-    if key in _REFS:
-        return _REFS[key]
-    prob = dropped(problem(name), drop)
-    g, S = prob['g'], prob['S']
-    ks, bs, geom_t, hp = oracle_inputs(g)
-    d_em = prob['dimg'].reshape((prob['B'], max(S, 1)) + prob['spatial'])
-    d_em = d_em if S else d_em[:, 0]
-    em = None if recipe is None else ob.Bf16Trainer(ks, bs, geom_t, hp, recipe)
-    if want_ties:
-        ties = relu_tie_count(g, return_points=True)[1] if em is None else em.relu_tie_points(t64(g['t_frames']))
-        out = ties & (g['g'] != 0)
-    else:
-        out = ob.flat((ot.grad_linear(ks, bs, geom_t, hp, t64(g['t_frames']), d_em) if em is None else em.grad_linear(t64(g['t_frames']), d_em)))
-        assert np.abs(out).max() > 0
-    out.setflags(write=False)
-    _REFS[key] = out
-    return out
-
-
-def device_gradients(dev, prob, mode, k, calls):
-    """`calls` x eng.render_bwd on a FRESH predictor -- all frames at once (k None), or with max_workspace_bytes = the size query
-    for k frames -> (gradients, info)."""
+def device_gradients(dev, name, prob, mode, recipe, compact, k, calls):
+    """`calls` x eng.render_bwd on a FRESH predictor, on the fused path `recipe` (gpu_support.assert_path) -- all frames at once (k
+    None), or with max_workspace_bytes = the size query for k frames -> (gradients, groups per frame)."""
     g, B = prob['g'], prob['B']
     pred, eng, geom, flat, tM0 = device_setup(g, mode, dev)
     P, gpf = geom.P_eff, geom.P_eff // 32
-    flags = eng.tape_info(gpf)['flags']
+    assert_path(name, eng, geom, mode, recipe, False, compact=compact)
     if k is None:
         assert eng.fits_tape(B, P)
     else:
@@ -113,7 +81,7 @@ def device_gradients(dev, prob, mode, k, calls):
     dimg = prob['dimg'].float().to(dev).contiguous()
     assert tuple(dimg.shape) == (B, geom.Sx, geom.R)
     grads = [eng.render_bwd(geom, tM0, dimg).cpu().numpy().astype(np.float64) for _ in range(calls)]
-    return grads, dict(flags=flags, gpf=gpf, compact=geom.compact is not None)
+    return grads, gpf
 
 
 def evaluate(dev, name, k, drop=None):
@@ -124,29 +92,22 @@ def evaluate(dev, name, k, drop=None):
     depth, width, mode, S, rays, B, _ = CASES[name]
     prob = dropped(problem(name), drop)
     fkey = (name, None, drop is not None)
-    if fkey not in _RUNS:
-        _RUNS[fkey] = device_gradients(dev, prob, mode, None, 1)
-    (full,), _ = _RUNS[fkey]
-    (chunked, again), info = device_gradients(dev, prob, mode, k, 2)
-    flags = info['flags']
-    # the path that ran, as test_gpu_bf16_faithful.check_case asserts it
     recipe = expected_recipe(depth, kernel_width(width), False) if mode == 'bf16' else None
-    assert not flags['general'] and info['compact'] == (rays == 'compacted') and info['gpf'] >= 96
+    run = lambda frames, calls: device_gradients(dev, name, prob, mode, recipe, rays == 'compacted', frames, calls)
+    if fkey not in _RUNS:
+        _RUNS[fkey] = run(None, 1)
+    (full,), _ = _RUNS[fkey]
+    (chunked, again), gpf = run(k, 2)
+    assert gpf >= 96
     if rays == 'compacted':
-        assert info['gpf'] >= 100 and RAY_SETS[rays][2] % 32 != 0
+        assert gpf >= 100 and RAY_SETS[rays][2] % 32 != 0
     else:
-        assert info['gpf'] == int(rays.split()[1])
-    if mode == 'bf16':
-        assert ob.recipe_for(flags) == recipe, (name, flags, recipe)
-        assert flags['fused128'] == (recipe == 'fused128') and flags['ga0_chain'] == (recipe == 'ga0_chain')
-        assert flags['drop_ga'] == (recipe in ('fold', 'ga0_chain'))
-    else:
-        assert not (flags['fused128'] or flags['ga0_chain'] or flags['drop_ga']), (name, flags)
-    gref = reference(name, recipe, drop)
+        assert gpf == int(rays.split()[1])
+    gref = linear_reference('frame chunks', name, problem(name), recipe, drop)['grad']
     cuts = tensor_cuts(prob['g'], depth)
     spans = [(c0, c1) for c0, c1 in zip(cuts[:-1], cuts[1:])]
-    assert cuts[-1] == gref.size == chunked.size
-    tens = [l2err(chunked[c0:c1], gref[c0:c1]) for c0, c1 in spans]
+    assert cuts[-1] == gref.size == chunked.size and np.abs(gref).max() > 0
+    tens = tensor_l2(chunked, gref, cuts, False)
     # against the all-at-once call, per tensor: the largest |difference| / (1e-6 max|full tensor| + 1e-5 |full|); must be <= 1
     vs_full = []
     for c0, c1 in spans:
@@ -156,11 +117,10 @@ def evaluate(dev, name, k, drop=None):
     passes = [k] * (B // k) + ([B % k] if B % k else [])
     r = dict(grad=l2err(chunked, gref), tensor=max(tens), gmax=float(np.abs(chunked - gref).max() / np.abs(gref).max()), vs_full=max(vs_full),
              repro=bool(np.array_equal(chunked, again)), chunked=chunked, recipe=recipe or 'f32', passes=passes)
-    label = lambda i: ('K%d' if i % 2 == 0 else 'b%d') % (i // 2)
     print('\n[frame chunks] %-24s %-9s %3d groups/frame  passes %-9s vs %s: L2 %.2e  max %.2e  worst tensor %.2e (%s)   vs all-at-once %.2f of '
           'the bound (%s)  repeat bitwise %s%s'
-          % (name, r['recipe'], info['gpf'], '+'.join(map(str, passes)), 'f64 oracle' if recipe is None else 'emulator', r['grad'], r['gmax'],
-             r['tensor'], label(int(np.argmax(tens))), r['vs_full'], label(int(np.argmax(vs_full))), r['repro'],
+          % (name, r['recipe'], gpf, '+'.join(map(str, passes)), 'f64 oracle' if recipe is None else 'emulator', r['grad'], r['gmax'],
+             r['tensor'], tensor_label(int(np.argmax(tens))), r['vs_full'], tensor_label(int(np.argmax(vs_full))), r['repro'],
              '' if drop is None else '  [tied samples taken out]'))
     _RUNS[key] = r
     return r
@@ -175,14 +135,9 @@ def test_chunked_backward_against_reference_and_all_at_once(dev, name, k):
         bg, bt = bf16_bounds('%s k%d' % (name, k))
         ok = lambda r: r['grad'] < bg and r['tensor'] < bt
     r = evaluate(dev, name, k)
-    ref_ok = ok(r)
-    if not ref_ok:
-        # a ReLU tie only explains it if the same problem without exactly the tied ray samples meets the same bounds
-        ties = reference(name, None if mode == 'f32' else r['recipe'], want_ties=True)
-        if ties.any():
-            r2 = evaluate(dev, name, k, drop=ties)
-            ref_ok = ok(r2) and r2['repro'] and r2['vs_full'] <= 1.0
-            print('relu ties (%s, %d per pass): %d tied ray samples taken out: %s' % (name, k, int(ties.sum()), 'adjudicated' if ref_ok else 'NOT a tie'))
+    ref_ok, _ = held_or_adjudicated('%s, %d per pass' % (name, k), r, ok,
+                                    lambda: linear_reference('frame chunks', name, problem(name), None if mode == 'f32' else r['recipe'], want_ties=True),
+                                    lambda ties: evaluate(dev, name, k, drop=ties), lambda r2: r2['repro'] and r2['vs_full'] <= 1.0)
     # both comparisons are evaluated, and a failure reports both: which of them sees a fault is part of the finding
     figures = 'vs reference: L2 %.2e max %.2e worst tensor %.2e (%s); vs all-at-once: %.3g of the bound; repeat bitwise: %s' % (
         r['grad'], r['gmax'], r['tensor'], 'inside the bounds' if ref_ok else 'OUTSIDE the bounds', r['vs_full'], r['repro'])
@@ -195,13 +150,11 @@ def test_tape8_chunked_backward_calibrating_and_second_call(dev):
     the bf16 mode's bounds against the float64 oracle, and within test_tape8_mode_gradient's 4e-2 of the bf16 mode's chunked
     gradient.  (Not compared with the all-at-once call, whose calibration sees other frames; the two calls differ in their scales.)"""
     prob = problem(T8_BASE)
-    grads, info = device_gradients(dev, prob, 'bf16_t8', 1, 2)
     # the 8-bit tape folds W_out as the bf16 mode does but keeps dW_0 in dw_kernel (fused_bwd.hip ga0_chain_ok: its chain has no
-    # registers to spare for the consumer), so this is the one case that runs dw_kernel's 8-bit flushes with accumulate = 1
-    flags = info['flags']
-    assert flags['drop_ga'] and not (flags['ga0_chain'] or flags['fused128'] or flags['general']), flags
-    assert info['gpf'] == 144
-    gref = reference(T8_BASE, None)
+    # registers to spare for the consumer), so this is the one case that runs dw_kernel's 8-bit flushes with accumulate = 1: path 't8'
+    grads, gpf = device_gradients(dev, T8_BASE, prob, 'bf16_t8', 't8', False, 1, 2)
+    assert gpf == 144
+    gref = linear_reference('frame chunks', T8_BASE, prob, None)['grad']
     g16 = evaluate(dev, T8_BASE, 1)['chunked']
     for i, g8 in enumerate(grads):
         assert np.isfinite(g8).all()

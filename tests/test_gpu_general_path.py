@@ -7,18 +7,17 @@ every case has the property it is listed for.
 Per case and mode the C ABI is called directly, on buffers of exactly the sizes the ABI names that are pre-filled with 0xFF (NaN as f32
 and as bf16, every relu bit set: a read of a tape or slab slot nobody wrote shows up as NaN) between guard bands: bhn_pack_weights,
 bhn_predict_fwd, bhn_render_fwd, bhn_render_fwd_train + bhn_render_bwd_tape, bhn_render_bwd all at once -- twice, on fresh buffers.
-Asserted: the `general` flag of engine.tape_info; packed and workspace bytes equal to the restated layout; both images and both
+Asserted: the general path (gpu_support.assert_path); packed and workspace bytes equal to the restated layout; both images and both
 gradients bitwise equal to each other, and everything bitwise equal on the second run (that includes `long 257` and the
-direct layouts); emission, images and gradients against a reference outside the code under test --
+direct layouts); emission, images and gradients against a reference outside the code under test (mlp_reference.linear_reference) --
   f32   the float64 oracle: images and emission 1e-5 max(1, 2^(deg-5)) of the maximum, gradient max-norm and relative L2
         2e-5 max(1, 2^(deg-5)) (gpu_support.check_general_path_problem's figures; octave i multiplies the f32 rounding of the warped
         coordinate by 2^i before the sine, and the emission feels that as the images do);
   bf16  oracle_bf16's emulator of the `general` recipe: mlp_bounds.caps_of('random', deg) -- images 5e-4 max(1, 2^(deg-5)), whole
         gradient 3e-3, worst tensor 6e-3 relative L2, the emission (relative L2) at the image cap.
 No bound comes from the kernels; the figures every case prints are recorded in DESIGN.md 2 and bound nothing.  ReLU ties are adjudicated
-as in test_gpu_buffer_contract: the same problem without exactly the tied ray samples of the reference's own forward must meet the same
-bounds (the CPU test holds the tied share of every case under a quarter).  A workspace 256 bytes under slabs + min(tiles, 2) tiles of
-tape is refused with BHN_EWORKSPACE, outputs untouched.
+by mlp_bounds.held_or_adjudicated (the CPU test holds the tied share of every case under a quarter).  A workspace 256 bytes under
+slabs + min(tiles, 2) tiles of tape is refused with BHN_EWORKSPACE, outputs untouched.
 
 Chunk sweep (general_path_cases.CHUNK_SWEEP: NG 4, NG 2, compacted): bhn_render_bwd in a workspace of slabs + k tiles of tape, k = 2, 3, 5
 and the tile count minus one (chunks that cut frames, a short last chunk, twelve and more accumulating passes) -- per tensor within rtol 1e-5 /
@@ -32,11 +31,10 @@ import torch
 import buffer_contract_cases as bc
 import general_path_cases as gp
 from general_path_cases import CASES, MODES, bounds, case_layout, problem, reference
-from gpu_support import dev, lib, device_setup, ptr, stream_ptr  # noqa: F401
+from gpu_support import assert_path, dev, lib, device_setup, ptr, stream_ptr  # noqa: F401
 from guarded import Guarded
-from mlp_bounds import expected_recipe, l2err, maxerr as mx
+from mlp_bounds import expected_recipe, first_difference, held_or_adjudicated, l2err, maxerr as mx, tensor_l2, tensor_label
 from mlp_problems import tensor_cuts
-from oracle import oracle_bf16 as ob
 
 pytestmark = pytest.mark.gpu
 
@@ -108,12 +106,6 @@ def evaluate(dev, lib, name, mode):
     return _RUNS[(name, mode)]
 
 
-def first_difference(a, b):
-    """None when the float32 arrays are bitwise equal, else (flat index, a, b) of the first element that differs."""
-    d = np.nonzero(a.reshape(-1).view(np.uint32) != b.reshape(-1).view(np.uint32))[0]
-    return None if d.size == 0 else (int(d[0]), float(a.reshape(-1)[d[0]]), float(b.reshape(-1)[d[0]]))
-
-
 def compare(out, ref, su):
     """The figures of one run against a reference."""
     prob, geom = su['prob'], su['geom']
@@ -126,7 +118,7 @@ def compare(out, ref, su):
     cuts = tensor_cuts(prob['g'])
     gref = ref['grad']
     routes = {k: out[k].astype(np.float64) for k in ('grad_tape', 'grad_rec')}
-    tens = [max(l2err(g[c0:c1], gref[c0:c1]) for g in routes.values()) for c0, c1 in zip(cuts[:-1], cuts[1:])]
+    tens = np.max([tensor_l2(g, gref, cuts, False) for g in routes.values()], axis=0)
     img = max(mx(out[k].reshape(ref['images'].shape).astype(np.float64), ref['images']) for k in ('images', 'images_train'))
     return dict(emission_max=mx(e, e_ref), emission_l2=l2err(e, e_ref), image=img, grad=max(l2err(g, gref) for g in routes.values()),
                 gmax=max(mx(g, gref) for g in routes.values()), tensor=max(tens), worst=int(np.argmax(tens)),
@@ -140,10 +132,9 @@ def within(f, mode, bnd):
 
 
 def line(f, mode):
-    label = lambda i: ('K%d' if i % 2 == 0 else 'b%d') % (i // 2)
     return ('vs %s: image %.2e  emission max %.2e L2 %.2e  gradient L2 %.2e max %.2e  worst tensor %.2e (%s)  per-layer dK L2 %s'
             % ('f64 oracle' if mode == 'f32' else 'emulator', f['image'], f['emission_max'], f['emission_l2'], f['grad'], f['gmax'], f['tensor'],
-               label(f['worst']), ' '.join('%.1e' % v for v in f['layers'])))
+               tensor_label(f['worst']), ' '.join('%.1e' % v for v in f['layers'])))
 
 
 @pytest.mark.parametrize('name,mode', PAIRS, ids=IDS)
@@ -154,10 +145,9 @@ def test_path_sizes_and_refusal(dev, lib, name, mode):
     r = evaluate(dev, lib, name, mode)
     su, L = r['su'], case_layout(name)
     eng, geom = su['eng'], su['geom']
-    flags = eng.tape_info(L['groups'])['flags']
-    assert flags['general'] and eng.general and ob.recipe_for(flags) == expected_recipe(depth, L['Wp'], True) == 'general', (name, flags)
     compact = rays.startswith('compacted')
-    assert (geom.compact is not None) == compact and geom.P_eff == 32 * L['groups'] and geom.G == gp.RAY_SETS[rays][2]
+    assert_path(name, eng, geom, mode, expected_recipe(depth, L['Wp'], True), True, compact=compact)
+    assert eng.general and geom.P_eff == 32 * L['groups'] and geom.G == gp.RAY_SETS[rays][2]
     assert (geom.compact['ray_span'] if compact else None) == L['ray_span'], (name, L['ray_span'])
     assert (geom.compact['n'] if compact else geom.P) == gp.points_per_frame(name)
     M, m, gs, fs, st = call_args(dev, su)
@@ -194,16 +184,15 @@ def test_results_against_reference(dev, lib, name, mode):
     su, bnd = r['su'], bounds(name, mode)
     f = compare(r['first'], reference(name, mode), su)
     print('\n[general path] %-32s %-4s %s' % (name, mode, line(f, mode)))
-    good = within(f, mode, bnd)
-    if not good:
-        # a ReLU tie only explains it if the same problem without exactly the tied ray samples meets the same bounds
-        ties = reference(name, mode, want_ties=True)
-        if ties.any():
-            su2 = setup(dev, name, mode, drop=ties)
-            out2, bad2, _ = run_sequence(dev, lib, su2)
-            f2 = compare(out2, reference(name, mode, drop=ties), su2)
-            good = within(f2, mode, bnd) and not bad2
-            print('relu ties (%s %s): %d tied ray samples taken out: %s   %s' % (name, mode, int(ties.sum()), 'adjudicated' if good else 'NOT a tie', line(f2, mode)))
+
+    def rerun(ties):
+        su2 = setup(dev, name, mode, drop=ties)
+        out2, bad2, _ = run_sequence(dev, lib, su2)
+        f2 = compare(out2, reference(name, mode, drop=ties), su2)
+        print('    without the tied ray samples: %s' % line(f2, mode))
+        return dict(f2, bad=bad2)
+    good, _ = held_or_adjudicated('%s %s' % (name, mode), f, lambda f: within(f, mode, bnd), lambda: reference(name, mode, want_ties=True),
+                                   rerun, lambda f2: not f2['bad'])
     assert good, (name, mode, line(f, mode), bnd)
 
 

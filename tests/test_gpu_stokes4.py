@@ -1,14 +1,14 @@
 """GPU tests of every render path at four Stokes planes (I, Q, U, V: what kgeo.py and bhn_grf_transport produce whenever V_frac != 0).
-The cases, why each is there (the branch, and the LDS bytes of its kernels at Sx = 4), the references, the comparator and the bounds
-live in tests/stokes4_cases.py; tests/test_stokes4_cases_cpu.py proves on the CPU that these bounds see a lost, aliased or
+The cases, why each is there (the branch, and the LDS bytes of its kernels at Sx = 4), the comparator and the bounds live in
+tests/stokes4_cases.py, the references in tests/mlp_reference.py (Reference: the emission on the in-domain points); tests/test_stokes4_cases_cpu.py proves on the CPU that these bounds see a lost, aliased or
 mis-strided fourth plane.  Each case, per arithmetic mode:
 
 * runs twice on fresh predictors and is bitwise equal to itself;
 * f32: per-plane image figure (error of plane s over the largest entry of the float64 oracle's |J| image of that plane) below
-  IMG_TOL['f32'], gradient below GTOL / L2TOL['f32'] against the float64 oracle, ReLU ties adjudicated as in
-  gpu_support.check_random_problem and test_gpu_frame_chunks (the tied ray samples get Doppler weight 0 on both sides, same bounds);
+  IMG_TOL['f32'], gradient below GTOL / L2TOL['f32'] against the float64 oracle, ReLU ties adjudicated by
+  mlp_bounds.held_or_adjudicated;
 * bf16: per-plane image figure against the float64 oracle below IMG_TOL['bf16']; whole-image error, gradient and worst tensor against
-  the emulator of the recipe that ran (asserted through engine.tape_info, as test_gpu_bf16_faithful.check_case does) inside 4x the
+  the emulator of the recipe that ran (gpu_support.assert_path) inside 4x the
   figures observed on the MI355X (mlp_bounds.OBSERVED under the case's name), never above the caps of its class; 8x256 (class 'deep',
   no cap): the float64 gradient bounds and 4x the figures of the same network at three planes;
 * planes 0 to 2 of the S = 4 render equal the S = 3 render of the same problem without the V row: bit for bit on a dense layout (a
@@ -23,33 +23,22 @@ import pytest
 import torch
 
 import stokes4_cases as sc
-from gpu_support import chi2_step, dev, device_setup, ray_args  # noqa: F401
-from oracle import oracle_bf16 as ob
+from gpu_support import assert_path, chi2_step, dev, device_setup, ray_args  # noqa: F401
+from mlp_bounds import held_or_adjudicated
 
 pytestmark = pytest.mark.gpu
 
 PARAMS = [(name, mode) for name, c in sc.CASES.items() for mode in c['modes']]
 
 
-def assert_path(name, mode, eng, geom):
-    """The path that runs is the one the case is listed (and, in bf16, emulated) for."""
+def assert_case_path(name, mode, eng, geom):
+    """gpu_support.assert_path of a case, and the ray sums it is listed for."""
     c = sc.CASES[name]
-    info = eng.tape_info((geom.P_eff + 31) // 32)
-    flags = info['flags']
-    assert geom.S == 4 and geom.Sx == 4 and (geom.compact is not None) == c['compact'], (name, 'layout')
+    assert_path(name, eng, geom, mode, sc.case_recipe(name, mode), c['general'], compact=c['compact'], tile_groups=c.get('tile_groups'))
+    assert geom.S == 4 and geom.Sx == 4, (name, 'layout')
     # direct adds or the combine through LDS (fused_fwd.hip fused_fill_args: ray_direct)
     direct = geom.compact['ray_span'] in (1, 2) if c['compact'] else geom.G <= 33 or (geom.G <= 64 and geom.G % 32 == 0)
     assert direct == c['direct'], (name, 'ray_direct', direct)
-    assert flags['general'] == c['general'], (name, flags)
-    if mode == 'bf16':
-        recipe = sc.case_recipe(name, mode)
-        assert ob.recipe_for(flags) == recipe, (name, flags, recipe)
-        assert flags['fused128'] == (recipe == 'fused128') and flags['ga0_chain'] == (recipe == 'ga0_chain')
-        assert flags['general'] or flags['drop_ga'] == (recipe in ('fold', 'ga0_chain'))
-    elif not c['general']:
-        assert not (flags['fused128'] or flags['ga0_chain'] or flags['drop_ga']), (name, flags)
-    if 'tile_groups' in c:
-        assert info['fwd_groups_per_tile'] == c['tile_groups'], (name, info)
 
 
 def device_outputs(dev, name, mode, prob):
@@ -57,7 +46,7 @@ def device_outputs(dev, name, mode, prob):
     chi^2 step; 'linear': render_train + render_bwd_tape, render + render_bwd), and the plain render (B, 4, R) as a tensor."""
     c, g = sc.CASES[name], prob['g']
     pred, eng, geom, flat, tM0 = device_setup(g, mode, dev)
-    assert_path(name, mode, eng, geom)
+    assert_case_path(name, mode, eng, geom)
     B = len(g['t_frames'])
     eng.pack(flat)
     rendered = eng.render(geom, tM0).clone()
@@ -87,7 +76,8 @@ def three_plane_render(dev, mode, prob):
 
 def evaluate(dev, name, mode, drop=None):
     """A case in a mode (drop: without these ray samples) -> (the worst figures over its routes, whether two runs agreed bit for bit,
-    whether planes 0 to 2 equal the three-plane render: 'bitwise', 'rounding' (compacted layouts, <= 2e-6 of the largest entry) or no)."""
+    whether planes 0 to 2 equal the three-plane render: 'bitwise', 'rounding' (compacted layouts, <= 2e-6 of the largest entry) or no,
+    its references, the line it printed)."""
     r = sc.case_references(name, mode, drop)
     prob = r['prob']
     outs, rendered = device_outputs(dev, name, mode, prob)
@@ -101,25 +91,19 @@ def evaluate(dev, name, mode, drop=None):
     else:
         close = float((rendered[:, :3] - three).abs().max()) <= 2e-6 * float(three.abs().max())
         planes012 = 'rounding' if close and sc.CASES[name]['compact'] else 'NO'
-    return worst, repro, planes012, r
+    line = '\n[stokes4] %-24s %-5s %-9s %s  repeat bitwise %s  planes 0-2 vs S = 3: %s%s' % (
+        name, mode, sc.case_recipe(name, mode) or 'f32', sc.describe(worst), repro, planes012, '' if drop is None else '  [tied samples taken out]')
+    print(line)
+    return worst, repro, planes012, r, line
 
 
 @pytest.mark.parametrize('name,mode', PARAMS)
 def test_four_stokes_planes(dev, name, mode):
     b = sc.bounds(name, mode)
-    fig, repro, planes012, r = evaluate(dev, name, mode)
-    line = '\n[stokes4] %-24s %-5s %-9s %s  repeat bitwise %s  planes 0-2 vs S = 3: %s' % (
-        name, mode, sc.case_recipe(name, mode) or 'f32', sc.describe(fig), repro, planes012)
-    print(line)
-    ok = sc.within(fig, b)
-    if not ok:
-        # a ReLU tie only explains it if the same problem without exactly the tied ray samples meets the same bounds
-        ties = (r['r64'] if mode == 'f32' else r['rem']).relu_ties(r['prob']['g'])
-        if ties.any():
-            fig2, repro2, planes2, _ = evaluate(dev, name, mode, drop=ties)
-            ok = sc.within(fig2, b) and repro2 and planes2 != 'NO'
-            print('relu ties (%s, %s): %d tied ray samples taken out: %s -- %s' % (name, mode, int(ties.sum()), sc.describe(fig2),
-                                                                                  'adjudicated' if ok else 'NOT a tie'))
+    fig, repro, planes012, r, line = evaluate(dev, name, mode)
+    ok, _ = held_or_adjudicated('%s, %s' % (name, mode), (fig, repro, planes012), lambda run: sc.within(run[0], b),
+                                lambda: (r['r64'] if mode == 'f32' else r['rem']).relu_ties(r['prob']['g']),
+                                lambda ties: evaluate(dev, name, mode, drop=ties)[:3], lambda run: run[1] and run[2] != 'NO')
     assert ok, (line, {k: v for k, v in sc.ratios(fig, b).items() if v >= 1.0}, b)
     assert repro, (name, mode, 'two runs differ')
     assert planes012 != 'NO', (name, mode, 'planes 0 to 2 differ from the three-plane render')

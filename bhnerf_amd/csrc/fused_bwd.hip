@@ -4,12 +4,17 @@
 //   chain_kernel  per 32-point wave tile: (re)compute the forward, dE = sum_s dimg*w, dout = dE*e*(1-e),
 //                 delta chain gA_{l-1} = (W_l gA_l) * relu'(a_{l-1}) with the same register-chained MFMA
 //                 structure and software-pipelined ring steps as the forward (fused_common.h).  Every 32x32
-//                 tile of h_l (layer inputs) and gA_l (gradients w.r.t. pre-activations) is transposed by two
-//                 MFMAs against identity fragments (TapeEmit) and streamed to an HBM "tape" already in MFMA
-//                 fragment order [lane = feature][8 points].
+//                 tile of h_l (layer inputs) and gA_l (gradients w.r.t. pre-activations) is streamed to an HBM
+//                 "tape" (TapeEmit).  f32: transposed by two MFMAs against identity fragments, so that it lies on
+//                 the tape in MFMA fragment order [lane = feature][8 points].  bf16: stored as the producer holds
+//                 it (point on the lane, no transposing MFMAs); the dW kernel transposes while it reads the LDS
+//                 image (ds_read_b64_tr_b16, tr_frag).
 //   dw_kernel     weight-gradient GEMMs dW_l^T[out x in] = sum_points gA_l^T . in_l with K = points:
 //                 a workgroup owns ONE layer's whole dW^T in registers (<= 288 KB) and streams its
-//                 share of the tape through LDS; bias gradients come from a constant ones B-fragment.
+//                 share of the tape through LDS.  Bias gradients are sums over the A fragments (Pol::sum8),
+//                 not a product with a ones fragment.  bf16 (dw_body2): the job of layer depth-1 rebuilds
+//                 gA_{depth-1} from h_depth and dout and carries the output layer's row (v_dot2) -- at width 256
+//                 on a wave grid of its own (8 x 1: every fragment rebuilt once per workgroup).
 //                 One slab flush per workgroup at the end: no float atomics, deterministic.
 //   reduce_kernel sums the slabs of each layer's workgroups into the flat dparams (flax tree order).
 #include <climits>
@@ -22,6 +27,8 @@
 static constexpr int JOB1_W = 13;        // the layer-1 job (measured optimum)
 static constexpr int JOBL_W = 7;         // extra weight of the layer depth-1 job when it rebuilds gA_{depth-1} and carries the output row
                                          // (round 5, re-swept without the layer-0 job, profiles/r5_dw_job_weights.txt: 6-7 beat 8 by 1.2 % of the dW kernel)
+static constexpr int JOBL_ROWS_W = 3;    // ... on the NWAVES x 1 wave grid (BwdGeom::LAST_ROWS, width 256), where every gA_{depth-1} fragment is rebuilt once per workgroup
+                                         // (profiles/dw_last_job_once_ab.txt: 3 beats 2 and 4 by 1.4 - 1.9 % of the dW kernel; JOB1_W re-swept against it: 13 stays)
 static constexpr int GA0C_DIST = 4;      // weight chunks in flight in the delta chain that accumulates dW_0 (its LDS also holds 64 KB of staging images)
 static constexpr int TAPED_DIST = 7;     // weight chunks in flight in the training-forward / delta-chain kernels (bf16; 4 measured 2 % slower)
 static constexpr int T8_NBUF = 4;        // ring depth of the 8-bit tape's dW jobs (8 = the bf16 jobs' bytes in flight: measured no faster, the jobs are VALU-bound)
@@ -39,6 +46,9 @@ struct BwdGeom {
     static constexpr int WC = Pol::NWAVES / WR >= 1 ? Pol::NWAVES / WR : 1;
     static constexpr int WRR = (Pol::NWAVES < WR) ? Pol::NWAVES : WR;   // f32 policy has 4 waves
     static constexpr int WCC = Pol::NWAVES / WRR;
+    // ... but the bf16 layer depth-1 job that rebuilds gA_{depth-1} (dw_body2 LAST) runs on NWAVES x 1 where a wave per A tile exists
+    // (width 256; the 8-bit tape's A tiles come in pairs: 4 x 2)
+    static constexpr bool LAST_ROWS = Pol::ELEM_BYTES == 2 && !Pol::TAPE8 && MT == Pol::NWAVES;
     static constexpr int MPW = (MT + WRR - 1) / WRR;
     static constexpr int NPW_ALL = (NTMAX + WCC - 1) / WCC;          // B tiles owned per wave
     // B tiles accumulated per sweep of the tape: 5 with 8 waves (2 per SIMD, 256 registers each); all of them with the
@@ -1239,9 +1249,14 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     static_assert((NB & (NB - 1)) == 0 && NB >= 4 && NB * GB <= 160 * 1024, "ring size");
     constexpr int nH = has_h ? MT : 0, nB = nH + ((JT == JT_FIRST || JT == JT_SKIP) ? 1 : 0);   // slab tile nB: the bias column
     constexpr int nBr = has_h ? MT : 1;                                // B tiles of the regular tile grid
-    constexpr int WRR = BG::WRR, WCC = BG::WCC;
+    // wave grid of this job: 4 x 2 (BwdGeom), but 8 x 1 for the bf16 layer depth-1 job at width 256 -- a_load / a_prep depend on
+    // the wave ROW alone, so on 4 x 2 the two waves of a row rebuild the same gA_{depth-1} fragments from the same h_depth and
+    // dout; with one A tile and all MT B tiles per wave every fragment of the workgroup is prepared once.  Same MFMAs per wave
+    // and group (16), same accumulator tiles (8 + the encoded-input tile), and every accumulator still adds the same products in
+    // the same order; LDS fragment reads per group rise from 96 to 144 KiB.
+    constexpr bool ROWS8 = LAST && BG::LAST_ROWS;
+    constexpr int WRR = ROWS8 ? Pol::NWAVES : BG::WRR, WCC = Pol::NWAVES / WRR;
     constexpr int MPW = (MT + WRR - 1) / WRR, NPW = (nBr + WCC - 1) / WCC;
-    static_assert(NPW <= 5, "one sweep");
     // the B tiles are 8-bit tape tiles too: with both operands 8-bit the weight-gradient tiles are accumulated by
     // v_mfma_f32_32x32x16_fp8_fp8 straight from the sorted bytes (gA / scale times h; the scale is applied at the flush); bf16 is
     // made only where bf16 code needs it (bias sums, the encoded-input tile, the output layer's row)
@@ -1249,6 +1264,10 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     static_assert(!T8 || MPW == 2, "8-bit tape: the A tiles come in pairs (width 256)");
     static_assert(!F8 || NPW % 2 == 0, "8-bit tape: the B tiles come in pairs (width 256)");
     constexpr int ME = (MPW + WCC - 1) / WCC;                          // A tiles a wave pairs with the enc tile / the output row
+    static_assert(MPW * NPW + ME <= 10, "one sweep: at most 10 accumulator tiles per wave (two waves per SIMD)");
+    // B fragments of the MFMA phase (the one in use + those being fetched): a fragment feeds MPW MFMAs, so with one A tile per wave
+    // the fetch runs one step further ahead (3, 4, 5 and 6 fragments measured within the run-to-run spread of each other)
+    constexpr int BQD = ROWS8 ? 4 : 3, NBC = BQD - 1;
     constexpr int NTOT = 2 * NPW;                                      // MFMA steps per group (k-step major)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: wave-uniform branches
     const int trl = tr_lane_off();
@@ -1267,7 +1286,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     const char *srcD = A.tape + A.t.dout_off;
     const char *srcH = has_h ? A.tape + A.t.h_off[job] : nullptr;
     const char *srcE = A.tape + (make_h ? A.t.encp_off : A.t.enc_off);
-    const int wr = wv % WRR, wc = wv / WRR;
+    const int wr = WCC == 1 ? wv : wv % WRR, wc = WCC == 1 ? 0 : wv / WRR;
     const int nbase = wc * NPW;
     const bool works = wr * MPW < MT && nbase < nBr;                   // this wave owns accumulator tiles
     // HIDDEN1: W_0 and b_0 behind the ring (see dw_body)
@@ -1477,9 +1496,9 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     constexpr int T_PREP = NTOT > 3 ? 3 : NTOT - 1;
     // MFMA phase of the group in `gp` (A fragments `cur`, first B fragments `bc`), with the loads / preparation of the
     // next group's A state `nx` and first B fragments `bn` from `gnext` folded into its steps
-    auto mma_phase = [&](const char *gp, const AState &cur, const frag (&bc)[2], const char *gnext, AState &nx, frag (&bn)[2],
+    auto mma_phase = [&](const char *gp, const AState &cur, const frag (&bc)[NBC], const char *gnext, AState &nx, frag (&bn)[NBC],
                          bool live_next) {
-        frag bq[3], benc;
+        frag bq[BQD], benc;
         if constexpr (F8) {
             // e4m3 operands: pair u of the wave's B tiles arrives sorted in ONE register quad (bc[0] / bn[0]: fragments of tile 2k
             // in dwords 0-1, of tile 2k+1 in dwords 2-3)
@@ -1525,18 +1544,21 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
         if constexpr (make_h) {
             bq[0] = load_b(gp, 0);
             if (NTOT > 1) bq[1] = load_b(gp, 1);
-        } else {
+        } else if constexpr (NBC == 2) {
             bq[0] = bc[0]; bq[1] = bc[1];
+        } else {
+#pragma unroll
+            for (int j = 0; j < NBC; ++j) bq[j] = bc[j];
         }
 #pragma unroll
         for (int t = 0; t < NTOT; ++t) {
-            if (t + 2 < NTOT) bq[(t + 2) % 3] = load_b(gp, t + 2);
+            if (t + BQD - 1 < NTOT) bq[(t + BQD - 1) % BQD] = load_b(gp, t + BQD - 1);
             if (enc_extra && (t % NPW) == (NPW >= 2 ? NPW - 2 : 0)) benc = tr_frag(gp + OFF_E, t / NPW, trl);     // used at ni == NPW-1
             if (t == 0) a_load(gnext, nx);
             __builtin_amdgcn_sched_barrier(0);
             const int s2 = t / NPW, ni = t % NPW;
 #pragma unroll
-            for (int mi = 0; mi < MPW; ++mi) acc[mi][ni] = Pol::mma(cur.af[s2][mi], bq[t % 3], acc[mi][ni]);
+            for (int mi = 0; mi < MPW; ++mi) acc[mi][ni] = Pol::mma(cur.af[s2][mi], bq[t % BQD], acc[mi][ni]);
             if constexpr (enc_extra) {
                 if (ni == NPW - 1) {
 #pragma unroll
@@ -1548,8 +1570,14 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
             for (int k = 0; k < NPREP; ++k)
                 if (t == (T_PREP + k < NTOT ? T_PREP + k : NTOT - 1)) a_prep(nx, k, live_next);
             if constexpr (!make_h) {
-                if (t == (NTOT >= 2 ? NTOT - 2 : 0)) bn[0] = load_b(gnext, 0);
-                if (t == NTOT - 1) bn[1] = load_b(gnext, NTOT > 1 ? 1 : 0);
+                if constexpr (NBC == 2) {
+                    if (t == (NTOT >= 2 ? NTOT - 2 : 0)) bn[0] = load_b(gnext, 0);
+                    if (t == NTOT - 1) bn[1] = load_b(gnext, NTOT > 1 ? 1 : 0);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < NBC; ++j)
+                        if (t == NTOT - NBC + j) bn[j] = load_b(gnext, j);
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1565,7 +1593,7 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
     __syncthreads();                                            // W_0 / b_0 visible (HIDDEN1)
     if (q0 < q1) {
         AState sa, sb;
-        frag ba[2], bb[2];
+        frag ba[NBC], bb[NBC];
 #pragma unroll
         for (int j = 0; j < NB - 1; ++j) issue(q0 + j, smem + j * GB);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 2) * PPW) : "memory");
@@ -1579,9 +1607,13 @@ DEVI void dw_body2(const BwdArgs &A, int job, char *smem) {
             if constexpr (F8) {
                 const Pair8 pr = tr8_sort(load_braw(smem, 0));
                 ba[0] = __builtin_bit_cast(frag, (u32x4){pr.a[0], pr.a[1], pr.b[0], pr.b[1]});
-            } else if constexpr (!make_h) { ba[0] = load_b(smem, 0); ba[1] = load_b(smem, NTOT > 1 ? 1 : 0); }
+            } else if constexpr (!make_h && NBC == 2) { ba[0] = load_b(smem, 0); ba[1] = load_b(smem, NTOT > 1 ? 1 : 0); }
+            else if constexpr (!make_h) {
+#pragma unroll
+                for (int j = 0; j < NBC; ++j) ba[j] = load_b(smem, j);
+            }
         }
-        auto body = [&](AState &cur, AState &nx, frag (&bc)[2], frag (&bn)[2], long long q, int it) {
+        auto body = [&](AState &cur, AState &nx, frag (&bc)[NBC], frag (&bn)[NBC], long long q, int it) {
             // group q+1 has landed for this wave (q+2 .. q+NB-2 may still be in flight), then it is published to the workgroup
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 3) * PPW) : "memory");
             if constexpr (make_h) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's h-tile writes
@@ -2008,6 +2040,10 @@ struct BwdPlan {
 // rebuild of gA, output row).  Balancing the jobs so that each takes the same time when it runs ALONE
 // (round 2) measured slower (5.0 vs 4.75 ms): run together they share the HBM stream, and the light
 // layer-0 job finishing early leaves its bandwidth to the others.
+// Wave grids: every job runs its workgroup's eight waves as 4 x 2 (A-tile rows x B-tile columns), on which the two waves of a
+// row prepare the same A fragments -- nothing for a job that only reads them, but the layer depth-1 job rebuilt every
+// gA_{depth-1} fragment twice (JOBL_W = 7 of its 24.5 at 4x256).  At width 256 that job runs 8 x 1 (BwdGeom::LAST_ROWS), rebuilds
+// each fragment once and weighs JOBL_ROWS_W = 3 (20.5 of 58.5); the narrower widths have fewer A tiles than waves and keep 4 x 2.
 template <int W, class Pol>
 static void dw_job_split(const MlpShape &s, const TapeLayout &t, int grid_dw, int *wg_begin) {
     using BG = BwdGeom<W, Pol>;
@@ -2021,7 +2057,7 @@ static void dw_job_split(const MlpShape &s, const TapeLayout &t, int grid_dw, in
                                                               // same MFMA work + the recompute: not byte-bound any more
         work[l] = (double)(mtA + nB) + 0.5;
         // + the rebuild of gA and the output row (8-bit tape: the byte masks of that job are its long pole; 12 measured 2-3 % faster than 8)
-        if (l == depth - 1 && t.drop_ga) work[l] += (Pol::TAPE8 ? 12 : JOBL_W) * BG::MT / 8.0;
+        if (l == depth - 1 && t.drop_ga) work[l] += (Pol::TAPE8 ? 12 : BG::LAST_ROWS ? JOBL_ROWS_W : JOBL_W) * BG::MT / 8.0;
         if constexpr (Pol::ELEM_BYTES == 4) {
             // f32: the jobs are MFMA-bound (a 32x32x2 MFMA is 64 cycles; one 32x32 tile product over a 32-point
             // group = 16 of them = 0.55 us at the observed 1.87 GHz) unless they stream more than ~34 GB/s per

@@ -1,5 +1,6 @@
 """ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
-(include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h) and libbhnerf_eql.so (include/bhnerf_eql.h).
+(include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h), libbhnerf_eql.so (include/bhnerf_eql.h) and libbhnerf_flow.so
+(include/bhnerf_flow.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -144,6 +145,26 @@ LIBRARIES = {
     'libbhnerf_grf': (GRF_LIB_PATH, GRF_SIGNATURES, 'bhn_grf_last_error', None),
     'libbhnerf_eql': (EQL_LIB_PATH, EQL_SIGNATURES, 'bhn_eql_last_error', None),
 }
+
+# libbhnerf_flow.so (include/bhnerf_flow.h): (g, J) for a general 4-velocity or the boosted ZAMO, the sixth library.  It is described
+# by a tuple of its own, FLOW_LIBRARY, in the layout of the entries of LIBRARIES
+FLOW_LIB_PATH = os.path.join(CSRC, 'libbhnerf_flow.so')
+
+
+class bhn_flow_geos(C.Structure):
+    _fields_ = bhn_grf_geos._fields_ + [('omega', C.c_void_p)]
+
+
+_FG = C.POINTER(bhn_flow_geos)
+FLOW_SIGNATURES = {
+    'bhn_flow_last_error': (C.c_char_p, []),
+    'bhn_flow_zamo_velocity': (C.c_int, [_FG, _D, _D, _P, _P]),
+    'bhn_flow_doppler': (C.c_int, [_FG, _P, _D, _I32, _P, _P]),
+    'bhn_flow_fluid_field': (C.c_int, [_FG, _P, _D, _D, _D, _P, _P]),
+    'bhn_flow_transport': (C.c_int, [_FG, _P, _P, _P, _P, _D, _D, _D, _P, _P]),
+    'bhn_flow_transport_zamo': (C.c_int, [_FG, _D, _D, _P, _P, _P, _D, _D, _P, _P]),
+}
+FLOW_LIBRARY = (FLOW_LIB_PATH, FLOW_SIGNATURES, 'bhn_flow_last_error', None)
 _loaded = {}                 # path -> handle
 
 
@@ -154,7 +175,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in LIBRARIES), CSRC))
+        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow']), CSRC))
     return LIB_PATH
 
 
@@ -182,14 +203,15 @@ def load(path, signatures, abi_version=None):
     return _loaded[path]
 
 
-def _lib(library):
-    path, signatures, _, abi_version = LIBRARIES[library]
+def _lib(library, entry=None):
+    """`library` of LIBRARIES, or the library that the tuple `entry` (path, signatures, last-error symbol, ABI version) describes."""
+    path, signatures, _, abi_version = entry or LIBRARIES[library]
     return load(path, signatures, abi_version)
 
 
-def _check(library, rc):
+def _check(library, rc, entry=None):
     if rc != 0:
-        raise HipError('%s: %s (code %d)' % (library, getattr(_lib(library), LIBRARIES[library][2])().decode(), rc))
+        raise HipError('%s: %s (code %d)' % (library, getattr(_lib(library, entry), (entry or LIBRARIES[library])[2])().decode(), rc))
 
 
 def lib():
@@ -217,6 +239,11 @@ def eql_lib():
     return _lib('libbhnerf_eql')
 
 
+def flow_lib():
+    """The loaded general-flow (g, J) library."""
+    return _lib('libbhnerf_flow', FLOW_LIBRARY)
+
+
 def check(rc):
     _check('libbhnerf_hip', rc)
 
@@ -235,6 +262,10 @@ def grf_check(rc):
 
 def eql_check(rc):
     _check('libbhnerf_eql', rc)
+
+
+def flow_check(rc):
+    _check('libbhnerf_flow', rc, FLOW_LIBRARY)
 
 
 def stream_ptr(device=None):

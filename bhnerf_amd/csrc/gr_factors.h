@@ -227,12 +227,13 @@ GRF_HD double grf_field_magnitude(const double b[3]) {
 // _transport: local EVPA from k x b in the emitter frame, emissivity scalings, rotation to the observer's screen through the
 // Penrose-Walker constant.  gfac is the Doppler factor handed in, b the fluid-frame field (already divided by the caller's scalar).
 // J[0..2] = I, Q, U; J[3] = V when with_v.
-GRF_HD void grf_point_transport(const GrfGeos &g, long long p, double Omega, double gfac, const double b[3], double Q_frac, double V_frac,
-                                double spectral_index, int with_v, double J[4]) {
+//
+// Two parts: the frame (grf_frame, the Keplerian one; csrc/flow_factors.h builds others) and the transport in a frame f, which reads
+// f.e, f.sin_th and f.cos_th only.
+GRF_HD void grf_transport_in_frame(const GrfGeos &g, long long p, const GrfFrame &f, double gfac, const double b[3], double Q_frac,
+                                   double V_frac, double spectral_index, int with_v, double J[4]) {
     const long long ray = p / g.ngeo;
     const int k = (int)(p - ray * g.ngeo);
-    GrfFrame f;
-    grf_frame(g, p, Omega, f);
     double kmu[4], k_loc[3], f_loc[3], fg[4], kup[4];
     grf_wave_vector(g, ray, k, kmu);
     grf_to_local_frame(f.e, kmu, k_loc);
@@ -276,6 +277,13 @@ GRF_HD void grf_point_transport(const GrfGeos &g, long long p, double Omega, dou
         const double cot_b = sqrt(1.0 - sin_b * sin_b) / sin_b;
         J[3] = V_frac * grf_pow(gfac, -spectral_index - 0.5) * grf_pow(b_mag, spectral_index + 1.5) * grf_pow(sin_b, spectral_index + 1.5) * cot_b;
     }
+}
+
+GRF_HD void grf_point_transport(const GrfGeos &g, long long p, double Omega, double gfac, const double b[3], double Q_frac, double V_frac,
+                                double spectral_index, int with_v, double J[4]) {
+    GrfFrame f;
+    grf_frame(g, p, Omega, f);
+    grf_transport_in_frame(g, p, f, gfac, b, Q_frac, V_frac, spectral_index, with_v, J);
 }
 
 // ---- the domain mean: a fixed-order two-stage reduction

@@ -17,7 +17,10 @@ relativistic Doppler factor far from the hole, conservation of the Penrose-Walke
 
 ``emission_factors`` is the chain ``alma.image_plane_model`` runs after the geodesics are traced (4-velocity -> Doppler factor ->
 fluid-frame field -> its mean over the recovery domain -> parallel transport) as one function, on the host (``backend='numpy'``:
-the functions above, composed) or on the GPU (``backend='hip'``: ``libbhnerf_grf.so``, include/bhnerf_grf.h).
+the functions above, composed) or on the GPU (``backend='hip'``: ``libbhnerf_grf.so``, include/bhnerf_grf.h).  With
+``flow=`` it takes a general 4-velocity instead -- a ``umu`` array, or the boosted ZAMO of ``zamo_frame_velocity`` -- and
+``frame='zamo'`` transports in the ZAMO tetrad (``parallel_transport_zamo``); on the GPU that is ``libbhnerf_flow.so``,
+include/bhnerf_flow.h, DESIGN.md 4.13.
 """
 import numpy as np
 import torch
@@ -309,30 +312,55 @@ def _emission_factors_numpy(geos, Omega, b_consts, domain, Q_frac, V_frac, spect
     return g, J
 
 
-def _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device):
-    """The calls of include/bhnerf_grf.h on one record: fields uploaded once, g (and J) downloaded."""
-    import ctypes as C
+def _hip_device(geos, b_consts, Q_frac, lib, device):
+    """What both device paths check before anything touches the device, in this order; the torch device."""
     r = _f(geos, 'r')
     if r.ndim < 1 or r.shape[-1] < 2:            # np.gradient's own error, before anything touches the device
         raise ValueError('Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.')
     if b_consts is not None and (Q_frac > 1.0 or Q_frac < 0.0):
         raise AttributeError('Q_frac should be in [0,1]')
-    lib = _hip.grf_lib()
+    lib()
     if not torch.cuda.is_available():
         raise _hip.HipError("backend='hip' needs a HIP device (there is no CPU fallback; backend='numpy' computes the factors on the host)")
-    dev = torch.device('cuda' if device is None else device)
-    shape, ngeo = r.shape, r.shape[-1]
-    n = r.size // ngeo
-    with torch.cuda.device(dev):
-        def up(v, shp):
-            v = np.asarray(v, dtype=np.float64)
-            return torch.as_tensor(np.ascontiguousarray(v if v.shape == shp else np.broadcast_to(v, shp).copy()), device=dev)
+    return torch.device('cuda' if device is None else device)
 
-        fields = {k: up(_f(geos, k), shape) for k in _GRF_POINT_FIELDS}
-        fields.update({k: up(_f(geos, k), shape[:-1]) for k in _GRF_RAY_FIELDS})
-        Om = up(Omega, shape)
-        rec = _hip.bhn_grf_geos(n, ngeo, *[fields[k].data_ptr() for k in _GRF_POINT_FIELDS + _GRF_RAY_FIELDS],
-                                float(_f(geos, 'spin')), float(_f(geos, 'M')), float(_f(geos, 'E')), float(_f(geos, 'inc')))
+
+def _upload(v, shp, dev):
+    v = np.asarray(v, dtype=np.float64)
+    return torch.as_tensor(np.ascontiguousarray(v if v.shape == shp else np.broadcast_to(v, shp).copy()), device=dev)
+
+
+def _upload_record(geos, dev):
+    """The fields of include/bhnerf_grf.h's record on the device and the struct that names them: (fields, bhn_grf_geos)."""
+    shape = _f(geos, 'r').shape
+    fields = {k: _upload(_f(geos, k), shape, dev) for k in _GRF_POINT_FIELDS}
+    fields.update({k: _upload(_f(geos, k), shape[:-1], dev) for k in _GRF_RAY_FIELDS})
+    rec = _hip.bhn_grf_geos(_f(geos, 'r').size // shape[-1], shape[-1], *[fields[k].data_ptr() for k in _GRF_POINT_FIELDS + _GRF_RAY_FIELDS],
+                            float(_f(geos, 'spin')), float(_f(geos, 'M')), float(_f(geos, 'E')), float(_f(geos, 'inc')))
+    return fields, rec
+
+
+def _domain_mean_hip(rec, b, domain, dev, stream):
+    """bhn_grf_domain_mean on the device buffers of `rec`: the mean of |b| over the domain, one float64 on the device."""
+    import ctypes as C
+    lib = _hip.grf_lib()
+    z_width, rmin, rmax = (float(v) for v in domain)
+    nbytes = int(lib.bhn_grf_ws_bytes(rec.n, rec.ngeo))
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    mean = torch.empty((1,), dtype=torch.float64, device=dev)
+    _hip.grf_check(lib.bhn_grf_domain_mean(C.byref(rec), _hip.ptr(b), z_width, rmin, rmax, _hip.ptr(mean), _hip.ptr(ws), nbytes, stream))
+    return mean
+
+
+def _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device):
+    """The calls of include/bhnerf_grf.h on one record: fields uploaded once, g (and J) downloaded."""
+    import ctypes as C
+    dev = _hip_device(geos, b_consts, Q_frac, _hip.grf_lib, device)
+    lib = _hip.grf_lib()
+    shape = _f(geos, 'r').shape
+    with torch.cuda.device(dev):
+        fields, rec = _upload_record(geos, dev)                         # `fields` owns the buffers `rec` points into
+        Om = _upload(Omega, shape, dev)
         stream = _hip.stream_ptr(dev)
         g = torch.empty(shape, dtype=torch.float64, device=dev)
         no_fill = _no_fill(fillna)
@@ -342,13 +370,7 @@ def _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectra
         b = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
         _hip.grf_check(lib.bhn_grf_fluid_field(C.byref(rec), _hip.ptr(Om), float(b_consts['arad']), float(b_consts['avert']),
                                                float(b_consts['ator']), _hip.ptr(b), stream))
-        mean = None
-        if domain is not None:
-            z_width, rmin, rmax = (float(v) for v in domain)
-            nbytes = int(lib.bhn_grf_ws_bytes(n, ngeo))
-            ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
-            mean = torch.empty((1,), dtype=torch.float64, device=dev)
-            _hip.grf_check(lib.bhn_grf_domain_mean(C.byref(rec), _hip.ptr(b), z_width, rmin, rmax, _hip.ptr(mean), _hip.ptr(ws), nbytes, stream))
+        mean = None if domain is None else _domain_mean_hip(rec, b, domain, dev, stream)
         S = 4 if V_frac != 0 else 3
         J = torch.empty((S,) + shape, dtype=torch.float64, device=dev)
         _hip.grf_check(lib.bhn_grf_transport(C.byref(rec), _hip.ptr(Om), _hip.ptr(g), _hip.ptr(b), _hip.ptr(mean), float(Q_frac), float(V_frac),
@@ -356,20 +378,146 @@ def _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectra
         return g.cpu().numpy(), J.cpu().numpy()
 
 
-def emission_factors(geos, Omega, b_consts=None, domain=None, Q_frac=0.2, V_frac=0.01, spectral_index=1, fillna=0.0, backend='numpy',
-                     device=None):
-    """Doppler factor ``g`` and polarised transport factors ``J`` of matter on circular orbits with angular velocity ``Omega``:
-    ``azimuthal_velocity_vector -> doppler_factor -> magnetic_field_fluid_frame -> (domain mean) -> parallel_transport``, what
-    ``alma.image_plane_model`` computes after the geodesics are traced.  Returns ``(g, J)``; ``J`` is None when ``b_consts``
-    (``arad, avert, ator``) is None.  ``domain=(z_width, rmin, rmax)`` divides the field by its mean magnitude over the points with
-    ``|z| < z_width, rmin < r < rmax``; None leaves it as it is.
+# ---- a general 4-velocity: a umu array per point, or the boosted ZAMO
+
+def _parse_flow(geos, flow, frame):
+    """``flow`` and ``frame`` of emission_factors -> (zamo, umu): ``zamo = (beta, chi)``, scalars as given, for the device functions,
+    or ``umu``, a host array of the record's shape + (4,)."""
+    shape = _f(geos, 'r').shape
+    if frame not in ('fluid', 'zamo'):
+        raise ValueError("frame must be 'fluid' or 'zamo', not %r" % (frame,))
+    if isinstance(flow, tuple) and len(flow) == 3 and isinstance(flow[0], str):
+        if flow[0] != 'zamo':
+            raise ValueError("flow must be ('zamo', beta, chi) or a umu array, not a %r flow" % (flow[0],))
+        beta, chi = flow[1], flow[2]
+        if np.ndim(beta) == 0 and np.ndim(chi) == 0:
+            return (beta, chi), None
+        if np.broadcast(np.empty(shape), beta, chi).shape != shape:
+            raise ValueError('per-point beta and chi must have the shape of the record, %s' % (shape,))
+        zamo, umu = None, zamo_frame_velocity(geos, beta, chi)
+    else:
+        zamo, umu = None, np.asarray(flow, dtype=np.float64)
+        if umu.shape != shape + (4,):
+            raise ValueError('flow must be (\'zamo\', beta, chi) or a umu array of shape %s, not %s' % (shape + (4,), umu.shape))
+    if frame == 'zamo':
+        raise ValueError("frame='zamo' needs a scalar ZAMO flow, flow=('zamo', beta, chi)")
+    return zamo, umu
+
+
+def _field_kind(b_consts):
+    """'fluid' (arad, avert, ator: the field follows the flow), 'spherical' (b_r, b_th, b_ph) or 'array' ((..., 3), taken as it is)."""
+    if isinstance(b_consts, dict):
+        if set(b_consts) == {'arad', 'avert', 'ator'}:
+            return 'fluid'
+        if set(b_consts) == {'b_r', 'b_th', 'b_ph'}:
+            return 'spherical'
+        raise ValueError('b_consts must have the keys arad, avert, ator or b_r, b_th, b_ph, not %s' % sorted(b_consts))
+    return 'array'
+
+
+def _given_field(geos, b_consts, kind):
+    shape = _f(geos, 'r').shape + (3,)
+    b = magnetic_field_spherical(geos, **b_consts) if kind == 'spherical' else np.asarray(b_consts, dtype=np.float64)
+    return b if b.shape == shape else np.broadcast_to(b, shape)
+
+
+def _flow_factors_numpy(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac, spectral_index, fillna):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if zamo is not None:
+            umu = zamo_frame_velocity(geos, *zamo)
+        g = doppler_factor(geos, umu, fillna)
+        if b_consts is None:
+            return g, None
+        kind = _field_kind(b_consts)
+        b = magnetic_field_fluid_frame(geos, umu, **b_consts) if kind == 'fluid' else _given_field(geos, b_consts, kind)
+        if domain is not None:
+            z_width, rmin, rmax = domain
+            r = _f(geos, 'r')
+            sel = (np.abs(r * np.cos(_f(geos, 'theta'))) < z_width) & (r > rmin) & (r < rmax)
+            b = b / np.sqrt((b[sel] ** 2).sum(axis=-1)).mean()
+        if frame == 'zamo':
+            return g, parallel_transport_zamo(geos, zamo[0], zamo[1], g, b, Q_frac=Q_frac, spectral_index=spectral_index)
+        return g, parallel_transport(geos, umu, g, b, Q_frac=Q_frac, V_frac=V_frac, spectral_index=spectral_index)
+
+
+def _flow_factors_hip(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device):
+    """The calls of include/bhnerf_flow.h on one record: fields uploaded once, g (and J) downloaded.  The domain mean is
+    bhn_grf_domain_mean on the same device buffers."""
+    import ctypes as C
+    kind = None if b_consts is None else _field_kind(b_consts)
+    dev = _hip_device(geos, b_consts, Q_frac, _hip.flow_lib, device)
+    lib = _hip.flow_lib()
+    shape = _f(geos, 'r').shape
+    with torch.cuda.device(dev):
+        fields, grf_rec = _upload_record(geos, dev)
+        fields['omega'] = _upload(_f(geos, 'omega'), shape, dev)
+        rec = _hip.bhn_flow_geos(*[getattr(grf_rec, k) for k, _ in _hip.bhn_grf_geos._fields_], fields['omega'].data_ptr())
+        stream = _hip.stream_ptr(dev)
+        if zamo is not None:
+            beta, chi = float(zamo[0]), float(zamo[1])
+            u = torch.empty(shape + (4,), dtype=torch.float64, device=dev)
+            _hip.flow_check(lib.bhn_flow_zamo_velocity(C.byref(rec), beta, chi, _hip.ptr(u), stream))
+        else:
+            u = _upload(umu, shape + (4,), dev)
+        g = torch.empty(shape, dtype=torch.float64, device=dev)
+        no_fill = _no_fill(fillna)
+        _hip.flow_check(lib.bhn_flow_doppler(C.byref(rec), _hip.ptr(u), 0.0 if no_fill else float(fillna), 0 if no_fill else 1, _hip.ptr(g), stream))
+        if b_consts is None:
+            return g.cpu().numpy(), None
+        if kind == 'fluid':
+            b = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+            _hip.flow_check(lib.bhn_flow_fluid_field(C.byref(rec), _hip.ptr(u), float(b_consts['arad']), float(b_consts['avert']),
+                                                     float(b_consts['ator']), _hip.ptr(b), stream))
+        else:
+            b = _upload(_given_field(geos, b_consts, kind), shape + (3,), dev)
+        mean = None if domain is None else _domain_mean_hip(grf_rec, b, domain, dev, stream)
+        if frame == 'zamo':
+            J = torch.empty((3,) + shape, dtype=torch.float64, device=dev)
+            _hip.flow_check(lib.bhn_flow_transport_zamo(C.byref(rec), beta, chi, _hip.ptr(g), _hip.ptr(b), _hip.ptr(mean), float(Q_frac),
+                                                        float(spectral_index), _hip.ptr(J), stream))
+        else:
+            J = torch.empty(((4 if V_frac != 0 else 3),) + shape, dtype=torch.float64, device=dev)
+            _hip.flow_check(lib.bhn_flow_transport(C.byref(rec), _hip.ptr(u), _hip.ptr(g), _hip.ptr(b), _hip.ptr(mean), float(Q_frac),
+                                                   float(V_frac), float(spectral_index), _hip.ptr(J), stream))
+        return g.cpu().numpy(), J.cpu().numpy()
+
+
+def emission_factors(geos, Omega=None, b_consts=None, domain=None, Q_frac=0.2, V_frac=0.01, spectral_index=1, fillna=0.0, backend='numpy',
+                     device=None, flow=None, frame='fluid'):
+    """Doppler factor ``g`` and polarised transport factors ``J`` of one hypothesis about the emitting matter.  Returns ``(g, J)``;
+    ``J`` is None when ``b_consts`` is None.  ``domain=(z_width, rmin, rmax)`` divides the field by its mean magnitude over the
+    points with ``|z| < z_width, rmin < r < rmax``; None leaves it as it is.
+
+    The 4-velocity is given by exactly one of ``Omega`` and ``flow`` (both, or neither, is a ``ValueError``):
+
+    * ``Omega``: matter on circular orbits with that angular velocity, ``azimuthal_velocity_vector -> doppler_factor ->
+      magnetic_field_fluid_frame -> (domain mean) -> parallel_transport``, what ``alma.image_plane_model`` computes after the
+      geodesics are traced; ``b_consts`` is ``dict(arad, avert, ator)``.
+    * ``flow=('zamo', beta, chi)``: the boosted ZAMO of ``zamo_frame_velocity`` (Gelles et al. 2021).  Scalars go to the device
+      function; per-point arrays of the record's shape are evaluated on the host and taken as a ``umu`` array.
+    * ``flow=`` an array of shape ``geos.r.shape + (4,)``: a general ``umu`` per point.
+
+    With a ``flow``, ``b_consts`` is ``dict(arad, avert, ator)`` (``magnetic_field_fluid_frame`` of the flow),
+    ``dict(b_r, b_th, b_ph)`` (``magnetic_field_spherical``) or an array ``(..., 3)`` taken as it is, and ``frame`` chooses the
+    tetrad of the transport: ``'fluid'`` is ``parallel_transport(geos, umu, ...)``; ``'zamo'`` is ``parallel_transport_zamo``,
+    which needs a scalar ZAMO flow (anything else is a ``ValueError``), ignores ``V_frac`` and returns three rows.
 
     ``backend='numpy'`` (the default) composes the functions above on the host.  ``'hip'`` uploads the fields of the record once and
-    makes the calls of ``include/bhnerf_grf.h`` (``libbhnerf_grf.so``, csrc/gr_factors.hip: the same expressions, one GPU lane per
-    sample point) on ``device`` (a torch device, default the current one); float64 NumPy arrays of the same shapes come back.
-    There is no CPU fallback: ``'hip'`` without a device raises ``HipError``."""
+    makes the calls of ``include/bhnerf_grf.h`` (``Omega``; ``libbhnerf_grf.so``, csrc/gr_factors.hip) or ``include/bhnerf_flow.h``
+    (``flow``; ``libbhnerf_flow.so``, csrc/flow_factors.hip) -- the same expressions, one GPU lane per sample point -- on ``device``
+    (a torch device, default the current one); float64 NumPy arrays of the same shapes come back.  There is no CPU fallback:
+    ``'hip'`` without a device raises ``HipError``."""
     from .geodesics import _check_backend
     _check_backend(backend)
+    if (Omega is None) == (flow is None):
+        raise ValueError('give exactly one of Omega and flow (%s were given)' % ('both' if flow is not None else 'neither'))
+    if flow is None:
+        if frame != 'fluid':
+            raise ValueError("frame=%r needs a scalar ZAMO flow, flow=('zamo', beta, chi)" % (frame,))
+        if backend == 'hip':
+            return _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device)
+        return _emission_factors_numpy(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna)
+    zamo, umu = _parse_flow(geos, flow, frame)
     if backend == 'hip':
-        return _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device)
-    return _emission_factors_numpy(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna)
+        return _flow_factors_hip(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device)
+    return _flow_factors_numpy(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac, spectral_index, fillna)

@@ -1,6 +1,6 @@
 """ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
-(include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h), libbhnerf_eql.so (include/bhnerf_eql.h) and libbhnerf_flow.so
-(include/bhnerf_flow.h).
+(include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h), libbhnerf_eql.so (include/bhnerf_eql.h), libbhnerf_flow.so
+(include/bhnerf_flow.h) and libbhnerf_rec.so (include/bhnerf_rec.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -165,6 +165,23 @@ FLOW_SIGNATURES = {
     'bhn_flow_transport_zamo': (C.c_int, [_FG, _D, _D, _P, _P, _P, _D, _D, _P, _P]),
 }
 FLOW_LIBRARY = (FLOW_LIB_PATH, FLOW_SIGNATURES, 'bhn_flow_last_error', None)
+
+# libbhnerf_rec.so (include/bhnerf_rec.h): the geodesic record from the tracer's samples and the Keplerian Omega, the seventh library,
+# described like the sixth by a tuple of its own
+REC_LIB_PATH = os.path.join(CSRC, 'libbhnerf_rec.so')
+REC_FIELDS = ('r', 'theta', 'phi', 't', 'mino', 'Delta', 'Sigma', 'Xi', 'omega', 'x', 'y', 'z', 'R', 'Theta', 'vr', 'vth', 'dtau', 'affine')
+
+
+class bhn_rec_fields(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in REC_FIELDS]
+
+
+REC_SIGNATURES = {
+    'bhn_rec_last_error': (C.c_char_p, []),
+    'bhn_rec_build': (C.c_int, [_P, _P, _P, _I64, _I32, _D, _D, C.POINTER(bhn_rec_fields), _P]),
+    'bhn_rec_kepler': (C.c_int, [_P, _I64, _D, _D, _D, _P, _P]),
+}
+REC_LIBRARY = (REC_LIB_PATH, REC_SIGNATURES, 'bhn_rec_last_error', None)
 _loaded = {}                 # path -> handle
 
 
@@ -175,7 +192,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow']), CSRC))
+        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec']), CSRC))
     return LIB_PATH
 
 
@@ -244,6 +261,11 @@ def flow_lib():
     return _lib('libbhnerf_flow', FLOW_LIBRARY)
 
 
+def rec_lib():
+    """The loaded geodesic-record library."""
+    return _lib('libbhnerf_rec', REC_LIBRARY)
+
+
 def check(rc):
     _check('libbhnerf_hip', rc)
 
@@ -266,6 +288,10 @@ def eql_check(rc):
 
 def flow_check(rc):
     _check('libbhnerf_flow', rc, FLOW_LIBRARY)
+
+
+def rec_check(rc):
+    _check('libbhnerf_rec', rc, REC_LIBRARY)
 
 
 def stream_ptr(device=None):

@@ -38,6 +38,36 @@ def preprocess_data(data_path, window_size, I_hs_mean, P_sha, chi_sha, de_rot_an
     return target, t_frames
 
 
+def _check_resident(params):
+    tracer, factors = params.get('tracer', 'numpy'), params.get('factors', 'numpy')
+    if params.get('resident', False) and not (tracer == 'hip' and factors == 'hip'):
+        raise ValueError("params['resident'] needs params['tracer'] == params['factors'] == 'hip', not %r and %r" % (tracer, factors))
+
+
+def _resident_image_plane_model(inc, spin, params, rot_angle, randomize_subpixel_rays):
+    """image_plane_model without leaving the device: the record from ``bhn_rec_build``, Omega from ``bhn_rec_kepler``, J from the
+    (g, J) library on the record's buffers, ``nan_to_num`` and ``rotate_evpa`` on float64 tensors."""
+    import torch
+    from . import _hip
+    _check_resident(params)
+    fov = params['fov_M']
+    rmin = float(constants.isco_pro(spin)) if params['rmin'] == 'ISCO' else params['rmin']
+    rmax = fov / 2.0
+    geos = kgeo.image_plane_geos(spin, inc, num_alpha=params['num_alpha'], num_beta=params['num_beta'],
+                                 alpha_range=[-fov / 2.0, fov / 2.0], beta_range=[-fov / 2.0, fov / 2.0],
+                                 randomize_subpixel_rays=randomize_subpixel_rays, backend='hip', resident=True).fillna(0.0)
+    dev = geos.device
+    with torch.cuda.device(dev):
+        Omega = torch.empty_like(geos.r)
+        _hip.rec_check(_hip.rec_lib().bhn_rec_kepler(_hip.ptr(geos.r), geos.r.numel(), float(geos.spin), float(geos.M),
+                                                     float(params.get('Omega_frac', 1.0) * _ROTATION_SIGN[params['Omega_dir']]),
+                                                     _hip.ptr(Omega), _hip.stream_ptr(dev)))
+    _, J = kgeo.emission_factors(geos, Omega, params['b_consts'], (params['z_width'], rmin, rmax), Q_frac=params['Q_frac'], V_frac=0,
+                                 backend='hip')
+    J = emission.rotate_evpa(torch.nan_to_num(J, nan=0.0), rot_angle)
+    return geos, Omega, J
+
+
 def image_plane_model(inc, spin, params, rot_angle=0.0, randomize_subpixel_rays=False):
     """Geodesics, Keplerian angular velocity and polarised emission factors J (3, alpha, beta, geo) of one
     (inclination, spin) hypothesis (alma.py:27-64).
@@ -46,9 +76,12 @@ def image_plane_model(inc, spin, params, rot_angle=0.0, randomize_subpixel_rays=
     (``arad, avert, ator``), ``Omega_dir`` (``'cw'|'ccw'``) and optionally ``Omega_frac`` (sub-Keplerian factor) and ``tracer``
     (``'numpy'|'hip'``: where the geodesics are integrated, ``geodesics.image_plane_geos``'s ``backend``; default ``'numpy'``) and
     ``factors`` (``'numpy'|'hip'``: where the Doppler factor and J are computed, ``kgeo.emission_factors``'s ``backend``; default
-    ``'numpy'``)."""
+    ``'numpy'``).  ``resident`` (default False; needs ``tracer == factors == 'hip'``): the record, Omega and J are created on the GPU and
+    stay there -- a ``geodesics.DeviceGeodesics`` and float64 tensors come back."""
     factors = params.get('factors', 'numpy')
     geodesics._check_backend(factors)
+    if params.get('resident', False):
+        return _resident_image_plane_model(inc, spin, params, rot_angle, randomize_subpixel_rays)
     fov = params['fov_M']
     rmin = float(constants.isco_pro(spin)) if params['rmin'] == 'ISCO' else params['rmin']
     rmax = fov / 2.0
@@ -73,6 +106,7 @@ def get_raytracing_args(inc, spin, params, stokes=_STOKES, rot_angle=0.0, num_su
     """List of ``network.raytracing_args`` -- one per sub-pixel ray set (alma.py:66-82).  One set uses the regular pixel
     centres; several sets jitter the rays inside their pixels."""
     rows = [_STOKES.index(s) for s in stokes]
+    _check_resident(params)
     jitter = num_subpixel_rays != 1
     out = []
     for _ in range(num_subpixel_rays):

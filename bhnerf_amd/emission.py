@@ -163,9 +163,26 @@ def image_plane_dynamics(emission_0, geos, Omega, t_frames, t_injection, J=1.0, 
     return np.squeeze(out) if geom.S else out                                          # emission.py:299 squeeze quirk
 
 
+def _rotate_evpa_tensor(stokes, angle, axis):
+    n = stokes.shape[axis]
+    if n not in (2, 3, 4):
+        raise AttributeError('Shape of stokes vector along axis={} not supported'.format(axis))
+    q = 0 if n == 2 else 1
+    moved = torch.movedim(stokes, axis, 0)
+    c, s = float(np.cos(2.0 * angle)), float(np.sin(2.0 * angle))
+    out = moved.to(torch.float64, copy=True)
+    # separate products and one difference / sum each: no fused multiply-add, as NumPy evaluates it
+    out[q] = torch.sub(torch.mul(moved[q], c), torch.mul(moved[q + 1], s))
+    out[q + 1] = torch.add(torch.mul(moved[q], s), torch.mul(moved[q + 1], c))
+    return torch.movedim(out, 0, axis)
+
+
 def rotate_evpa(stokes, angle, axis=0):
     """Rotate the electric-vector position angle by ``angle`` [rad]: ``Q + iU -> exp(2i angle) (Q + iU)``
-    (emission.py:395-407).  The Stokes axis holds (Q, U), (I, Q, U) or (I, Q, U, V); I and V are unchanged."""
+    (emission.py:395-407).  The Stokes axis holds (Q, U), (I, Q, U) or (I, Q, U, V); I and V are unchanged.  A float64 torch tensor is
+    rotated where it is, by the same products and differences (NumPy's bits), and a tensor comes back."""
+    if isinstance(stokes, torch.Tensor):
+        return _rotate_evpa_tensor(stokes, angle, axis)
     stokes = np.asarray(stokes)
     n = stokes.shape[axis]
     if n not in (2, 3, 4):

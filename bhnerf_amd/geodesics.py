@@ -51,6 +51,32 @@ class Geodesics(dict):
         return out
 
 
+class DeviceGeodesics(Geodesics):
+    """The record of ``image_plane_geos(..., backend='hip', resident=True)``: the keys and shapes of ``Geodesics``, every array field a
+    float64 torch tensor on one device (created there by ``bhn_rec_build``, include/bhnerf_rec.h), the scalars floats.
+    ``kgeo.emission_factors`` and ``network.raytracing_args`` read it where it is; ``numpy()`` gives the ordinary record."""
+
+    @property
+    def device(self):
+        return self['r'].device
+
+    def fillna(self, value):
+        """Copy with the NaNs (and nothing else) of every floating tensor replaced, on the device."""
+        import torch
+        out = DeviceGeodesics()
+        for k, v in self.items():
+            if isinstance(v, torch.Tensor) and v.is_floating_point() and v.ndim:
+                out[k] = torch.where(torch.isnan(v), torch.as_tensor(value, dtype=v.dtype, device=v.device), v)
+            else:
+                out[k] = v
+        return out
+
+    def numpy(self):
+        """The ``Geodesics`` record of NumPy arrays with the same contents."""
+        import torch
+        return Geodesics((k, v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in self.items())
+
+
 def kerr_functions(r, theta, spin, M=1.0):
     """Δ, Σ, Ξ and the frame-dragging frequency ω of the Kerr metric (spin in units of M)."""
     a = spin * M
@@ -267,10 +293,11 @@ def _check_backend(backend):
         raise ValueError('backend must be one of %s, not %r' % (', '.join(repr(b) for b in BACKENDS), backend))
 
 
-def _trace_hip(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, ngeo, device=None):
+def _trace_device(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, ngeo, device=None):
     """``bhn_kerr_trace`` (include/bhnerf_kerr.h; csrc/kerr_trace.hip restates ``_integrate`` with one GPU lane per ray) on
-    one set of rays: ``(end (7, n), samples (7, n, ngeo) or None, lam, eta)`` as NumPy arrays, ``end`` rows final Mino time,
-    r, theta, phi, t, vr, vth.  Raises ``_integrate``'s RuntimeError when a ray is not finished after ``max_steps``."""
+    one set of rays: ``(end (7, n), samples (7, n, ngeo) or None, lam, eta, dev)``, ``end`` and ``samples`` float64 tensors on the torch
+    device ``dev``, ``lam`` and ``eta`` NumPy arrays.  Raises ``_integrate``'s RuntimeError when a ray is not finished after
+    ``max_steps``."""
     import torch
     from . import _hip
     alpha = np.ascontiguousarray(alpha, dtype=np.float64).ravel()
@@ -293,7 +320,14 @@ def _trace_hip(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, n
                                       int(max_steps), ngeo, _hip.ptr(samples), _hip.ptr(end), _hip.ptr(status), _hip.stream_ptr(dev)))
         if bool((status < 0).any()):
             raise RuntimeError('geodesic integration did not terminate in %d steps' % max_steps)
-        return end.cpu().numpy(), (samples.cpu().numpy() if ngeo > 0 else None), lam, eta
+        return end, samples, lam, eta, dev
+
+
+def _trace_hip(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, ngeo, device=None):
+    """``_trace_device`` with its results downloaded: ``(end (7, n), samples (7, n, ngeo) or None, lam, eta)`` as NumPy arrays, ``end``
+    rows final Mino time, r, theta, phi, t, vr, vth."""
+    end, samples, lam, eta, _ = _trace_device(alpha, beta, spin, inclination, distance, M, h, r_c, max_steps, ngeo, device)
+    return end.cpu().numpy(), (samples.cpu().numpy() if samples is not None else None), lam, eta
 
 
 def trace(alpha, beta, spin, inclination, distance=1000.0, M=1.0, h=0.02, r_c=5.0, max_steps=400000, backend='numpy', device=None):
@@ -417,9 +451,53 @@ def _sampled_record(alpha, beta, spin, inclination, ngeo, distance, E, M, h, chu
     return _build_record(out, lam_all, eta_all, alpha, beta, spin, inclination, distance, E, M)
 
 
+def _check_resident(resident, backend):
+    if resident and backend != 'hip':
+        raise ValueError("resident=True keeps the record on the GPU: it needs backend='hip', not %r" % (backend,))
+
+
+def _resident_record(alpha, beta, spin, inclination, ngeo, distance, E, M, h, chunk, max_steps, device, verbose):
+    """``_sampled_record`` without leaving the device: every chunk's samples go from ``bhn_kerr_trace`` straight into
+    ``bhn_rec_build`` (include/bhnerf_rec.h), which writes the chunk's slab of the 18 per-point fields.  The host sends the screen
+    coordinates and the rays' constants ``lam``, ``eta`` and reads the tracer's status.  Returns a ``DeviceGeodesics``."""
+    import ctypes as C
+    import torch
+    from . import _hip
+    n, ngeo = alpha.size, int(ngeo)
+    if ngeo < 1:
+        raise ValueError('ngeo must be at least 1')
+    rays = alpha.shape
+    af, bf = alpha.ravel(), beta.ravel()
+    bf = np.where(bf == 0.0, 1e-9, bf)                    # (as in _sampled_record)
+    lib = _hip.rec_lib()
+    fields = dev = None
+    lam_all, eta_all = np.empty(n), np.empty(n)
+    for c0 in range(0, n, chunk):
+        sl = slice(c0, min(c0 + chunk, n))
+        _, samples, lam, eta, dev = _trace_device(af[sl], bf[sl], spin, inclination, distance, M, h, 5.0, max_steps, ngeo, device)
+        lam_all[sl], eta_all[sl] = lam, eta
+        with torch.cuda.device(dev):
+            if fields is None:
+                fields = {k: torch.empty((n, ngeo), dtype=torch.float64, device=dev) for k in _hip.REC_FIELDS}
+            lam_c, eta_c = torch.as_tensor(lam, device=dev), torch.as_tensor(eta, device=dev)
+            out = _hip.bhn_rec_fields(*[fields[k][c0:].data_ptr() for k in _hip.REC_FIELDS])
+            _hip.rec_check(lib.bhn_rec_build(_hip.ptr(samples), _hip.ptr(lam_c), _hip.ptr(eta_c), sl.stop - c0, ngeo, float(spin), float(M),
+                                             C.byref(out), _hip.stream_ptr(dev)))
+        if verbose:
+            print('traced rays %d-%d of %d' % (c0, sl.stop, n))
+    g = DeviceGeodesics()
+    shape3 = rays + (ngeo,)
+    g.update((k, fields[k].reshape(shape3)) for k in _hip.REC_FIELDS)              # the key order of _build_record
+    up = lambda v: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64), device=dev)
+    g['alpha'], g['beta'] = up(alpha), up(beta)
+    g['lam'], g['eta'] = up(lam_all.reshape(rays)), up(eta_all.reshape(rays))
+    g['spin'], g['inc'], g['M'], g['E'], g['r_o'] = float(spin), float(inclination), float(M), float(E), float(distance)
+    return g
+
+
 def image_plane_geos(spin, inclination, alpha_range, beta_range, ngeo=100, num_alpha=64, num_beta=64, distance=1000.0,
                      E=1.0, M=1.0, randomize_subpixel_rays=False, verbose=False, h=0.02, chunk=65536, max_steps=400000,
-                     backend='numpy', device=None):
+                     backend='numpy', device=None, resident=False):
     """Kerr geodesics for the whole image plane (signature of ``bhnerf.kgeo.image_plane_geos``, kgeo.py:6-63).
 
     Returns a ``Geodesics`` record with arrays of shape ``(num_alpha, num_beta, ngeo)`` (per-ray constants
@@ -428,26 +506,35 @@ def image_plane_geos(spin, inclination, alpha_range, beta_range, ngeo=100, num_a
     arrival at the observer (negative along the ray), ``dtau`` the Mino step between consecutive samples.
 
     ``backend``: ``'numpy'`` (the default) integrates on the host, ``'hip'`` on the GPU (``bhn_kerr_trace``, one call per
-    ``chunk`` rays on ``device``); the record is built from the samples by the same code either way."""
+    ``chunk`` rays on ``device``); the record is built from the samples by the same code either way.
+
+    ``resident=True`` (``backend='hip'`` only) leaves the record where the tracer wrote its samples: ``bhn_rec_build`` builds the
+    fields on the device and a ``DeviceGeodesics`` of float64 tensors comes back."""
     _check_backend(backend)
+    _check_resident(resident, backend)
     alpha_1d = np.linspace(*alpha_range, num_alpha)
     beta_1d = np.linspace(*beta_range, num_beta)
     if randomize_subpixel_rays:
         alpha_1d = alpha_1d + (np.random.random(num_alpha) - 0.5) * (alpha_range[1] - alpha_range[0]) / max(num_alpha - 1, 1)
         beta_1d = beta_1d + (np.random.random(num_beta) - 0.5) * (beta_range[1] - beta_range[0]) / max(num_beta - 1, 1)
     alpha, beta = np.meshgrid(alpha_1d, beta_1d, indexing='ij')
+    if resident:
+        return _resident_record(alpha, beta, spin, inclination, ngeo, distance, E, M, h, chunk, max_steps, device, verbose)
     return _sampled_record(alpha, beta, spin, inclination, ngeo, distance, E, M, h, chunk, max_steps, backend, device, verbose)
 
 
 def ray_geos(spin, inclination, alpha, beta, ngeo=100, distance=1000.0, E=1.0, M=1.0, verbose=False, h=0.02, chunk=65536,
-             max_steps=400000, backend='numpy', device=None):
+             max_steps=400000, backend='numpy', device=None, resident=False):
     """The record of ``image_plane_geos`` for an arbitrary LIST of rays: ``alpha``, ``beta`` of n screen coordinates each; fields of
     shape ``(n, ngeo)``, per-ray constants ``(n,)``.  Stands in for ``kgeo.raytrace_ana(...).get_dataset()`` of the external
     package (dims ``(pix, geo)``), which the Gelles-2021 notebook of the reference calls; built by the same code as the grid form, so
-    ``ray_geos`` on a grid's flattened rays holds the grid's record bit for bit."""
+    ``ray_geos`` on a grid's flattened rays holds the grid's record bit for bit.  ``resident=True``: as in ``image_plane_geos``."""
     _check_backend(backend)
+    _check_resident(resident, backend)
     alpha = np.array(alpha, dtype=np.float64).ravel()
     beta = np.array(beta, dtype=np.float64).ravel()
     if alpha.shape != beta.shape or alpha.size < 1:
         raise ValueError('alpha and beta must be lists of the same length, at least one ray')
+    if resident:
+        return _resident_record(alpha, beta, spin, inclination, ngeo, distance, E, M, h, chunk, max_steps, device, verbose)
     return _sampled_record(alpha, beta, spin, inclination, ngeo, distance, E, M, h, chunk, max_steps, backend, device, verbose)

@@ -312,20 +312,36 @@ def _emission_factors_numpy(geos, Omega, b_consts, domain, Q_frac, V_frac, spect
     return g, J
 
 
+def _is_resident(geos):
+    from .geodesics import DeviceGeodesics
+    return isinstance(geos, DeviceGeodesics)
+
+
+def _shape(geos):
+    """The shape of the record's per-point fields, without a copy of a resident record's."""
+    return tuple(geos.r.shape) if _is_resident(geos) else _f(geos, 'r').shape
+
+
 def _hip_device(geos, b_consts, Q_frac, lib, device):
-    """What both device paths check before anything touches the device, in this order; the torch device."""
-    r = _f(geos, 'r')
-    if r.ndim < 1 or r.shape[-1] < 2:            # np.gradient's own error, before anything touches the device
+    """What both device paths check before anything touches the device, in this order; the torch device (a resident record's own)."""
+    shape = _shape(geos)
+    if len(shape) < 1 or shape[-1] < 2:            # np.gradient's own error, before anything touches the device
         raise ValueError('Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.')
     if b_consts is not None and (Q_frac > 1.0 or Q_frac < 0.0):
         raise AttributeError('Q_frac should be in [0,1]')
     lib()
     if not torch.cuda.is_available():
         raise _hip.HipError("backend='hip' needs a HIP device (there is no CPU fallback; backend='numpy' computes the factors on the host)")
+    if _is_resident(geos):
+        if device is not None and torch.device(device) != geos.device and torch.device(device) != torch.device(geos.device.type):
+            raise ValueError('the record lives on %s, not on %s' % (geos.device, device))
+        return geos.device
     return torch.device('cuda' if device is None else device)
 
 
 def _upload(v, shp, dev):
+    if isinstance(v, torch.Tensor):              # already a tensor (a resident record's Omega, umu, field): no host copy
+        return v.to(device=dev, dtype=torch.float64).expand(shp).contiguous()
     v = np.asarray(v, dtype=np.float64)
     return torch.as_tensor(np.ascontiguousarray(v if v.shape == shp else np.broadcast_to(v, shp).copy()), device=dev)
 
@@ -337,6 +353,16 @@ def _upload_record(geos, dev):
     fields.update({k: _upload(_f(geos, k), shape[:-1], dev) for k in _GRF_RAY_FIELDS})
     rec = _hip.bhn_grf_geos(_f(geos, 'r').size // shape[-1], shape[-1], *[fields[k].data_ptr() for k in _GRF_POINT_FIELDS + _GRF_RAY_FIELDS],
                             float(_f(geos, 'spin')), float(_f(geos, 'M')), float(_f(geos, 'E')), float(_f(geos, 'inc')))
+    return fields, rec
+
+
+def _resident_fields(geos, dev):
+    """_upload_record for a DeviceGeodesics: the struct names the record's own buffers, nothing is copied."""
+    shape = _shape(geos)
+    fields = {k: _upload(geos[k], shape, dev) for k in _GRF_POINT_FIELDS}
+    fields.update({k: _upload(geos[k], shape[:-1], dev) for k in _GRF_RAY_FIELDS})
+    rec = _hip.bhn_grf_geos(fields['r'].numel() // shape[-1], shape[-1], *[fields[k].data_ptr() for k in _GRF_POINT_FIELDS + _GRF_RAY_FIELDS],
+                            float(geos.spin), float(geos.M), float(geos.E), float(geos.inc))
     return fields, rec
 
 
@@ -353,20 +379,22 @@ def _domain_mean_hip(rec, b, domain, dev, stream):
 
 
 def _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device):
-    """The calls of include/bhnerf_grf.h on one record: fields uploaded once, g (and J) downloaded."""
+    """The calls of include/bhnerf_grf.h on one record: fields uploaded once, g (and J) downloaded.  A resident record
+    (geodesics.DeviceGeodesics) is read where it is and g (and J) stay on its device."""
     import ctypes as C
     dev = _hip_device(geos, b_consts, Q_frac, _hip.grf_lib, device)
     lib = _hip.grf_lib()
-    shape = _f(geos, 'r').shape
+    shape = _shape(geos)
+    resident = _is_resident(geos)
     with torch.cuda.device(dev):
-        fields, rec = _upload_record(geos, dev)                         # `fields` owns the buffers `rec` points into
+        fields, rec = _resident_fields(geos, dev) if resident else _upload_record(geos, dev)      # `fields` owns the buffers `rec` points into
         Om = _upload(Omega, shape, dev)
         stream = _hip.stream_ptr(dev)
         g = torch.empty(shape, dtype=torch.float64, device=dev)
         no_fill = _no_fill(fillna)
         _hip.grf_check(lib.bhn_grf_doppler(C.byref(rec), _hip.ptr(Om), 0.0 if no_fill else float(fillna), 0 if no_fill else 1, _hip.ptr(g), stream))
         if b_consts is None:
-            return g.cpu().numpy(), None
+            return (g, None) if resident else (g.cpu().numpy(), None)
         b = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
         _hip.grf_check(lib.bhn_grf_fluid_field(C.byref(rec), _hip.ptr(Om), float(b_consts['arad']), float(b_consts['avert']),
                                                float(b_consts['ator']), _hip.ptr(b), stream))
@@ -375,15 +403,15 @@ def _emission_factors_hip(geos, Omega, b_consts, domain, Q_frac, V_frac, spectra
         J = torch.empty((S,) + shape, dtype=torch.float64, device=dev)
         _hip.grf_check(lib.bhn_grf_transport(C.byref(rec), _hip.ptr(Om), _hip.ptr(g), _hip.ptr(b), _hip.ptr(mean), float(Q_frac), float(V_frac),
                                              float(spectral_index), _hip.ptr(J), stream))
-        return g.cpu().numpy(), J.cpu().numpy()
+        return (g, J) if resident else (g.cpu().numpy(), J.cpu().numpy())
 
 
 # ---- a general 4-velocity: a umu array per point, or the boosted ZAMO
 
 def _parse_flow(geos, flow, frame):
     """``flow`` and ``frame`` of emission_factors -> (zamo, umu): ``zamo = (beta, chi)``, scalars as given, for the device functions,
-    or ``umu``, a host array of the record's shape + (4,)."""
-    shape = _f(geos, 'r').shape
+    or ``umu``, an array of the record's shape + (4,) (a tensor given with a resident record stays a tensor)."""
+    shape = _shape(geos)
     if frame not in ('fluid', 'zamo'):
         raise ValueError("frame must be 'fluid' or 'zamo', not %r" % (frame,))
     if isinstance(flow, tuple) and len(flow) == 3 and isinstance(flow[0], str):
@@ -394,11 +422,13 @@ def _parse_flow(geos, flow, frame):
             return (beta, chi), None
         if np.broadcast(np.empty(shape), beta, chi).shape != shape:
             raise ValueError('per-point beta and chi must have the shape of the record, %s' % (shape,))
+        if _is_resident(geos):
+            raise ValueError('per-point beta and chi are evaluated by the NumPy functions: give them the record\'s .numpy()')
         zamo, umu = None, zamo_frame_velocity(geos, beta, chi)
     else:
-        zamo, umu = None, np.asarray(flow, dtype=np.float64)
-        if umu.shape != shape + (4,):
-            raise ValueError('flow must be (\'zamo\', beta, chi) or a umu array of shape %s, not %s' % (shape + (4,), umu.shape))
+        zamo, umu = None, (flow if isinstance(flow, torch.Tensor) else np.asarray(flow, dtype=np.float64))
+        if tuple(umu.shape) != shape + (4,):
+            raise ValueError('flow must be (\'zamo\', beta, chi) or a umu array of shape %s, not %s' % (shape + (4,), tuple(umu.shape)))
     if frame == 'zamo':
         raise ValueError("frame='zamo' needs a scalar ZAMO flow, flow=('zamo', beta, chi)")
     return zamo, umu
@@ -416,7 +446,12 @@ def _field_kind(b_consts):
 
 
 def _given_field(geos, b_consts, kind):
-    shape = _f(geos, 'r').shape + (3,)
+    shape = _shape(geos) + (3,)
+    if isinstance(b_consts, torch.Tensor):
+        return b_consts                          # (broadcast on the device by _upload)
+    if kind == 'spherical' and _is_resident(geos):               # only the record's shape enters
+        from types import SimpleNamespace
+        return magnetic_field_spherical(SimpleNamespace(r=np.empty(shape[:-1])), **b_consts)
     b = magnetic_field_spherical(geos, **b_consts) if kind == 'spherical' else np.asarray(b_consts, dtype=np.float64)
     return b if b.shape == shape else np.broadcast_to(b, shape)
 
@@ -442,15 +477,16 @@ def _flow_factors_numpy(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac
 
 def _flow_factors_hip(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac, spectral_index, fillna, device):
     """The calls of include/bhnerf_flow.h on one record: fields uploaded once, g (and J) downloaded.  The domain mean is
-    bhn_grf_domain_mean on the same device buffers."""
+    bhn_grf_domain_mean on the same device buffers.  A resident record is read where it is and g (and J) stay on its device."""
     import ctypes as C
     kind = None if b_consts is None else _field_kind(b_consts)
     dev = _hip_device(geos, b_consts, Q_frac, _hip.flow_lib, device)
     lib = _hip.flow_lib()
-    shape = _f(geos, 'r').shape
+    shape = _shape(geos)
+    resident = _is_resident(geos)
     with torch.cuda.device(dev):
-        fields, grf_rec = _upload_record(geos, dev)
-        fields['omega'] = _upload(_f(geos, 'omega'), shape, dev)
+        fields, grf_rec = _resident_fields(geos, dev) if resident else _upload_record(geos, dev)
+        fields['omega'] = _upload(geos.omega if resident else _f(geos, 'omega'), shape, dev)
         rec = _hip.bhn_flow_geos(*[getattr(grf_rec, k) for k, _ in _hip.bhn_grf_geos._fields_], fields['omega'].data_ptr())
         stream = _hip.stream_ptr(dev)
         if zamo is not None:
@@ -463,7 +499,7 @@ def _flow_factors_hip(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac, 
         no_fill = _no_fill(fillna)
         _hip.flow_check(lib.bhn_flow_doppler(C.byref(rec), _hip.ptr(u), 0.0 if no_fill else float(fillna), 0 if no_fill else 1, _hip.ptr(g), stream))
         if b_consts is None:
-            return g.cpu().numpy(), None
+            return (g, None) if resident else (g.cpu().numpy(), None)
         if kind == 'fluid':
             b = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
             _hip.flow_check(lib.bhn_flow_fluid_field(C.byref(rec), _hip.ptr(u), float(b_consts['arad']), float(b_consts['avert']),
@@ -479,7 +515,7 @@ def _flow_factors_hip(geos, zamo, umu, frame, b_consts, domain, Q_frac, V_frac, 
             J = torch.empty(((4 if V_frac != 0 else 3),) + shape, dtype=torch.float64, device=dev)
             _hip.flow_check(lib.bhn_flow_transport(C.byref(rec), _hip.ptr(u), _hip.ptr(g), _hip.ptr(b), _hip.ptr(mean), float(Q_frac),
                                                    float(V_frac), float(spectral_index), _hip.ptr(J), stream))
-        return g.cpu().numpy(), J.cpu().numpy()
+        return (g, J) if resident else (g.cpu().numpy(), J.cpu().numpy())
 
 
 def emission_factors(geos, Omega=None, b_consts=None, domain=None, Q_frac=0.2, V_frac=0.01, spectral_index=1, fillna=0.0, backend='numpy',
@@ -506,9 +542,15 @@ def emission_factors(geos, Omega=None, b_consts=None, domain=None, Q_frac=0.2, V
     makes the calls of ``include/bhnerf_grf.h`` (``Omega``; ``libbhnerf_grf.so``, csrc/gr_factors.hip) or ``include/bhnerf_flow.h``
     (``flow``; ``libbhnerf_flow.so``, csrc/flow_factors.hip) -- the same expressions, one GPU lane per sample point -- on ``device``
     (a torch device, default the current one); float64 NumPy arrays of the same shapes come back.  There is no CPU fallback:
-    ``'hip'`` without a device raises ``HipError``."""
+    ``'hip'`` without a device raises ``HipError``.
+
+    A resident record (``geodesics.DeviceGeodesics``, ``image_plane_geos(..., backend='hip', resident=True)``) needs
+    ``backend='hip'``: the libraries read the record's own device buffers, ``Omega``, a ``umu`` array and a given field may be tensors
+    or arrays, and ``(g, J)`` come back as float64 tensors on the record's device."""
     from .geodesics import _check_backend
     _check_backend(backend)
+    if _is_resident(geos) and backend != 'hip':
+        raise ValueError("a resident record (DeviceGeodesics) needs backend='hip'; the NumPy functions take its .numpy()")
     if (Omega is None) == (flow is None):
         raise ValueError('give exactly one of Omega and flow (%s were given)' % ('both' if flow is not None else 'neither'))
     if flow is None:

@@ -643,6 +643,30 @@ def image_plane_checkpoint(raytracing_args, checkpoint_dir, t, rmin=0.0, rmax=np
     return image_plane
 
 
+def _resident_raytracing_args(geos, Omega, t_injection, t_start_obs, J):
+    """raytracing_args for a geodesics.DeviceGeodesics: the same entries as float32 tensors on the record's device."""
+    from . import kgeo
+    dev = geos.device
+
+    def f32(v):
+        if not isinstance(v, torch.Tensor):
+            v = torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.float64)), device=dev)
+        return v.to(device=dev, dtype=torch.float32).contiguous()
+
+    gfac = kgeo.emission_factors(geos, Omega, backend='hip')[0]
+    scalar_J = np.isscalar(J) or (isinstance(J, torch.Tensor) and J.ndim == 0)
+    return OrderedDict({
+        'coords': f32(torch.stack([geos.x, geos.y, geos.z])),
+        'Omega': f32(Omega),
+        'J': J if scalar_J else f32(J),
+        'g': f32(gfac),
+        'dtau': f32(geos.dtau),
+        'Sigma': f32(geos.Sigma),
+        't_start_obs': t_start_obs,
+        't_geos': f32(geos.t),
+        't_injection': t_injection})
+
+
 def raytracing_args(geos, Omega, t_injection, t_start_obs, J=1.0, backend='numpy', device=None):
     """Ordered dict of the non-optimised ray-tracing arguments (network.py:850-894).
 
@@ -650,10 +674,16 @@ def raytracing_args(geos, Omega, t_injection, t_start_obs, J=1.0, backend='numpy
     (``kgeo.image_plane_geos``: r, theta, affine, potentials, constants of motion) the Doppler factor is derived from
     the azimuthal 4-velocity of ``Omega`` as the reference does (network.py:875-876); a pre-computed table may carry
     its own ``g`` instead.  ``backend`` (``'numpy'|'hip'``) is where that Doppler factor is computed
-    (``kgeo.emission_factors``; ``device``: a torch device for ``'hip'``, default the current one)."""
+    (``kgeo.emission_factors``; ``device``: a torch device for ``'hip'``, default the current one).
+
+    A resident record (``geodesics.DeviceGeodesics``) stays where it is: g is ``bhn_grf_doppler`` on its fields, ``Omega`` and ``J``
+    may be tensors, and every array entry is a contiguous float32 tensor on the record's device (rounded as ``np.float32``
+    rounds); a scalar ``J`` stays a scalar."""
     from . import kgeo
-    from .geodesics import _check_backend
+    from .geodesics import DeviceGeodesics, _check_backend
     _check_backend(backend)
+    if isinstance(geos, DeviceGeodesics):
+        return _resident_raytracing_args(geos, Omega, t_injection, t_start_obs, J)
     get = (lambda k: geos[k]) if isinstance(geos, dict) else (lambda k: getattr(geos, k))
 
     def has(k):

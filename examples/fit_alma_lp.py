@@ -9,7 +9,7 @@ The ALMA data file does not ship with either repository: when `preprocess.data_p
 orbiting Gaussian hotspot rendered through the same geometry at 30 deg, plus a constant shadow polarisation, Faraday
 rotation and noise) is written there first.
 
-    python examples/fit_alma_lp.py 20 30 40 [--config examples/fit_alma_lp.yaml] [--seeds 4] [--tracer hip] [--factors hip]
+    python examples/fit_alma_lp.py 20 30 40 [--config examples/fit_alma_lp.yaml] [--seeds 4] [--tracer hip] [--factors hip] [--resident]
 """
 import argparse
 import os
@@ -58,6 +58,8 @@ def main():
     ap.add_argument('--tracer', choices=['numpy', 'hip'], help="where the geodesics are integrated (default: the config's model.tracer, else numpy)")
     ap.add_argument('--factors', choices=['numpy', 'hip'],
                     help="where the Doppler factor and the transport factors J are computed (default: the config's model.factors, else numpy)")
+    ap.add_argument('--resident', action='store_true',
+                    help="keep the geodesic record, Omega, g, J and the ray-tracing arguments on the GPU (needs --tracer hip --factors hip)")
     args = ap.parse_args()
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -67,7 +69,9 @@ def main():
     if args.factors:
         model['factors'] = args.factors
     if not os.path.exists(pre['data_path']):
-        synthetic_flare(pre['data_path'], model, pre)
+        synthetic_flare(pre['data_path'], dict(model, resident=False), pre)          # (rendered on the host from NumPy arguments)
+    if args.resident:
+        model['resident'] = True
 
     # data: window-averaged light curves, split in time into a training and a validation part
     target, t_frames = bhnerf.alma.preprocess_data(**pre)

@@ -1,6 +1,6 @@
 """ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
 (include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h), libbhnerf_eql.so (include/bhnerf_eql.h), libbhnerf_flow.so
-(include/bhnerf_flow.h) and libbhnerf_rec.so (include/bhnerf_rec.h).
+(include/bhnerf_flow.h), libbhnerf_rec.so (include/bhnerf_rec.h) and libbhnerf_cls.so (include/bhnerf_cls.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -182,6 +182,23 @@ REC_SIGNATURES = {
     'bhn_rec_kepler': (C.c_int, [_P, _I64, _D, _D, _D, _P, _P]),
 }
 REC_LIBRARY = (REC_LIB_PATH, REC_SIGNATURES, 'bhn_rec_last_error', None)
+
+# libbhnerf_cls.so (include/bhnerf_cls.h): log closure amplitudes and the combined closure loss from (u, v), the eighth library,
+# described like the sixth and the seventh by a tuple of its own
+CLS_LIB_PATH = os.path.join(CSRC, 'libbhnerf_cls.so')
+
+
+class bhn_cls_term(C.Structure):
+    _fields_ = [('target', C.c_void_p), ('sigma', C.c_void_p), ('weight', C.c_double)]
+
+
+_CT = C.POINTER(bhn_cls_term)
+CLS_SIGNATURES = {
+    'bhn_cls_last_error': (C.c_char_p, []),
+    'bhn_cls_ws_bytes': (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    'bhn_cls_chi2': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _D, _D, _CT, _CT, _CT, _P, _P, _I32, _P, _I32, _F, _P, _P, _P, _SZ, _P]),
+}
+CLS_LIBRARY = (CLS_LIB_PATH, CLS_SIGNATURES, 'bhn_cls_last_error', None)
 _loaded = {}                 # path -> handle
 
 
@@ -192,7 +209,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec']), CSRC))
+        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec', 'libbhnerf_cls']), CSRC))
     return LIB_PATH
 
 
@@ -266,6 +283,11 @@ def rec_lib():
     return _lib('libbhnerf_rec', REC_LIBRARY)
 
 
+def cls_lib():
+    """The loaded closure-loss library."""
+    return _lib('libbhnerf_cls', CLS_LIBRARY)
+
+
 def check(rc):
     _check('libbhnerf_hip', rc)
 
@@ -292,6 +314,10 @@ def flow_check(rc):
 
 def rec_check(rc):
     _check('libbhnerf_rec', rc, REC_LIBRARY)
+
+
+def cls_check(rc):
+    _check('libbhnerf_cls', rc, CLS_LIBRARY)
 
 
 def stream_ptr(device=None):

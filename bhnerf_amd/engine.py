@@ -570,6 +570,93 @@ def chi2_eht_uv(images, op, target, sigma, scale, dtype, want_grad=True):
 _EHT_WS_BYTES = {}
 
 
+def closure_terms(dtype):
+    """The terms of a combined closure dtype: a '+'-joined string of 'amp', 'cphase', 'logcamp' in that (canonical) order, each
+    at most once -- 'logcamp', 'cphase+logcamp', 'amp+cphase', 'amp+cphase+logcamp', 'amp', ... -> a tuple of names; None for
+    anything else."""
+    if not isinstance(dtype, str):
+        return None
+    terms = tuple(dtype.split('+'))
+    if terms and terms == tuple(t for t in observation.CLOSURE_TERMS if t in terms) and len(set(terms)) == len(terms):
+        return terms
+    return None
+
+
+def chi2_closure_uv(images, op, target, sigma, scale, dtype, want_grad=True):
+    """scale * sum_d w_d chi^2_d over the terms of `dtype` (closure_terms) from an observation.ClosureDFT: ONE visibility pass
+    and one image gradient (bhn_cls_chi2).  `target` / `sigma`: the terms' arrays concatenated along the last axis in the
+    canonical order (ClosureDFT.pack).  Returns (loss[1], dimages or None); the four floats {total, amp, cphase, logcamp} stay
+    on the device as ``op.last_terms``.  AttributeError for a dtype the operator has no table for and for every count mismatch,
+    before any launch."""
+    terms = closure_terms(dtype)
+    if terms is None:
+        raise AttributeError('eht dtype ({}) not supported'.format(dtype))
+    sizes = op.term_sizes()
+    for t in terms:
+        if t not in sizes:
+            raise AttributeError("dtype='{}' needs a ClosureDFT with {}".format(dtype, 'triangles' if t == 'cphase' else 'quadrangles'))
+    nterm = sum(sizes[t] for t in terms)
+    if target.ndim < 2 or int(target.shape[-1]) != nterm:
+        raise AttributeError('target {} should end in {} entries ({}) for dtype={}'.format(
+            tuple(target.shape), nterm, ' + '.join('{} {}'.format(sizes[t], t) for t in terms), dtype))
+    for name, table in (('triangle', op.tri), ('quadrangle', op.quad)):
+        if table is not None and _table_range(op, name, table) is not None:
+            raise AttributeError('{} table: baseline indices must lie in [0, {}), found {}'.format(name, op.nvis, _table_range(op, name, table)))
+    N = int(np.prod(target.shape[:-1]))
+    img, op_dev, Sx = _eht_uv_operands(images, op, N)
+    if int(target.shape[0]) != int(op_dev.uv.shape[0]):
+        raise AttributeError('target of {} frames, uv of {}'.format(int(target.shape[0]), int(op_dev.uv.shape[0])))
+    dev, lib = img.device, _hip.cls_lib()
+    tgt = _eht_uv_array(target, dev, torch.float32, None).reshape(N, nterm)
+    sig = _eht_uv_array(sigma, dev, torch.float32, tuple(target.shape)).reshape(N, nterm)
+    structs, keep, o = {}, [], 0
+    for t in terms:                                          # a term's columns as an array of its own: what the library takes
+        tt, ss = tgt[:, o:o + sizes[t]], sig[:, o:o + sizes[t]]
+        if len(terms) > 1:
+            tt, ss = tt.contiguous(), ss.contiguous()
+        keep += [tt, ss]
+        structs[t] = _hip.bhn_cls_term(tt.data_ptr(), ss.data_ptr(), float(op.weights[t]))
+        o += sizes[t]
+    ncp, nca = (op.ncp if 'cphase' in terms else 0), (op.nca if 'logcamp' in terms else 0)
+    key = (N, op.nvis, ncp, nca, op.H, op.W)
+    nbytes = _CLS_WS_BYTES.get(key)
+    if nbytes is None:
+        nbytes = _CLS_WS_BYTES[key] = int(lib.bhn_cls_ws_bytes(*key))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((4,), dtype=torch.float32, device=dev)
+    dimg = torch.empty_like(img) if want_grad else None
+    psy, psx = op.psize
+    ref = lambda t: C.byref(structs[t]) if t in structs else None
+    args = (img.data_ptr(), op_dev.uv.data_ptr(), N, Sx, op.nvis, op.H, op.W, psx, psy, ref('amp'), ref('cphase'), ref('logcamp'),
+            _hip.ptr(op_dev.tri) if ncp else None, _hip.ptr(op_dev.tri_sign) if ncp else None, ncp, _hip.ptr(op_dev.quad) if nca else None, nca,
+            float(scale), loss.data_ptr(), dimg.data_ptr() if want_grad else None, ws.data_ptr(), nbytes, _hip.stream_ptr(dev))
+    if dev.index is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            rc = lib.bhn_cls_chi2(*args)
+    else:
+        rc = lib.bhn_cls_chi2(*args)
+    _hip.cls_check(rc)
+    op.last_terms = loss
+    return loss[:1], (dimg.reshape(images.shape) if want_grad else None)
+
+
+_CLS_WS_BYTES = {}
+_TABLE_RANGE = {}                 # id of a checked table -> (the table, what lies outside [0, nvis) or None)
+
+
+def _table_range(op, name, table):
+    """None when every index of `table` lies in [0, nvis), else the offending (min, max); checked once per table object (a device
+    table is read back once, not at every step)."""
+    hit = _TABLE_RANGE.get(id(table))
+    if hit is None or hit[0] is not table or hit[1] != op.nvis:
+        t = table.cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+        lo, hi = int(t.min()), int(t.max())
+        if len(_TABLE_RANGE) > 64:
+            _TABLE_RANGE.clear()
+        hit = _TABLE_RANGE[id(table)] = (table, op.nvis, None if (lo >= 0 and hi < op.nvis) else (lo, hi))
+    return hit[2]
+
+
 def _eht_uv_array(x, dev, dtype, shape):
     """`x` as a contiguous device tensor of `dtype` (broadcast to `shape` when given); a tensor that is all that already is taken
     as it is (the per-step path: TemporalBatchedArgs hands over device tensors)."""
@@ -582,7 +669,10 @@ def _eht_uv_array(x, dev, dtype, shape):
 
 def chi2_eht(images, A, target, sigma, scale, dtype, want_grad=True):
     """loss_fn_eht tail (network.py:541-564) on device -> (loss[1], dimages shaped like images or None).  ``A``: the dense DFT
-    matrices, or an ``observation.DirectDFT`` (the matrix-free path, chi2_eht_uv)."""
+    matrices, an ``observation.DirectDFT`` (the matrix-free path, chi2_eht_uv) or an ``observation.ClosureDFT`` (one weighted sum
+    of real-valued terms from one visibility pass, chi2_closure_uv)."""
+    if isinstance(A, observation.ClosureDFT):
+        return chi2_closure_uv(images, A, target, sigma, scale, dtype, want_grad=want_grad)
     if isinstance(A, observation.DirectDFT):
         return chi2_eht_uv(images, A, target, sigma, scale, dtype, want_grad=want_grad)
     code, img, Ar, tgt, sig, N, C_, nvis, R = _eht_operands(images, A, target, sigma, dtype)

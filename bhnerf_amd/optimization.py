@@ -478,6 +478,30 @@ class TrainStep(object):
         return cls.eht_arrays(t_frames, target, sigma, observation.DirectDFT(uv, fov, npix, triangles, pairs), dtype, scale)
 
     @classmethod
+    def eht_closure(cls, t_frames, uv, fov, npix, pairs, data, weights=None, scale=1.0, triangles=None, quadrangles=None):
+        """Training step on ONE weighted objective over real-valued EHT terms from the baselines' (u, v) coordinates:
+        ``data`` = {'cphase': (target, sigma), 'logcamp': (target, sigma), 'amp': (target, sigma)} (any of them), the loss
+        ``scale * sum_d weights[d] chi^2_d``.  One render, one visibility pass and one Adam step per call -- where the sum
+        ``TrainStep.eht_uv(.., 'cphase') + TrainStep.eht_uv(.., 'amp')`` renders and steps once per term.  ``pairs`` (nvis, 2)
+        names the stations of each baseline; ``triangles`` / ``quadrangles`` default to every station triple
+        (``observation.closure_triangles``) and the two independent quadrangles of every station quadruple
+        (``observation.closure_quadrangles``) when 'cphase' / 'logcamp' is in ``data``.  See ``observation.ClosureDFT``."""
+        terms = [t for t in observation.CLOSURE_TERMS if t in data]
+        if not terms or len(terms) != len(data):
+            raise AttributeError('data should name terms of {}, got {}'.format(observation.CLOSURE_TERMS, sorted(data)))
+        nsites = int(np.asarray(pairs).max()) + 1
+        if 'cphase' in terms and triangles is None:
+            triangles = observation.closure_triangles(nsites)
+        if 'logcamp' in terms and quadrangles is None:
+            quadrangles = observation.closure_quadrangles(nsites)
+        op = observation.ClosureDFT(uv, fov, npix, pairs=pairs, triangles=triangles if 'cphase' in terms else None,
+                                    quadrangles=quadrangles if 'logcamp' in terms else None, weights=weights)
+        target = op.pack({t: np.asarray(data[t][0]) for t in terms})
+        sigma = op.pack({t: np.broadcast_to(np.asarray(data[t][1]), np.shape(data[t][0])) for t in terms})
+        args = TemporalBatchedArgs(t_frames, [target, sigma, op])
+        return cls('+'.join(terms), args, network.gradient_step_eht, network.test_eht, scale)
+
+    @classmethod
     def eht(cls, t_frames, obs, image_fov, image_size, chisqdata, pol='I', scale=1.0):
         """Training step for an ehtim observation (optimization.py:219-268); needs the external ehtim
         package to split the observation per frame and build (target, sigma, A)."""

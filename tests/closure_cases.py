@@ -1,0 +1,124 @@
+"""Inputs and the float64 reference of the combined closure loss (libbhnerf_cls.so, observation.ClosureDFT), shared by
+tests/test_closure_cpu.py and tests/test_gpu_closure.py.
+
+Built on tests/eht_uv_cases.py: its blobs, dense128, FOV and MIN_AMP, and its generator -- the same draws in the same order
+(stations, images, a second draw of images for the data, the visibility sigmas, the closure-phase sigmas), so that at the seeds
+of eht_uv_cases.CASES the 'amp' and 'cphase' data ARE that module's; the log-closure-amplitude sigmas, uniform(0.05, 0.2), are
+drawn last.  The data are the float64 closure quantities of the second draw.
+
+The reference is float64 torch autograd of  scale * sum_d w_d chi^2_d  in table form: a dense complex128 A, the visibilities
+A . image, closure phases through (tri, tri_sign) and log closure amplitudes through quad."""
+import numpy as np
+import torch
+
+import eht_uv_cases as E
+from bhnerf_amd import observation
+
+TERMS = observation.CLOSURE_TERMS
+DTYPES = ('amp', 'cphase', 'logcamp', 'amp+cphase', 'amp+logcamp', 'cphase+logcamp', 'amp+cphase+logcamp')
+COMBINED = tuple(d for d in DTYPES if '+' in d)
+# name -> (H, W, B, seed, stations).  '13x7': nvis 6 (fewer than a baseline block of 8), ncp 4, nca 2.  '12x20': nvis 10 (two
+# baseline blocks), nca 10.  '9x11': nvis 45, ncp 120, nca 420 -- more quadrangles than the 256 lanes of a workgroup, so the
+# lane-stride loops wrap, and the gather scans 1680 table entries in 64-lane slices.
+CASES = {'13x7': E.CASES['13x7'], '12x20': E.CASES['12x20'], '9x11': (9, 11, 1, 2, 10)}
+PARAMS = [('13x7', 0), ('12x20', 0), ('12x20', 2), ('9x11', 0)]
+WEIGHTS = {'amp': 0.5, 'cphase': 1.0, 'logcamp': 0.25}        # the non-unit weights of the parity tests
+
+
+def closure_loss(images, A, data, terms, weights, scale, tri, sign, quad):
+    """float64: (total, d total / d images, {term: scale w_d chi^2_d}, visibilities) of scale * sum_d w_d chi^2_d in table form.
+    images (B, [S,] H, W); A (B, nvis, R) complex128; data {term: (target, sigma)} shaped (B, [S,] n_d)."""
+    img = torch.tensor(np.asarray(images, dtype=np.float64), requires_grad=True)
+    At = torch.tensor(A)
+    B = img.shape[0]
+    vec = img.reshape(B, -1, img.shape[-2] * img.shape[-1]).to(torch.complex128)
+    vis = torch.einsum('bkr,bsr->bsk', At, vec).reshape(tuple(img.shape[:-2]) + (A.shape[1],))
+    t64 = lambda v: torch.tensor(np.asarray(v, dtype=np.float64))
+    parts = {}
+    for d in terms:
+        tg, sg = t64(data[d][0]), t64(data[d][1])
+        if d == 'amp':
+            chi2 = (((vis.abs() - tg) / sg) ** 2).sum()
+        elif d == 'cphase':
+            bis = 1.0
+            for leg in range(3):
+                v = vis[..., torch.tensor(tri[:, leg].astype(np.int64))]
+                bis = bis * torch.where(torch.tensor(sign[:, leg] < 0), v.conj(), v)
+            chi2 = ((1.0 - torch.cos(tg - torch.angle(bis))) / sg ** 2).sum()
+        else:
+            la = torch.log(vis.abs())
+            q = torch.tensor(quad.astype(np.int64))
+            y = la[..., q[:, 0]] + la[..., q[:, 1]] - la[..., q[:, 2]] - la[..., q[:, 3]]
+            chi2 = (((y - tg) / sg) ** 2).sum()
+        parts[d] = scale * weights[d] * chi2
+    total = sum(parts[d] for d in terms)
+    total.backward()
+    return total.item(), img.grad.numpy(), {d: v.item() for d, v in parts.items()}, vis.detach().numpy()
+
+
+_CASES, _REFS = {}, {}
+
+
+def case(name, Sx=0):
+    """Everything about one input set, computed once and left unchanged: the operator pieces (uv, pairs, triangles, quadrangles,
+    tri, sign, quad), images (B, [Sx,] H, W) float32, data {term: (target, sigma)} float32 and the float64 visibilities."""
+    key = (name, Sx)
+    if key in _CASES:
+        return _CASES[key]
+    H, W, B, seed, ns = CASES[name]
+    rng = np.random.default_rng(seed)
+    pos = rng.normal(size=(B, ns, 2)) * 3e9
+    pairs = np.array([(i, j) for i in range(ns) for j in range(i + 1, ns)])
+    uv = np.ascontiguousarray(pos[:, pairs[:, 0]] - pos[:, pairs[:, 1]])
+    triangles, quadrangles = observation.closure_triangles(ns), observation.closure_quadrangles(ns)
+    tri, sign = observation.closure_table(pairs, triangles)
+    quad = observation.quadrangle_table(pairs, quadrangles)
+    shape = (B, Sx, H, W) if Sx else (B, H, W)
+    images, truth = E.blobs(rng, shape), E.blobs(rng, shape)
+    A = E.dense128(uv, E.FOV, H, W)
+    vis_of = lambda im: np.einsum('bkr,bsr->bsk', A, im.astype(np.float64).reshape(B, -1, H * W)).reshape(shape[:-2] + (len(pairs),))
+    vis_truth, vis = vis_of(truth), vis_of(images)
+    op = observation.ClosureDFT(uv, E.FOV, (H, W), pairs=pairs, triangles=triangles, quadrangles=quadrangles)
+    s_vis = (0.05 * np.abs(vis_truth).mean() * rng.uniform(0.5, 1.5, vis_truth.shape)).astype(np.float32)
+    cp, lca = op.closure_phases(vis_truth), op.log_closure_amplitudes(vis_truth)
+    data = {'amp': (np.abs(vis_truth).astype(np.float32), s_vis),
+            'cphase': (cp.astype(np.float32), rng.uniform(0.05, 0.2, cp.shape).astype(np.float32)),
+            'logcamp': (lca.astype(np.float32), rng.uniform(0.05, 0.2, lca.shape).astype(np.float32))}
+    amp = np.abs(vis)
+    out = dict(name=name, H=H, W=W, B=B, ns=ns, Sx=Sx, uv=uv, pairs=pairs, triangles=triangles, quadrangles=quadrangles, tri=tri, sign=sign,
+               quad=quad, images=images, data=data, A128=A, vis=vis, min_amp=float(amp.min() / amp.max()))
+    _CASES[key] = out
+    return out
+
+
+def reference(c, dtype, weights=None, scale=1.0):
+    """(total, grad, {term: value}, vis) of the float64 reference for one '+'-joined dtype, computed once per argument set."""
+    weights = dict({t: 1.0 for t in TERMS}, **(weights or {}))
+    key = (c['name'], c['Sx'], dtype, tuple(sorted(weights.items())), scale)
+    if key not in _REFS:
+        _REFS[key] = closure_loss(c['images'], c['A128'], c['data'], dtype.split('+'), weights, scale, c['tri'], c['sign'], c['quad'])
+    return _REFS[key]
+
+
+def operator(c, dtype, weights=None):
+    """The ClosureDFT of a case with the tables the terms of `dtype` need."""
+    terms = dtype.split('+')
+    return observation.ClosureDFT(c['uv'], E.FOV, (c['H'], c['W']), pairs=c['pairs'], triangles=c['triangles'] if 'cphase' in terms else None,
+                                  quadrangles=c['quadrangles'] if 'logcamp' in terms else None, weights=weights)
+
+
+def packed(c, dtype):
+    """(target, sigma) of `dtype`: the terms' arrays concatenated along the last axis in the canonical order."""
+    terms = dtype.split('+')
+    return (np.concatenate([c['data'][t][0] for t in terms], axis=-1), np.concatenate([c['data'][t][1] for t in terms], axis=-1))
+
+
+def errors(dtype, total, parts, grad, ref):
+    """Relative errors against reference(): {'total', 'amp', 'cphase', 'logcamp' (present terms), 'dimages' (when grad is given)}."""
+    ref_total, ref_grad, ref_parts, _ = ref
+    out = {'total': abs(total - ref_total) / abs(ref_total)}
+    for t in dtype.split('+'):
+        out[t] = abs(parts[t] - ref_parts[t]) / abs(ref_parts[t])
+    if grad is not None:
+        out['dimages'] = E.rel_max(grad, ref_grad)
+    return out

@@ -1,0 +1,317 @@
+"""GPU tests of the combined closure loss: libbhnerf_cls.so (csrc/eht_closure.hip) behind observation.ClosureDFT, engine.chi2_eht
+and TrainStep.eht_closure -- bitwise against libbhnerf_eht.so where the two compute the same thing, against the float64 reference
+of tests/closure_cases.py, and held to the caller-owned-buffer contract of include/bhnerf_cls.h.
+
+Bounds.  The 'amp' and 'cphase' terms, and totals and gradients made of them alone: the project's f32 bound, 2e-5 -- the loss
+relative, dimages relative to its largest element.  The 'logcamp' term divides by |V| four times and its residual over sigma is
+of order 1 to 10, so it and every total or gradient that contains it are NOT assumed to meet that bound: their error against the
+float64 reference was measured on an MI355X (MEASURED_* below) and the tests bound it at ten times the measurement
+(box-to-box libm and ordering differences) and never above 1e-3 -- the rule of STEP_GRAD_BOUND in tests/test_gpu_eht_uv.py.
+Every case has its smallest visibility amplitude >= 0.05 of the largest (asserted on the float64 reference)."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import closure_cases as K                                              # noqa: E402
+import eht_uv_cases as E                                               # noqa: E402
+from guarded import Guarded                                            # noqa: E402
+from gpu_support import dev                                           # noqa: E402,F401
+
+# Largest error against float64 over the cases of closure_cases.PARAMS and every dtype that holds 'logcamp', with and without
+# gradient, weights closure_cases.WEIGHTS, scale 2 -- measured on an MI355X.  'loss': the logcamp term and the totals that hold it,
+# relative (largest: the term itself at 12x20, 1.2e-6); 'dimages': relative to the largest element (largest: 'logcamp' alone at
+# 13x7, 2.8e-6).  The host build (tests/test_closure_cpu.py, g++ -O2 -ffp-contract=off) gives 1.6e-6 and 6.1e-6 on the same cases;
+# 'amp' and 'cphase' alone and together measured 6.8e-7 / 8.5e-7 against their bound of 2e-5.
+MEASURED_LOGCAMP = {'loss': 1.2e-6, 'dimages': 2.8e-6}
+LOGCAMP_BOUND = {k: min(10.0 * v, 1e-3) for k, v in MEASURED_LOGCAMP.items()}
+# relative L2 between the parameter gradient of one 'cphase+logcamp' training step and the sum of the two single-term passes from
+# the same parameters (12 x 20 rays x 24 samples, 4x64 f32, B = 3), measured on an MI355X; bounded the same way
+MEASURED_STEP_GRAD_L2 = 4.98e-7
+STEP_GRAD_BOUND = min(10.0 * MEASURED_STEP_GRAD_L2, 1e-3)
+
+
+def _bound(names, what):
+    return LOGCAMP_BOUND[what] if 'logcamp' in names else E.F32_TOL
+
+
+def _chi2(c, dtype, dev, want_grad=True, scale=1.0, weights=None, op=None, images=None, data=None):
+    """engine.chi2_eht on the ClosureDFT of a case -> (loss[1], dimages, the four floats of op.last_terms as float32 NumPy)."""
+    from bhnerf_amd import engine
+    op = op if op is not None else K.operator(c, dtype, weights)
+    target, sigma = data if data is not None else K.packed(c, dtype)
+    images = torch.as_tensor(c['images'] if images is None else images, device=dev)
+    loss, dimg = engine.chi2_eht(images, op, target, sigma, scale, dtype, want_grad=want_grad)
+    assert loss.shape == (1,) and op.last_terms.shape == (4,) and op.last_terms.dtype == torch.float32
+    return loss, dimg, op.last_terms.cpu().numpy()
+
+
+@pytest.mark.parametrize('dtype', ['amp', 'cphase'])
+@pytest.mark.parametrize('name,Sx', K.PARAMS)
+def test_a_single_term_at_weight_one_is_the_uv_library_bit_for_bit(dev, name, Sx, dtype):
+    """The reference here is libbhnerf_eht.so (bhn_eht_chi2_uv), not the new code."""
+    from bhnerf_amd import engine, observation
+    c = K.case(name, Sx)
+    images = torch.as_tensor(c['images'], device=dev)
+    target, sigma = c['data'][dtype]
+    plain = observation.DirectDFT(c['uv'], E.FOV, (c['H'], c['W']), triangles=c['triangles'] if dtype == 'cphase' else None,
+                                  pairs=c['pairs'] if dtype == 'cphase' else None)
+    for scale in (1.0, 0.37):
+        for want_grad in (True, False):
+            want_loss, want_dimg = engine.chi2_eht(images, plain, target, sigma, scale, dtype, want_grad=want_grad)
+            loss, dimg, terms = _chi2(c, dtype, dev, want_grad, scale)
+            assert torch.equal(loss, want_loss), (scale, loss.item(), want_loss.item())
+            assert (dimg is None and want_dimg is None) if not want_grad else torch.equal(dimg, want_dimg)
+            assert terms[0] == terms[1 + K.TERMS.index(dtype)] == want_loss.item() and np.count_nonzero(terms[1:]) == 1
+    # the visibilities the terms were computed from are bhn_eht_vis'; with the tables of all three terms the single term keeps its bits
+    full = K.operator(c, 'amp+cphase+logcamp')
+    want_loss, want_dimg = engine.chi2_eht(images, plain, target, sigma, 1.0, dtype)
+    loss, dimg, _ = _chi2(c, dtype, dev, op=full)
+    assert torch.equal(loss, want_loss) and torch.equal(dimg, want_dimg)
+    assert torch.equal(torch.view_as_real(full.observe(images)), torch.view_as_real(plain.observe(images)))
+
+
+@pytest.mark.parametrize('want_grad', [True, False])
+@pytest.mark.parametrize('name,Sx', K.PARAMS)
+def test_parity_with_float64(dev, name, Sx, want_grad):
+    c = K.case(name, Sx)
+    assert c['min_amp'] >= E.MIN_AMP, c['min_amp']
+    for dtype in K.DTYPES:
+        terms = dtype.split('+')
+        ref = K.reference(c, dtype, K.WEIGHTS, 2.0)
+        loss, dimg, four = _chi2(c, dtype, dev, want_grad, 2.0, K.WEIGHTS)
+        assert loss.item() == four[0] and all(four[1 + K.TERMS.index(t)] == 0 for t in K.TERMS if t not in terms)
+        parts = {t: float(four[1 + K.TERMS.index(t)]) for t in terms}
+        if want_grad:
+            assert dimg.shape == c['images'].shape and dimg.dtype == torch.float32
+        else:
+            assert dimg is None
+        err = K.errors(dtype, loss.item(), parts, dimg.cpu().numpy() if want_grad else None, ref)
+        print('\n[closure] %s Sx %d %-18s %s' % (name, Sx, dtype, '  '.join('%s %.1e' % kv for kv in err.items())), end='')
+        for t in terms:
+            assert err[t] <= _bound([t], 'loss'), (dtype, t, err)
+        assert err['total'] <= _bound(terms, 'loss'), (dtype, err)
+        if want_grad:
+            assert err['dimages'] <= _bound(terms, 'dimages'), (dtype, err)
+    print()
+
+
+def _plane_sum(values):
+    """float32 sum over axis 0 in the order of cls_loss_sum_kernel (eht_loss_sum_kernel's): lane i of 256 adds the planes i, i + 256,
+    ...; each wave of 64 lanes adds its lanes in an xor butterfly (offsets 32 down to 1); the four waves are added in order."""
+    values = np.asarray(values, dtype=np.float32)
+    lanes = np.zeros((256,) + values.shape[1:], dtype=np.float32)
+    for i, v in enumerate(values):
+        lanes[i % 256] += v
+    waves = []
+    for w in range(4):
+        a = lanes[64 * w:64 * w + 64]
+        for o in (32, 16, 8, 4, 2, 1):
+            a = a + a[np.arange(64) ^ o]
+        waves.append(a[0])
+    return ((waves[0] + waves[1]) + waves[2]) + waves[3]
+
+
+@pytest.mark.parametrize('dtype', ['logcamp', 'cphase+logcamp', 'amp+cphase+logcamp'])
+def test_bitwise_reproducible_and_independent_of_the_batch(dev, dtype):
+    c = K.case('12x20')
+    op = K.operator(c, dtype, K.WEIGHTS)
+    loss, dimg, four = _chi2(c, dtype, dev, op=op)
+    loss2, dimg2, four2 = _chi2(c, dtype, dev, op=op)
+    assert torch.equal(loss, loss2) and torch.equal(dimg, dimg2) and four.tobytes() == four2.tobytes()
+    assert four[0] == np.float32(np.float32(four[1] + four[2]) + four[3])          # total = amp + cphase + logcamp in float32, in that order
+    # the forward-only call gives the same four floats
+    assert _chi2(c, dtype, dev, want_grad=False, op=op)[2].tobytes() == four.tobytes()
+    # every frame alone (B = 1) is its row of the B = 3 call, bit for bit; the B = 3 terms are the frames' own terms added in the
+    # library's one fixed order
+    tgt, sig = K.packed(c, dtype)
+    alone = []
+    for b in range(3):
+        _, dimg1, four1 = _chi2(c, dtype, dev, op=op.take([b]), images=c['images'][b:b + 1], data=(tgt[b:b + 1], sig[b:b + 1]))
+        assert torch.equal(dimg1[0], dimg[b]), b
+        alone.append(four1[1:])
+    assert _plane_sum(np.array(alone)).tobytes() == four[1:].tobytes()
+    # scale 2, weight 1 and scale 1, weight 2: one effective scale, the same bits
+    terms = dtype.split('+')
+    la, da, fa = _chi2(c, dtype, dev, scale=2.0)
+    lb, db, fb = _chi2(c, dtype, dev, scale=1.0, weights={t: 2.0 for t in terms})
+    assert torch.equal(la, lb) and torch.equal(da, db) and fa.tobytes() == fb.tobytes()
+
+
+def test_zero_amplitude_rule(dev):
+    """A frame before the injection renders an exactly zero image: 'logcamp' contributes 0 there and a zero gradient, nothing is NaN."""
+    c = K.case('13x7')
+    images = c['images'].copy()
+    images[0] = 0.0
+    for dtype in ('logcamp', 'amp+cphase+logcamp'):
+        loss, dimg, four = _chi2(c, dtype, dev, images=images)
+        full = _chi2(c, dtype, dev)
+        assert np.isfinite(four).all() and bool(torch.isfinite(dimg).all()) and torch.equal(dimg[1], full[1][1])
+        assert 0 < four[3] < full[2][3]
+        if dtype == 'logcamp':
+            assert not bool(dimg[0].any())
+
+
+GUARD = 4096          # bytes on either side of a buffer: 0xA5 there, the buffer itself poisoned with NaN bytes (0xFF)
+
+
+@pytest.mark.parametrize('dtype', ['logcamp', 'amp', 'amp+cphase+logcamp'])
+@pytest.mark.parametrize('name,Sx', [('13x7', 0), ('12x20', 2), ('9x11', 0)])
+def test_buffer_contract(dev, name, Sx, dtype):
+    from bhnerf_amd import _hip
+    lib = _hip.cls_lib()
+    c = K.case(name, Sx)
+    terms = dtype.split('+')
+    H, W, B, S = c['H'], c['W'], c['B'], max(Sx, 1)
+    N, nvis = B * S, len(c['pairs'])
+    ncp = len(c['tri']) if 'cphase' in terms else 0
+    nca = len(c['quad']) if 'logcamp' in terms else 0
+    img = torch.as_tensor(c['images'], device=dev).contiguous()
+    uv = torch.as_tensor(c['uv'], device=dev)
+    held = {t: [torch.as_tensor(a, device=dev).contiguous() for a in c['data'][t]] for t in terms}
+    structs = {t: _hip.bhn_cls_term(v[0].data_ptr(), v[1].data_ptr(), 1.0) for t, v in held.items()}
+    ref_of = lambda t: C.byref(structs[t]) if t in structs else None
+    tri, sign, quad = (torch.as_tensor(c[k], device=dev) for k in ('tri', 'sign', 'quad'))
+    need = int(lib.bhn_cls_ws_bytes(N, nvis, ncp, nca, H, W))
+    assert need > 0
+    psy, psx = E.FOV / H, E.FOV / W
+    stream = _hip.stream_ptr(dev)
+
+    def call(loss, dimages, ws, ws_bytes):
+        return lib.bhn_cls_chi2(_hip.ptr(img), _hip.ptr(uv), N, S, nvis, H, W, psx, psy, ref_of('amp'), ref_of('cphase'), ref_of('logcamp'),
+                                _hip.ptr(tri) if ncp else None, _hip.ptr(sign) if ncp else None, ncp, _hip.ptr(quad) if nca else None, nca,
+                                1.0, loss, dimages, ws, ws_bytes, stream)
+
+    mk = lambda label, nbytes: Guarded(label, nbytes, 0xFF, dev, guard=GUARD, guard_fill=0xA5)
+    loss, dimg, ws = mk('loss', 16), mk('dimages', 4 * N * H * W), mk('ws', need)
+    intact = lambda *bufs: all(b.disturbed() is None for b in bufs)
+    # one byte too little workspace: refused, nothing launched
+    assert call(loss.ptr, dimg.ptr, ws.ptr, need - 1) == _hip.BHN_EWORKSPACE
+    with pytest.raises(_hip.HipError, match='workspace'):
+        _hip.cls_check(_hip.BHN_EWORKSPACE)
+    torch.cuda.synchronize()
+    assert loss.untouched() and dimg.untouched() and ws.untouched()
+    # forward only: the would-be gradient buffer stays poisoned, and so do the workspace regions of the backward pass
+    assert call(loss.ptr, None, ws.ptr, need) == 0
+    torch.cuda.synchronize()
+    ref_total, ref_grad, ref_parts, _ = K.reference(c, dtype)
+    four = loss.f32().copy()
+    assert dimg.untouched() and np.isfinite(four).all() and abs(float(four[0]) - ref_total) <= _bound(terms, 'loss') * abs(ref_total)
+    assert intact(loss, ws, dimg)
+    if dtype != 'amp':                                                                     # (gv of 'amp' alone goes where the adjoint reads it)
+        gv_bytes = 256 * ((8 * N * nvis + 255) // 256)
+        eht_bytes = int(_hip.eht_lib().bhn_eht_ws_bytes(N, nvis, ncp, H, W))
+        assert bool((ws.mid[eht_bytes + gv_bytes:eht_bytes + gv_bytes + 8 * N * nvis] == 0xFF).all())      # the summed gv: the gather's output
+    # loss and gradient into poisoned buffers of exactly the documented sizes
+    loss.mid.fill_(0xFF); ws.mid.fill_(0xFF)
+    assert call(loss.ptr, dimg.ptr, ws.ptr, need) == 0
+    torch.cuda.synchronize()
+    got = dimg.f32().reshape(ref_grad.shape)
+    assert np.isfinite(got).all() and np.isfinite(loss.f32()).all()                        # every element written
+    assert loss.f32().tobytes() == four.tobytes()
+    assert intact(loss, ws, dimg)
+    assert E.rel_max(got, ref_grad) <= _bound(terms, 'dimages')
+    for t in terms:
+        assert abs(float(four[1 + K.TERMS.index(t)]) - ref_parts[t]) <= _bound([t], 'loss') * abs(ref_parts[t]), t
+
+
+def test_one_training_step_is_one_render_one_pass_one_adam_step(dev):
+    """TrainStep.eht_closure on 12 x 20 rays x 24 samples, 4x64 f32, B = 3, a compact 5-station array: 'cphase' alone leaves the
+    parameters of TrainStep.eht_uv(dtype='cphase'), bit for bit; 'cphase+logcamp' gives the parameter gradient of the two
+    single-term passes added (the backward is linear in dimages)."""
+    from bhnerf_amd import observation, optimization, units
+    from test_gpu_eht_uv import _network_case
+    s = _network_case(12, 20, dev, seed=12, spread=0.5e9)
+    op = observation.ClosureDFT(s['uv'], E.FOV, (12, 20), pairs=s['pairs'], triangles=observation.closure_triangles(5),
+                                quadrangles=observation.closure_quadrangles(5))
+    cp = (op.closure_phases(s['vis']) + 0.3).astype(np.float32)
+    lca = (op.log_closure_amplitudes(s['vis']) + 0.2).astype(np.float32)
+    sigma = np.full(cp.shape, 0.1, dtype=np.float32)
+    t_frames = s['t_frames'] * units.hr
+    mk = lambda data: optimization.TrainStep.eht_closure(t_frames, s['uv'], E.FOV, (12, 20), s['pairs'], data)
+    steps = {'uv': optimization.TrainStep.eht_uv(t_frames, cp, sigma, s['uv'], E.FOV, (12, 20), dtype='cphase',
+                                                 triangles=observation.closure_triangles(5), pairs=s['pairs']),
+             'cphase': mk({'cphase': (cp, sigma)}), 'logcamp': mk({'logcamp': (lca, sigma)}),
+             'both': mk({'cphase': (cp, sigma), 'logcamp': (lca, sigma)})}
+    assert all(st.num_losses == 1 for st in steps.values())
+    hp = {'num_iters': 10, 'lr_init': 1e-4, 'lr_final': 1e-5, 'seed': 3}
+    res = {}
+    for kind, reps in (('uv', 1), ('cphase', 1), ('logcamp', 1), ('both', 2)):
+        for rep in range(reps):
+            opt = optimization.Optimizer(hp, s['pred'], s['rt'])
+            with torch.no_grad():
+                opt.state.flat.copy_(s['params'].flat)
+            loss, state, imgs = steps[kind](opt.state, s['rt'], np.arange(3))
+            assert imgs.shape == (1, 3, 12, 20) and state.step == 1
+            res[(kind, rep)] = (float(loss.sum()), state.grad[:state.flat.numel()].clone(), state.flat.clone(), imgs[0].clone())
+    vis = op.observe(res[('both', 0)][3]).cpu().numpy()
+    assert np.abs(vis).min() >= E.MIN_AMP * np.abs(vis).max(), (np.abs(vis).min(), np.abs(vis).max())     # off the 1 / |vis| pole
+    # 'cphase' alone: the step of the (u, v) library, bit for bit
+    assert res[('cphase', 0)][0] == res[('uv', 0)][0] and torch.equal(res[('cphase', 0)][1], res[('uv', 0)][1])
+    assert torch.equal(res[('cphase', 0)][2], res[('uv', 0)][2]) and float((res[('uv', 0)][2] - s['params'].flat).abs().max()) > 0
+    # two runs of the combined step are bitwise equal
+    assert res[('both', 0)][0] == res[('both', 1)][0]
+    assert torch.equal(res[('both', 0)][1], res[('both', 1)][1]) and torch.equal(res[('both', 0)][2], res[('both', 1)][2])
+    lb, gb, _, _ = res[('both', 0)]
+    want = res[('cphase', 0)][1].double() + res[('logcamp', 0)][1].double()
+    l2 = float((gb.double() - want).norm() / want.norm())
+    lsum = res[('cphase', 0)][0] + res[('logcamp', 0)][0]
+    print('\n[closure] training step cphase+logcamp 12x20: loss %.6e, single terms %.6e + %.6e, parameter gradient relative L2 to their sum %.2e'
+          % (lb, res[('cphase', 0)][0], res[('logcamp', 0)][0], l2))
+    assert float(want.norm()) > 0 and float(res[('logcamp', 0)][1].norm()) > 0 and abs(lb - lsum) <= 1e-5 * abs(lsum)
+    assert l2 <= STEP_GRAD_BOUND, l2
+
+
+def test_errors_fire_before_any_launch(dev):
+    from bhnerf_amd import engine, network, units
+    c = K.case('12x20')
+    img = torch.as_tensor(c['images'], device=dev)
+    tgt, sig = K.packed(c, 'cphase+logcamp')
+    closed = K.operator(c, 'cphase+logcamp')
+    chi2 = lambda op, t, s, dtype, im=img: engine.chi2_eht(im, op, t, s, 1.0, dtype)
+    with pytest.raises(AttributeError):                                # an unknown dtype, a term order that is not canonical, 'vis'
+        chi2(closed, tgt, sig, 'nope')
+    with pytest.raises(AttributeError):
+        chi2(closed, tgt, sig, 'logcamp+cphase')
+    with pytest.raises(AttributeError):                                # 'vis' with triangles
+        chi2(closed, *c['data']['amp'], 'vis')
+    with pytest.raises(AttributeError):                                # a dtype the operator has no table for
+        chi2(K.operator(c, 'cphase'), tgt, sig, 'cphase+logcamp')
+    with pytest.raises(AttributeError):
+        chi2(K.operator(c, 'logcamp'), tgt, sig, 'cphase+logcamp')
+    for plain in (E.operator(E.case('12x20'), 'cphase'), E.operator(E.case('12x20'), 'amp')):      # a plain DirectDFT
+        with pytest.raises(AttributeError):
+            chi2(plain, tgt, sig, 'cphase+logcamp')
+        with pytest.raises(AttributeError):
+            chi2(plain, *c['data']['logcamp'], 'logcamp')
+        with pytest.raises(AttributeError):                            # ... through the training step's body and loss_fn_eht as well
+            network.test_eht(None, units.hr, 'cphase+logcamp', tgt, sig, plain, *([None] * 10), 1.0)
+        with pytest.raises(AttributeError):
+            network.gradient_step_eht(None, units.hr, 'logcamp', tgt, sig, plain, *([None] * 10), 1.0)
+    with pytest.raises(AttributeError):                                # dense matrices
+        engine.chi2_eht(img.reshape(3, -1), closed.dense()[:, 0], *c['data']['logcamp'], 1.0, 'logcamp')
+    with pytest.raises(AttributeError):                                # the last axis
+        chi2(closed, tgt[:, :19], sig[:, :19], 'cphase+logcamp')
+    with pytest.raises(AttributeError):
+        chi2(closed, tgt, sig, 'logcamp')
+    with pytest.raises(AttributeError):                                # Stokes count: two planes of target, one of images
+        chi2(closed, np.stack([tgt, tgt], 1), np.stack([sig, sig], 1), 'cphase+logcamp')
+    with pytest.raises(AttributeError):                                # frame count
+        chi2(closed.take([0, 1]), tgt, sig, 'cphase+logcamp')
+    with pytest.raises(AttributeError):                                # image size
+        chi2(closed, tgt, sig, 'cphase+logcamp', img[:, :, :19])
+    for table in ('quad', 'tri'):                                      # a table index out of range (the constructor refuses it; set behind its back)
+        bad = K.operator(c, 'cphase+logcamp')
+        t = getattr(bad, table).copy()
+        t[3, 1] = 10
+        setattr(bad, table, t)
+        with pytest.raises(AttributeError, match='table'):
+            chi2(bad, tgt, sig, 'cphase+logcamp')
+    # what was refused left no error behind: the next call runs
+    loss, dimg = chi2(closed, tgt, sig, 'cphase+logcamp')
+    assert np.isfinite(loss.item()) and bool(torch.isfinite(dimg).all())

@@ -6,7 +6,11 @@ its sign/ordering conventions (parity unpinned: SURVEY 8c iii).
 
 ``DirectDFT`` is the same operator kept as its (u, v) coordinates: the losses then run matrix-free (libbhnerf_eht.so).
 ``ClosureDFT`` is a ``DirectDFT`` with the closure tables (triangles, quadrangles) and weights of one combined objective over
-'amp', 'cphase' and 'logcamp', the log closure amplitude (libbhnerf_cls.so)."""
+'amp', 'cphase' and 'logcamp', the log closure amplitude (libbhnerf_cls.so).
+
+``Array``, ``empty_eht_obs``, ``observe_same`` and ``Observation`` lead from a station table to those operators: baseline
+coordinates, elevations, thermal noise, synthetic visibilities and the targets, sigmas and closure tables of a station set that
+changes from frame to frame -- what the reference asks of ehtim (observation.py:79-222), in NumPy float64 on the host."""
 import numpy as np
 
 
@@ -319,3 +323,283 @@ class ClosureDFT(DirectDFT):
             out[t] = array[..., o:o + sizes[t]]
             o += sizes[t]
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# From a station table to what the operators above take: baseline coordinates, thermal noise and per-frame closure tables of an
+# earth-rotation synthesis (reference: observation.py:79-119 and 121-222 hand this to ehtim).  NumPy float64 on the host.
+# ---------------------------------------------------------------------------------------------------------------------------
+C_LIGHT = 299792458.0            # m / s
+QUANT_EFFICIENCY = 0.88          # 2-bit quantisation, the factor of the thermal noise of one baseline
+
+
+class Array(object):
+    """A station table: ``names`` (nsites,), ``xyz`` (nsites, 3) earth-fixed metres, ``sefd`` (nsites,) Jy."""
+
+    def __init__(self, names, xyz, sefd):
+        self.names = [str(n) for n in names]
+        self.xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64))
+        self.sefd = np.ascontiguousarray(np.asarray(sefd, dtype=np.float64))
+        n = len(self.names)
+        if n < 2 or self.xyz.shape != (n, 3) or self.sefd.shape != (n,):
+            raise AttributeError('an Array takes n >= 2 names, xyz (n, 3) and sefd (n,); got {} names, xyz {}, sefd {}'.format(
+                n, self.xyz.shape, self.sefd.shape))
+        if not (np.isfinite(self.xyz).all() and np.isfinite(self.sefd).all() and (self.sefd > 0).all()):
+            raise AttributeError('station coordinates must be finite and SEFDs finite and positive')
+
+    @classmethod
+    def load_txt(cls, path):
+        """A table in the text format of ehtim's arrays: '#' lines and blank lines are skipped, the columns are
+        ``NAME X Y Z SEFDR [SEFDL ...]`` (further columns ignored).  The station's SEFD is (SEFDR + SEFDL) / 2, SEFDL = SEFDR when
+        the table has no such column."""
+        names, xyz, sefd = [], [], []
+        with open(path) as f:
+            for line in f:
+                col = line.split()
+                if not col or col[0].startswith('#'):
+                    continue
+                if len(col) < 5:
+                    raise AttributeError('{}: a station line needs NAME X Y Z SEFDR, got {!r}'.format(path, line.rstrip()))
+                names.append(col[0])
+                xyz.append([float(v) for v in col[1:4]])
+                sefd.append(0.5 * (float(col[4]) + float(col[5] if len(col) > 5 else col[4])))
+        return cls(names, xyz, sefd)
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def pairs(self):
+        """Every station pair i < j: (nsites (nsites - 1) / 2, 2)."""
+        n = len(self)
+        return np.array([(i, j) for i in range(n) for j in range(i + 1, n)], dtype=np.int64)
+
+
+def utc_to_gmst(mjd, utc_hours):
+    """Greenwich mean sidereal time in hours [0, 24) at ``utc_hours`` of the day ``mjd``: the IAU-1982 linear form
+    18.697374558 + 24.06570982441908 D, D the days from JD 2451545.0, with UT1 = UTC."""
+    D = (np.asarray(mjd, dtype=np.float64) - 51544.5) + np.asarray(utc_hours, dtype=np.float64) / 24.0
+    return np.mod(18.697374558 + 24.06570982441908 * D, 24.0)
+
+
+def empty_eht_obs(array, nt, tint, tstart=4.0, tstop=15.5, ra=17.761121055553343, dec=-29.00784305556, rf=226191789062.5,
+                  mjd=57850, bw=1856000000.0, timetype='UTC', polrep='stokes', *, times=None, elev_min=10.0, elev_max=85.0):
+    """The empty observation of ``array`` (an ``Array``) on a source: baseline coordinates, elevations and thermal noise of ``nt``
+    scans -- the reference's name, argument order and defaults (observation.py:79), so its ``obs_params`` works with only 'array'
+    changed.  ``tint``: integration time in seconds; ``tstart`` / ``tstop``: hours, scan k at tstart + k (tstop - tstart) / nt;
+    ``times`` (hours) overrides that grid; ``ra``: hours, ``dec``: degrees; ``rf``, ``bw``: Hz; ``timetype``: 'UTC' (converted with
+    ``utc_to_gmst`` on the day ``mjd``) or 'GMST' (the times are Greenwich mean sidereal hours).  ``polrep``: 'stokes' only.
+
+    Baselines are all station pairs i < j.  (u, v) in wavelengths c / rf by the closed form of Thompson, Moran & Swenson eq. 4.1
+    for the baseline vector xyz_j - xyz_i; elevation arcsin(s . r) per station with r the geocentric unit vector; a baseline is
+    ``up`` when both stations lie strictly between ``elev_min`` and ``elev_max`` degrees; thermal noise
+    sigma_ij = sqrt(sefd_i sefd_j / (2 bw tint)) / 0.88.
+
+    Not ehtim: no precession or nutation, no geodetic latitude, UT1 = UTC, and none of ehtim's scan bookkeeping (tadv rounding,
+    time-sorted records, conjugate ordering) -- parity with ``ehtim.Array.obsdata`` is NOT pinned."""
+    if not isinstance(array, Array):
+        raise AttributeError('array should be an observation.Array (Array.load_txt(path)), got {}'.format(type(array).__name__))
+    if polrep != 'stokes':
+        raise AttributeError("polrep ({}) not supported: 'stokes' only".format(polrep))
+    if timetype not in ('UTC', 'GMST'):
+        raise AttributeError("timetype ({}) should be 'UTC' or 'GMST'".format(timetype))
+    if times is None:
+        if int(nt) < 1:
+            raise AttributeError('nt must be at least 1')
+        times = float(tstart) + np.arange(int(nt)) * ((float(tstop) - float(tstart)) / int(nt))
+    times = np.atleast_1d(np.asarray(times, dtype=np.float64))
+    if times.ndim != 1 or times.size != int(nt):
+        raise AttributeError('times should hold nt = {} hours, got the shape {}'.format(nt, times.shape))
+    if not (tint > 0 and bw > 0 and rf > 0):
+        raise AttributeError('tint, bw and rf must be positive')
+    gmst = np.mod(times, 24.0) if timetype == 'GMST' else utc_to_gmst(mjd, times)
+    pairs = array.pairs
+    lam = C_LIGHT / float(rf)
+    H = (gmst - float(ra)) * (np.pi / 12.0)                                # Greenwich hour angle of the source
+    d = np.deg2rad(float(dec))
+    B = array.xyz[pairs[:, 1]] - array.xyz[pairs[:, 0]]                    # earth-fixed baseline vectors (m)
+    sH, cH = np.sin(H)[:, None], np.cos(H)[:, None]
+    u = (sH * B[None, :, 0] + cH * B[None, :, 1]) / lam
+    v = (-np.sin(d) * cH * B[None, :, 0] + np.sin(d) * sH * B[None, :, 1] + np.cos(d) * B[None, :, 2]) / lam
+    # the source direction in the earth-fixed frame (hour angle H west of Greenwich) against each station's geocentric direction
+    s = np.stack([np.cos(d) * np.cos(-H), np.cos(d) * np.sin(-H), np.full_like(H, np.sin(d))], axis=-1)
+    rhat = array.xyz / np.linalg.norm(array.xyz, axis=1, keepdims=True)
+    elevation = np.arcsin(np.clip(s @ rhat.T, -1.0, 1.0))
+    site_up = (elevation > np.deg2rad(elev_min)) & (elevation < np.deg2rad(elev_max))
+    up = site_up[:, pairs[:, 0]] & site_up[:, pairs[:, 1]]
+    sigma = np.sqrt(array.sefd[pairs[:, 0]] * array.sefd[pairs[:, 1]] / (2.0 * float(bw) * float(tint))) / QUANT_EFFICIENCY
+    return Observation(array, times, gmst, pairs, np.stack([u, v], axis=-1), up, np.broadcast_to(sigma, up.shape).copy(), elevation,
+                       ra=float(ra), dec=float(dec), rf=float(rf), bw=float(bw), tint=float(tint), mjd=mjd, timetype=timetype)
+
+
+class Observation(object):
+    """What ``empty_eht_obs`` returns -- ``array``, ``times`` (nt,) hours, ``gmst`` (nt,) hours, ``pairs`` (nvis, 2), ``uv``
+    (nt, nvis, 2) float64 wavelengths, ``up`` (nt, nvis) bool, ``sigma`` (nt, nvis) Jy, ``elevation`` (nt, nsites) radians and the
+    scalars ``ra`` (hours), ``dec`` (degrees), ``rf``, ``bw``, ``tint`` -- and the way from complex visibilities to the targets,
+    sigmas and closure tables the operators of this module take (``data``).  Every baseline is kept in every frame; one that is
+    not ``up`` carries no weight.  Parity with ehtim's scan bookkeeping is not pinned (``empty_eht_obs``)."""
+
+    def __init__(self, array, times, gmst, pairs, uv, up, sigma, elevation, ra, dec, rf, bw, tint, mjd=None, timetype='GMST'):
+        self.array, self.times, self.gmst, self.pairs = array, times, gmst, pairs
+        self.uv = np.ascontiguousarray(uv, dtype=np.float64)
+        self.up, self.sigma, self.elevation = np.asarray(up, dtype=bool), np.asarray(sigma, dtype=np.float64), elevation
+        self.ra, self.dec, self.rf, self.bw, self.tint, self.mjd, self.timetype = ra, dec, rf, bw, tint, mjd, timetype
+        self._min_quads = {}                                   # up stations -> the independent quadrangles of count='min'
+
+    @property
+    def nt(self):
+        return int(self.uv.shape[0])
+
+    @property
+    def nvis(self):
+        return int(self.uv.shape[1])
+
+    def dft(self, fov, npix):
+        """The ``DirectDFT`` of ``uv`` for images of ``npix`` pixels over ``fov`` radians."""
+        return DirectDFT(self.uv, fov, npix)
+
+    def _per_baseline(self, vis, what):
+        """``what`` (nt, nvis) shaped to broadcast against vis (nt, [S,] nvis)."""
+        if vis.ndim not in (2, 3) or vis.shape[0] != self.nt or vis.shape[-1] != self.nvis:
+            raise AttributeError('vis should have the shape ({}, [S,] {}), got {}'.format(self.nt, self.nvis, vis.shape))
+        return what if vis.ndim == 2 else what[:, None, :]
+
+    def add_thermal_noise(self, vis, seed=None):
+        """vis (nt, [S,] nvis) plus complex Gaussian noise of ``sigma`` per real and imaginary part, 0 where the baseline is not
+        up; complex64.  One call ``np.random.default_rng(seed).standard_normal(vis.shape + (2,))``: [..., 0] the real parts,
+        [..., 1] the imaginary ones.  A host function."""
+        vis = np.asarray(vis)
+        sigma, up = self._per_baseline(vis, self.sigma), self._per_baseline(vis, self.up)
+        n = np.random.default_rng(seed).standard_normal(vis.shape + (2,))
+        noisy = vis.astype(np.complex128) + sigma * (n[..., 0] + 1j * n[..., 1])
+        return np.where(up, noisy, 0.0).astype(np.complex64)
+
+    # -- closure sets
+    def _stations_up(self, f):
+        return tuple(sorted(set(self.pairs[self.up[f]].ravel().tolist())))
+
+    def _frame_triangles(self, stations, count):
+        if count == 'max':
+            return [(a, b, c) for i, a in enumerate(stations) for j, b in enumerate(stations[i + 1:], i + 1) for c in stations[j + 1:]]
+        ref = min(stations, key=lambda s: (self.array.sefd[s], s))          # lowest SEFD, ties by lowest index
+        rest = [s for s in stations if s != ref]
+        return [tuple(sorted((ref, a, b))) for i, a in enumerate(rest) for b in rest[i + 1:]]
+
+    def _frame_quadrangles(self, stations, count):
+        m = len(stations)
+        if m < 4:
+            return []
+        st = np.asarray(stations)
+        cand = [tuple(map(tuple, q)) for q in st[closure_quadrangles(m)].tolist()]
+        if count == 'max':
+            return cand
+        if stations not in self._min_quads:
+            # a greedy pass over the candidates keeps each one that raises the rank of the +-1 design matrix over the baselines,
+            # until the m (m - 3) / 2 independent log closure amplitudes are found.  `basis` is kept in reduced row echelon form.
+            col = {p: i for i, p in enumerate((a, b) for i, a in enumerate(stations) for b in stations[i + 1:])}
+            need, keep = m * (m - 3) // 2, []
+            basis, pivots = np.zeros((need, len(col))), []
+            for q in cand:
+                row = np.zeros(len(col))
+                for leg, p in enumerate(q):
+                    row[col[p]] += 1.0 if leg < 2 else -1.0
+                r = len(keep)
+                row -= row[pivots] @ basis[:r]
+                p = int(np.argmax(np.abs(row)))
+                if abs(row[p]) < 1e-9:
+                    continue
+                row /= row[p]
+                basis[:r] -= np.outer(basis[:r, p], row)
+                basis[r] = row
+                pivots.append(p)
+                keep.append(q)
+                if len(keep) == need:
+                    break
+            self._min_quads[stations] = keep
+        return self._min_quads[stations]
+
+    def closure_sets(self, count='min', triangles=True, quadrangles=True):
+        """The global closure tables of all frames and who is observed when: (triangles, tri_obs, quadrangles, quad_obs) --
+        station triples (a < b < c), (nt, ntri) bool, quadrangles of station pairs in the form of ``closure_quadrangles`` and
+        (nt, nquad) bool; the tables are the sorted union of the frames' sets (None, None where not asked for).
+
+        count='max': per frame every triangle whose three baselines are up and both forms of every quadruple whose baselines are
+        up.  count='min': per frame an independent set -- the (m - 1)(m - 2) / 2 triangles through the up station of lowest SEFD
+        (ties: lowest index) and m (m - 3) / 2 quadrangles of full rank picked from the same two forms in a fixed order."""
+        if count not in ('min', 'max'):
+            raise AttributeError("count ({}) should be 'min' or 'max'".format(count))
+        index = {tuple(p): i for i, p in enumerate(self.pairs.tolist())}
+        stations = [self._stations_up(f) for f in range(self.nt)]
+        tri_legs = lambda t: ((t[0], t[1]), (t[1], t[2]), (t[0], t[2]))
+        out = []
+        for want, per_frame, legs in ((triangles, self._frame_triangles, tri_legs), (quadrangles, self._frame_quadrangles, lambda q: q)):
+            if not want:
+                out += [None, None]
+                continue
+            of_stations = {st: per_frame(st, count) if st else [] for st in set(stations)}
+            sets = [{t for t in of_stations[st] if all(self.up[f, index[p]] for p in legs(t))} for f, st in enumerate(stations)]
+            table = sorted(set().union(*sets))
+            out += [table, np.array([[t in s for t in table] for s in sets], dtype=bool).reshape(self.nt, len(table))]
+        return tuple(out)
+
+    def data(self, vis, dtype, count='min', debias=True):
+        """Targets, sigmas and closure tables of complex visibilities ``vis`` (nt, [S,] nvis) as the operators take them: a dict
+        term -> (target, sigma) for every term of ``dtype`` ('vis', or 'amp', 'cphase', 'logcamp' and their '+'-joined sets in
+        that order), plus 'triangles' and 'quadrangles' (station tuples, one table for all frames; None when no term needs it).
+
+        'vis': (vis, sigma).  'amp': sqrt(max(|V|^2 - sigma^2, 0)) with ``debias`` else |V|, sigma.  'cphase': the closure phase
+        of vis (radians, ``ClosureDFT.closure_phases``) with sqrt(sum_legs (sigma_l / |V_l|)^2).  'logcamp':
+        ``ClosureDFT.log_closure_amplitudes`` of the amplitudes (debiased with ``debias``) with sqrt(sum_legs (sigma_l / |V_l|)^2)
+        over the four legs, |V_l| the same amplitudes.  ``count``: the closure sets (``closure_sets``).
+
+        A baseline, triangle or quadrangle that a frame does not observe -- and one with a leg of zero amplitude -- gets the
+        target 0 and the sigma +inf: every term of the losses divides by sigma, so it adds exactly 0 to the loss and to the
+        gradient.  AttributeError when no frame observes a triangle / quadrangle that ``dtype`` needs."""
+        terms = tuple(str(dtype).split('+'))
+        if terms != ('vis',) and (terms != tuple(t for t in CLOSURE_TERMS if t in terms) or len(set(terms)) != len(terms)):
+            raise AttributeError("dtype ({}) should be 'vis' or a '+'-joined set of {} in that order".format(dtype, CLOSURE_TERMS))
+        vis = np.asarray(vis).astype(np.complex128)
+        up, sigma = self._per_baseline(vis, self.up), self._per_baseline(vis, self.sigma)
+        up, sigma = np.broadcast_to(up, vis.shape), np.broadcast_to(sigma, vis.shape)
+        out = {'triangles': None, 'quadrangles': None}
+        s_base = np.where(up, sigma, np.inf)
+        amp = np.abs(vis)
+        amp_db = np.sqrt(np.maximum(amp ** 2 - sigma ** 2, 0.0)) if debias else amp
+        if 'vis' in terms:
+            out['vis'] = (np.where(up, vis, 0.0).astype(np.complex64), s_base)
+        if 'amp' in terms:
+            out['amp'] = (np.where(up, amp_db, 0.0), s_base)
+        if 'cphase' in terms or 'logcamp' in terms:
+            tris, tri_obs, quads, quad_obs = self.closure_sets(count, 'cphase' in terms, 'logcamp' in terms)
+            for name, table in (('cphase', tris), ('logcamp', quads)):
+                if name in terms and not table:
+                    raise AttributeError("dtype='{}': no frame observes a {}".format(name, 'triangle' if name == 'cphase' else 'quadrangle'))
+            op = ClosureDFT(self.uv, 1.0, 1, pairs=self.pairs, triangles=tris, quadrangles=quads)       # (only its tables are used)
+            shaped = lambda obs: obs if vis.ndim == 2 else obs[:, None, :]
+            with np.errstate(divide='ignore', invalid='ignore'):
+                if 'cphase' in terms:
+                    snr2 = (sigma / amp) ** 2
+                    sig = np.sqrt(sum(snr2[..., op.tri[:, leg]] for leg in range(3)))
+                    ok = shaped(tri_obs) & np.isfinite(sig)
+                    out['cphase'] = (np.where(ok, op.closure_phases(vis), 0.0), np.where(ok, sig, np.inf))
+                    out['triangles'] = tris
+                if 'logcamp' in terms:
+                    snr2 = (sigma / amp_db) ** 2
+                    sig = np.sqrt(sum(snr2[..., op.quad[:, leg]] for leg in range(4)))
+                    ok = shaped(quad_obs) & np.isfinite(sig)
+                    out['logcamp'] = (np.where(ok, op.log_closure_amplitudes(amp_db), 0.0), np.where(ok, sig, np.inf))
+                    out['quadrangles'] = quads
+        return out
+
+
+def observe_same(movie, obs, fov, thermal_noise=True, seed=None, device=None):
+    """Synthetic visibilities of ``movie`` (nt, [S,] H, W), one frame per scan of ``obs`` (an ``Observation``), over ``fov`` radians:
+    the clean visibilities from ``DirectDFT.observe`` on the device (``HipError`` without one), plus ``obs.add_thermal_noise`` with
+    ``thermal_noise``; 0 where the baseline is not up.  Returns complex64 NumPy (nt, [S,] nvis).  The reference hands the movie
+    to ehtim, which also corrupts with station gains and D-terms: those are out of scope here -- the closure terms are what this
+    package offers against gains."""
+    movie = np.asarray(movie) if not hasattr(movie, 'detach') else movie
+    vis = obs.dft(fov, tuple(movie.shape[-2:])).observe(movie, device=device).cpu().numpy()
+    if thermal_noise:
+        return obs.add_thermal_noise(vis, seed)
+    return np.where(obs._per_baseline(vis, obs.up), vis, 0.0).astype(np.complex64)

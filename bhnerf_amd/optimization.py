@@ -502,6 +502,26 @@ class TrainStep(object):
         return cls('+'.join(terms), args, network.gradient_step_eht, network.test_eht, scale)
 
     @classmethod
+    def eht_obs(cls, t_frames, obs, vis, image_fov, image_size, dtype='vis', scale=1.0, count='min', weights=None, debias=True):
+        """Training step on an ``observation.Observation`` (``observation.empty_eht_obs``) and its complex visibilities ``vis``
+        (nt, [S,] nvis) (``observation.observe_same``, or measured ones in the observation's baseline order) -- what
+        ``TrainStep.eht`` does with ehtim, with this package only.  ``image_fov`` in radians, ``image_size`` an int or (H, W).
+        ``dtype``: 'vis', 'amp' or 'cphase' alone run through ``TrainStep.eht_uv``; 'logcamp' and '+'-joined sets such as
+        'cphase+logcamp' through ``TrainStep.eht_closure`` (``weights`` belong to those).  ``count`` and ``debias``: the closure
+        sets and the amplitude debiasing of ``Observation.data``.  Stokes planes share ``uv``.  Baselines and closure quantities
+        that a frame does not observe carry sigma = +inf: no loss, no gradient."""
+        data = obs.data(vis, dtype, count=count, debias=debias)
+        if dtype in ('vis', 'amp', 'cphase'):
+            if weights is not None:
+                raise AttributeError("weights belong to 'logcamp' and '+'-joined dtypes; a single '{}' takes scale".format(dtype))
+            target, sigma = data[dtype]
+            return cls.eht_uv(t_frames, target, sigma, obs.uv, image_fov, image_size, dtype=dtype, scale=scale,
+                              triangles=data['triangles'], pairs=obs.pairs if dtype == 'cphase' else None)
+        terms = dtype.split('+')
+        return cls.eht_closure(t_frames, obs.uv, image_fov, image_size, obs.pairs, {t: data[t] for t in terms}, weights=weights,
+                               scale=scale, triangles=data['triangles'], quadrangles=data['quadrangles'])
+
+    @classmethod
     def eht(cls, t_frames, obs, image_fov, image_size, chisqdata, pol='I', scale=1.0):
         """Training step for an ehtim observation (optimization.py:219-268); needs the external ehtim
         package to split the observation per frame and build (target, sigma, A)."""

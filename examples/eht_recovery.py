@@ -1,0 +1,105 @@
+"""Recovery of 3-D emission from EHT observations end to end on one MI355X (the flow of the reference's Tutorial 4, with its
+Tutorial 2 inside), with nothing but this package -- no ehtim, no astropy:
+
+  Kerr geodesics (own tracer)  ->  a Gaussian hotspot on a Keplerian orbit  ->  image_plane_dynamics: the 'true' movie  ->
+  empty_eht_obs: the (u, v) tracks, elevations and thermal noise of a station table (ngEHT, GMST 2 h + 40 min, 64 frames)  ->
+  observe_same: noisy complex visibilities  ->  TrainStep.eht_obs on 'vis', 'amp', 'cphase', 'logcamp' or a '+'-joined set  ->
+  Optimizer.run  ->  the 3-D emission sampled back.
+
+    python examples/eht_recovery.py [--dtype vis] [--array ngEHT] [--size 32] [--iters 1000] [--render out] [--tracer hip]
+
+--array names a table under tests/golden/eht_arrays/ (ngEHT, EHT2017) or is the path of one in the same text format.
+--render PATH also renders the recovered volume through visualization.VolumeVisualizer and saves PATH.npy (PATH.png with
+matplotlib).  What is and is not ehtim here: see observation.empty_eht_obs and INTEGRATION.md.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bhnerf_amd as bhnerf  # noqa: E402
+from bhnerf_amd import constants, kgeo, network, observation, optimization, units  # noqa: E402
+
+# GM / c^2 of Sgr A* over its distance (26673 light years), in radians: 5.0 micro-arcseconds
+RAD_PER_M = constants.GM_c3('s') * 299792458.0 / (26673 * 9.4607304725808e15)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--dtype', default='vis', help="'vis', 'amp', 'cphase', 'logcamp' or a '+'-joined set such as 'cphase+logcamp'")
+    ap.add_argument('--array', default='ngEHT', help='a table under tests/golden/eht_arrays/ or the path of one')
+    ap.add_argument('--size', type=int, default=32, help='image is size x size pixels')
+    ap.add_argument('--iters', type=int, default=1000)
+    ap.add_argument('--render', metavar='PATH', default=None, help='render the recovered volume to PATH.npy (and PATH.png with matplotlib)')
+    ap.add_argument('--ngeo', type=int, default=64)
+    ap.add_argument('--frames', type=int, default=64)
+    ap.add_argument('--width', type=int, default=128)
+    ap.add_argument('--mode', default='bf16', choices=['bf16', 'f32'], help='arithmetic of the fused kernels')
+    ap.add_argument('--batch', type=int, default=6, help='frames per step')
+    ap.add_argument('--count', default='min', choices=['min', 'max'], help='closure sets per frame: an independent set or all')
+    ap.add_argument('--seed', type=int, default=0, help='seed of the thermal noise')
+    ap.add_argument('--tracer', default='numpy', choices=['numpy', 'hip'], help='where the geodesics are integrated: on the host or on the GPU')
+    args = ap.parse_args()
+    import torch
+
+    fov_M, spin, inclination, nt = 16.0, 0.2, np.deg2rad(60.0), args.frames
+    flux_scale = 0.1                                            # image-plane fluxes of a `reasonable` size in Jy
+    tstart = 2.0                                                # GMST hours
+    tstop = tstart + 40.0 / 60.0
+    rmax, z_width = fov_M / 2, 4.0
+
+    geos = kgeo.image_plane_geos(spin, inclination, (-fov_M / 2, fov_M / 2), (-fov_M / 2, fov_M / 2), ngeo=args.ngeo,
+                                 num_alpha=args.size, num_beta=args.size, backend=args.tracer)
+    Omega = np.sign(spin + np.finfo(float).eps) / (np.asarray(geos.r) ** 1.5 + spin)           # Keplerian, prograde (M = 1)
+    geos['g'] = kgeo.doppler_factor(geos, kgeo.azimuthal_velocity_vector(geos, Omega))
+    t_injection = -float(geos.r_o)
+    emission_0 = flux_scale * np.asarray(bhnerf.emission.generate_hotspot_xr(
+        resolution=(64, 64, 64), rot_axis=[0.0, 0.0, 1.0], rot_angle=0.0, orbit_radius=5.5, std=0.7, r_isco=constants.isco_pro(spin),
+        fov=(fov_M, 'GM/c^2')).data)
+    t_frames = np.linspace(tstart, tstop, nt) * units.hr
+    movie = bhnerf.emission.image_plane_dynamics((emission_0, fov_M), geos, Omega, t_frames, t_injection, J=1.0, doppler=True)
+
+    # Tutorial 2: the empty observation of the station table and the synthetic data.  The scans sit at the movie's frame times.
+    path = args.array if os.path.exists(args.array) else os.path.join(ROOT, 'tests', 'golden', 'eht_arrays', args.array + '.txt')
+    obs_params = {'mjd': 57851, 'timetype': 'GMST', 'nt': nt, 'tstart': tstart, 'tstop': tstop, 'tint': 30.0,
+                  'array': observation.Array.load_txt(path)}
+    obs = observation.empty_eht_obs(times=np.linspace(tstart, tstop, nt), **obs_params)
+    fov_rad = fov_M * RAD_PER_M
+    vis = observation.observe_same(movie, obs, fov_rad, thermal_noise=True, seed=args.seed)
+    up = obs.up[0].sum()
+    snr = np.abs(vis[obs.up]) / obs.sigma[obs.up]
+    print('%s: %d stations, %d of %d baselines up in frame 0, |uv| up to %.1f Glambda; movie %s of %.3g .. %.3g Jy, median SNR %.0f'
+          % (os.path.basename(path), len(obs.array), up, obs.nvis, np.sqrt((obs.uv[obs.up] ** 2).sum(-1)).max() / 1e9, movie.shape,
+             movie.sum((-1, -2)).min(), movie.sum((-1, -2)).max(), np.median(snr)))
+
+    # Tutorial 4: the training step on the observation, the optimisation and the recovered volume
+    train_step = optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype=args.dtype, count=args.count)
+    rmin = float(np.asarray(geos.r).min())
+    predictor = network.NeRF_Predictor(rmax, rmin, rmax, z_width, net_depth=4, net_width=args.width, mode=args.mode)
+    rt = network.raytracing_args(geos, Omega, t_injection, t_frames[0], J=1.0)
+    opt = optimization.Optimizer({'num_iters': args.iters, 'lr_init': 1e-3, 'lr_final': 1e-4}, predictor, rt)
+    first = optimization.total_movie_loss(args.batch, opt.state, train_step, rt)
+    t0 = time.perf_counter()
+    opt.run(args.batch, train_step, rt, log_fns=[optimization.LogFn(
+        lambda o: print('iter %5d  chi2/frame %.4g' % (o.step, float(np.mean(o.loss)))), max(50, args.iters // 10))])
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    last = optimization.total_movie_loss(args.batch, opt.state, train_step, rt)
+    print("'%s' chi2 per frame %.4g -> %.4g   (%d iterations in %.1f s = %.2f ms/iteration)" % (args.dtype, first, last, args.iters, dt, 1e3 * dt / args.iters))
+    n = 64
+    ax = np.linspace(-rmax, rmax, n)
+    vol = network.sample_3d_grid(predictor.apply, opt.state.params, fov=fov_M, resolution=n)
+    i = np.unravel_index(np.argmax(vol), vol.shape)
+    print('recovered emission peaks at (x, y, z) = (%.1f, %.1f, %.1f) M; truth (5.5, 0.0, 0.0) at the first frame' % (ax[i[0]], ax[i[1]], ax[i[2]]))
+    if args.render:
+        from image_plane_recovery import render_volume
+        render_volume(args.render, predictor, opt.state.params, rmax)
+
+
+if __name__ == '__main__':
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    main()

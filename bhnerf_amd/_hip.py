@@ -1,6 +1,7 @@
 """ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
 (include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h), libbhnerf_eql.so (include/bhnerf_eql.h), libbhnerf_flow.so
-(include/bhnerf_flow.h), libbhnerf_rec.so (include/bhnerf_rec.h) and libbhnerf_cls.so (include/bhnerf_cls.h).
+(include/bhnerf_flow.h), libbhnerf_rec.so (include/bhnerf_rec.h), libbhnerf_cls.so (include/bhnerf_cls.h) and libbhnerf_pol.so
+(include/bhnerf_pol.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -199,6 +200,22 @@ CLS_SIGNATURES = {
     'bhn_cls_chi2': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _D, _D, _CT, _CT, _CT, _P, _P, _I32, _P, _I32, _F, _P, _P, _P, _SZ, _P]),
 }
 CLS_LIBRARY = (CLS_LIB_PATH, CLS_SIGNATURES, 'bhn_cls_last_error', None)
+
+# libbhnerf_pol.so (include/bhnerf_pol.h): the polarimetric EHT losses 'pvis' and 'm' from (u, v), the ninth library
+POL_LIB_PATH = os.path.join(CSRC, 'libbhnerf_pol.so')
+
+
+class bhn_pol_term(C.Structure):
+    _fields_ = [('target', C.c_void_p), ('sigma', C.c_void_p), ('weight', C.c_double)]
+
+
+_PT = C.POINTER(bhn_pol_term)
+POL_SIGNATURES = {
+    'bhn_pol_last_error': (C.c_char_p, []),
+    'bhn_pol_ws_bytes': (_SZ, [_I32, _I32, _I32, _I32]),
+    'bhn_pol_chi2': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _D, _D, _PT, _PT, _F, _P, _P, _P, _SZ, _P]),
+}
+POL_LIBRARY = (POL_LIB_PATH, POL_SIGNATURES, 'bhn_pol_last_error', None)
 _loaded = {}                 # path -> handle
 
 
@@ -209,7 +226,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec', 'libbhnerf_cls']), CSRC))
+        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec', 'libbhnerf_cls', 'libbhnerf_pol']), CSRC))
     return LIB_PATH
 
 
@@ -288,6 +305,11 @@ def cls_lib():
     return _lib('libbhnerf_cls', CLS_LIBRARY)
 
 
+def pol_lib():
+    """The loaded polarimetric-loss library."""
+    return _lib('libbhnerf_pol', POL_LIBRARY)
+
+
 def check(rc):
     _check('libbhnerf_hip', rc)
 
@@ -318,6 +340,10 @@ def rec_check(rc):
 
 def cls_check(rc):
     _check('libbhnerf_cls', rc, CLS_LIBRARY)
+
+
+def pol_check(rc):
+    _check('libbhnerf_pol', rc, POL_LIBRARY)
 
 
 def stream_ptr(device=None):

@@ -640,8 +640,75 @@ def chi2_closure_uv(images, op, target, sigma, scale, dtype, want_grad=True):
     return loss[:1], (dimg.reshape(images.shape) if want_grad else None)
 
 
+def pol_terms(dtype):
+    """The terms of a polarimetric dtype: 'pvis', 'm' or 'pvis+m' (the canonical order, each at most once) -> a tuple of names;
+    None for anything else."""
+    if not isinstance(dtype, str):
+        return None
+    terms = tuple(dtype.split('+'))
+    if terms and terms == tuple(t for t in observation.POL_TERMS if t in terms) and len(set(terms)) == len(terms):
+        return terms
+    return None
+
+
+def chi2_eht_pol(images, op, target, sigma, scale, dtype, want_grad=True):
+    """scale * sum_d w_d chi^2_d over the terms of `dtype` (pol_terms) from an observation.PolDFT: the polarised visibility
+    P = Q + iU ('pvis') and the fractional polarisation P / I ('m') of every frame and baseline, ONE visibility pass over the
+    Sx = 3 or 4 Stokes planes of `images` (B, Sx, H W) and one image gradient (bhn_pol_chi2).  `target` complex (B, nterm) and
+    `sigma` real (B, nterm): one entry per frame and baseline, the terms' arrays concatenated along the last axis in the canonical
+    order (PolDFT.pack).  Returns (loss[1], dimages or None); the three floats {total, pvis, m} stay on the device as
+    ``op.last_terms``.  AttributeError for every shape mismatch, before any launch."""
+    terms = pol_terms(dtype)
+    if terms is None:
+        raise AttributeError('eht dtype ({}) not supported'.format(dtype))
+    nvis, nterm = op.nvis, op.nvis * len(terms)
+    if target.ndim != 2 or int(target.shape[-1]) != nterm:
+        raise AttributeError('target {} should be (frames, {}) ({}) for dtype={}'.format(
+            tuple(target.shape), nterm, ' + '.join('{} {}'.format(nvis, t) for t in terms), dtype))
+    B = int(target.shape[0])
+    if images.ndim < 2 or int(images.shape[0]) != B or int(images.numel()) % (B * op.H * op.W) != 0:
+        raise AttributeError('images {} are not {} frames of Stokes planes of {} x {} pixels'.format(tuple(images.shape), B, op.H, op.W))
+    Sx = int(images.numel()) // (B * op.H * op.W)
+    if Sx not in (3, 4):
+        raise AttributeError("dtype='{}' couples the Stokes planes I, Q, U[, V] of a frame: images of 3 or 4 planes, got {}".format(dtype, Sx))
+    N = B * Sx
+    img, op_dev, _ = _eht_uv_operands(images, op, N)
+    if B != int(op_dev.uv.shape[0]):
+        raise AttributeError('target of {} frames, uv of {}'.format(B, int(op_dev.uv.shape[0])))
+    dev, lib = img.device, _hip.pol_lib()
+    tgt = _eht_uv_array(target, dev, torch.complex64, None)
+    sig = _eht_uv_array(sigma, dev, torch.float32, (B, nterm))
+    structs, keep = {}, []
+    for i, t in enumerate(terms):                            # a term's columns as an array of its own: what the library takes
+        tt, ss = tgt[:, i * nvis:(i + 1) * nvis], sig[:, i * nvis:(i + 1) * nvis]
+        if len(terms) > 1:
+            tt, ss = tt.contiguous(), ss.contiguous()
+        keep += [tt, ss]
+        structs[t] = _hip.bhn_pol_term(tt.data_ptr(), ss.data_ptr(), float(op.weights[t]))
+    key = (N, nvis, op.H, op.W)
+    nbytes = _POL_WS_BYTES.get(key)
+    if nbytes is None:
+        nbytes = _POL_WS_BYTES[key] = int(lib.bhn_pol_ws_bytes(*key))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((3,), dtype=torch.float32, device=dev)
+    dimg = torch.empty_like(img) if want_grad else None
+    psy, psx = op.psize
+    ref = lambda t: C.byref(structs[t]) if t in structs else None
+    args = (img.data_ptr(), op_dev.uv.data_ptr(), N, Sx, nvis, op.H, op.W, psx, psy, ref('pvis'), ref('m'), float(scale), loss.data_ptr(),
+            dimg.data_ptr() if want_grad else None, ws.data_ptr(), nbytes, _hip.stream_ptr(dev))
+    if dev.index is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            rc = lib.bhn_pol_chi2(*args)
+    else:
+        rc = lib.bhn_pol_chi2(*args)
+    _hip.pol_check(rc)
+    op.last_terms = loss
+    return loss[:1], (dimg.reshape(images.shape) if want_grad else None)
+
+
 _CLS_WS_BYTES = {}
-_TABLE_RANGE = {}                 # id of a checked table -> (the table, what lies outside [0, nvis) or None)
+_POL_WS_BYTES = {}
+_TABLE_RANGE = {}               # id of a checked table -> (the table, what lies outside [0, nvis) or None)
 
 
 def _table_range(op, name, table):
@@ -670,7 +737,10 @@ def _eht_uv_array(x, dev, dtype, shape):
 def chi2_eht(images, A, target, sigma, scale, dtype, want_grad=True):
     """loss_fn_eht tail (network.py:541-564) on device -> (loss[1], dimages shaped like images or None).  ``A``: the dense DFT
     matrices, an ``observation.DirectDFT`` (the matrix-free path, chi2_eht_uv) or an ``observation.ClosureDFT`` (one weighted sum
-    of real-valued terms from one visibility pass, chi2_closure_uv)."""
+    of real-valued terms from one visibility pass, chi2_closure_uv) or an ``observation.PolDFT`` (the polarimetric terms that couple
+    the Stokes planes of a frame, chi2_eht_pol)."""
+    if isinstance(A, observation.PolDFT):
+        return chi2_eht_pol(images, A, target, sigma, scale, dtype, want_grad=want_grad)
     if isinstance(A, observation.ClosureDFT):
         return chi2_closure_uv(images, A, target, sigma, scale, dtype, want_grad=want_grad)
     if isinstance(A, observation.DirectDFT):

@@ -451,7 +451,7 @@ def loss_fn_eht(params, predictor_fn, target, sigma, A, t_frames, coords, Omega,
     the DFT matrices per frame: (b, nvis, H*W) ('vis'/'amp') or (b, 3, nvis, H*W) ('cphase')."""
     images = image_plane_prediction(params, predictor_fn, t_frames, coords, Omega, J, g, dtau, Sigma, t_start_obs,
                                     t_geos, t_injection, t_units)
-    if dtype not in engine.EHT_DTYPES and not _closure_dtype(dtype, A):
+    if dtype not in engine.EHT_DTYPES and not _closure_dtype(dtype, A) and not _pol_dtype(dtype, A):
         raise AttributeError('eht dtype ({}) not supported'.format(dtype))
     loss = engine.EhtChi2Function.apply(images.reshape(tuple(images.shape[:-2]) + (-1,)), A, target, sigma, scale, dtype)
     return loss, [images]
@@ -460,6 +460,11 @@ def loss_fn_eht(params, predictor_fn, target, sigma, A, t_frames, coords, Omega,
 def _closure_dtype(dtype, A):
     """A combined closure dtype ('cphase+logcamp', ...: engine.closure_terms) on the operator that carries its tables."""
     return isinstance(A, observation.ClosureDFT) and engine.closure_terms(dtype) is not None
+
+
+def _pol_dtype(dtype, A):
+    """A polarimetric dtype ('pvis', 'm', 'pvis+m': engine.pol_terms) on the operator that couples the Stokes planes."""
+    return isinstance(A, observation.PolDFT) and engine.pol_terms(dtype) is not None
 
 
 def _fill_loss_slots(buf, n, loss, rank):
@@ -519,7 +524,7 @@ def _step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, 
     """Per-process body of gradient_step_image/_eht and test_image/_eht with no torch.autograd in the
     loop: pack -> `_pass` (fused render -> chi^2 kernel -> fused backward) -> all-reduce -> Adam.  For the EHT
     losses ``offset`` carries the DFT matrices A."""
-    if dtype not in (engine.EHT_DTYPES if eht else ('full', 'lc')) and not (eht and _closure_dtype(dtype, offset)):
+    if dtype not in (engine.EHT_DTYPES if eht else ('full', 'lc')) and not (eht and (_closure_dtype(dtype, offset) or _pol_dtype(dtype, offset))):
         raise AttributeError('{} dtype ({}) not supported'.format('eht' if eht else 'image', dtype))
     pred = state.predictor
     eng = pred.engine()

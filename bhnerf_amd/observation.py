@@ -6,7 +6,9 @@ its sign/ordering conventions (parity unpinned: SURVEY 8c iii).
 
 ``DirectDFT`` is the same operator kept as its (u, v) coordinates: the losses then run matrix-free (libbhnerf_eht.so).
 ``ClosureDFT`` is a ``DirectDFT`` with the closure tables (triangles, quadrangles) and weights of one combined objective over
-'amp', 'cphase' and 'logcamp', the log closure amplitude (libbhnerf_cls.so).
+'amp', 'cphase' and 'logcamp', the log closure amplitude (libbhnerf_cls.so).  ``PolDFT`` is a ``DirectDFT`` for the polarimetric
+terms that couple the Stokes planes of a frame: 'pvis', P = Q + iU, and 'm', the visibility-domain fractional polarisation P / I
+(libbhnerf_pol.so).
 
 ``Array``, ``empty_eht_obs``, ``observe_same`` and ``Observation`` lead from a station table to those operators: baseline
 coordinates, elevations, thermal noise, synthetic visibilities and the targets, sigmas and closure tables of a station set that
@@ -325,6 +327,91 @@ class ClosureDFT(DirectDFT):
         return out
 
 
+POL_TERMS = ('pvis', 'm')                           # the canonical order of the polarimetric terms
+
+
+class PolDFT(DirectDFT):
+    """A ``DirectDFT`` for ONE weighted objective over the polarimetric terms 'pvis' and 'm' (libbhnerf_pol.so), which couple the
+    Stokes planes I, Q, U[, V] of a frame: with P = Q~ + i U~ per frame and baseline,
+
+    'pvis': |P - target|^2 / sigma^2, the calibrated polarised visibility; 'm': |P / I~ - target|^2 / sigma^2, the fractional
+    polarisation in the visibility domain.  A complex station gain G_a conj(G_b) common to the Stokes planes of a baseline
+    multiplies P and I~ alike, so 'm' does not see it: the polarimetric counterpart of the closure quantities.
+
+    ``weights``: {'pvis' | 'm': w_d >= 0}, 1.0 where not given.  Targets are complex (nt, nvis), sigmas real (nt, nvis) -- one per
+    frame and baseline, not per plane; the data of 'pvis+m' are the terms' arrays concatenated along the last axis in the
+    canonical order (``pack``).  ``observe`` is ``DirectDFT``'s."""
+
+    def __init__(self, uv, fov, npix, weights=None):
+        DirectDFT.__init__(self, uv, fov, npix)
+        self.weights = self._weights(weights)
+
+    @staticmethod
+    def _weights(weights):
+        weights = dict(weights or {})
+        unknown = sorted(set(weights) - set(POL_TERMS))
+        if unknown:
+            raise AttributeError('weights name unknown terms {} (known: {})'.format(unknown, ', '.join(POL_TERMS)))
+        out = {k: float(weights.get(k, 1.0)) for k in POL_TERMS}
+        if not all(np.isfinite(w) and w >= 0 for w in out.values()):
+            raise AttributeError('weights must be finite and >= 0, got {}'.format(out))
+        return out
+
+    def _like(self, uv, tri=None, tri_sign=None):
+        out = object.__new__(type(self))
+        out.uv, out.H, out.W, out.fov = uv, self.H, self.W, self.fov
+        out.tri = out.tri_sign = None
+        out.weights = dict(self.weights)
+        return out
+
+    @staticmethod
+    def _planes(vis):
+        vis = np.asarray(vis, dtype=np.complex128)
+        if vis.ndim < 2 or vis.shape[-2] < 3:
+            raise AttributeError('polarimetric quantities need visibilities (..., S >= 3, nvis) of the planes I, Q, U; got {}'.format(vis.shape))
+        return vis
+
+    def polarised_visibility(self, vis):
+        """complex128 P = Q~ + i U~ (..., nvis) of complex visibilities (..., S >= 3, nvis) of the planes I, Q, U[, V]."""
+        vis = self._planes(vis)
+        return vis[..., 1, :] + 1j * vis[..., 2, :]
+
+    def fractional_polarisation(self, vis):
+        """complex128 P / I~ (..., nvis) of complex visibilities (..., S >= 3, nvis); inf or NaN where I~ is zero."""
+        vis = self._planes(vis)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return (vis[..., 1, :] + 1j * vis[..., 2, :]) / vis[..., 0, :]
+
+    def pack(self, data):
+        """{'m': y, 'pvis': x} -> the arrays concatenated along the last axis in the canonical order (pvis, m; only the terms named)."""
+        unknown = sorted(set(data) - set(POL_TERMS))
+        if unknown or not data:
+            raise AttributeError('pack takes terms of {}, got {}'.format(POL_TERMS, sorted(data)))
+        parts = []
+        for name in POL_TERMS:
+            if name in data:
+                x = np.asarray(data[name])
+                if x.ndim < 1 or x.shape[-1] != self.nvis:
+                    raise AttributeError("term '{}' of shape {} does not end in the operator's {} baselines".format(name, x.shape, self.nvis))
+                parts.append(x)
+        return np.concatenate(parts, axis=-1)
+
+    def split(self, array, terms=None):
+        """The inverse of ``pack``: {term: its slice of the last axis}.  ``terms``: the names (any iterable, or a '+'-joined string);
+        None: both terms for a last axis of 2 nvis entries (one term alone has to be named: 'pvis' and 'm' have the same size)."""
+        n = int(array.shape[-1])
+        if terms is None:
+            if n != 2 * self.nvis:
+                raise AttributeError('a last axis of {} entries does not name its terms ({} baselines): pass terms'.format(n, self.nvis))
+            terms = POL_TERMS
+        elif isinstance(terms, str):
+            terms = terms.split('+')
+        terms = [t for t in POL_TERMS if t in set(terms)]
+        if not terms or len(terms) * self.nvis != n:
+            raise AttributeError('a last axis of {} entries is not the terms {} of {} baselines'.format(n, terms, self.nvis))
+        return {t: array[..., i * self.nvis:(i + 1) * self.nvis] for i, t in enumerate(terms)}
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # From a station table to what the operators above take: baseline coordinates, thermal noise and per-frame closure tables of an
 # earth-rotation synthesis (reference: observation.py:79-119 and 121-222 hand this to ehtim).  NumPy float64 on the host.
@@ -458,6 +545,10 @@ class Observation(object):
         """The ``DirectDFT`` of ``uv`` for images of ``npix`` pixels over ``fov`` radians."""
         return DirectDFT(self.uv, fov, npix)
 
+    def pol_dft(self, fov, npix, weights=None):
+        """The ``PolDFT`` of ``uv`` for images of ``npix`` pixels over ``fov`` radians."""
+        return PolDFT(self.uv, fov, npix, weights=weights)
+
     def _per_baseline(self, vis, what):
         """``what`` (nt, nvis) shaped to broadcast against vis (nt, [S,] nvis)."""
         if vis.ndim not in (2, 3) or vis.shape[0] != self.nt or vis.shape[-1] != self.nvis:
@@ -473,6 +564,16 @@ class Observation(object):
         n = np.random.default_rng(seed).standard_normal(vis.shape + (2,))
         noisy = vis.astype(np.complex128) + sigma * (n[..., 0] + 1j * n[..., 1])
         return np.where(up, noisy, 0.0).astype(np.complex64)
+
+    def apply_gains(self, vis, gains):
+        """vis[f, [s,] k] G[f, a_k] conj(G[f, b_k]) with (a_k, b_k) = ``pairs[k]``: complex station gains ``gains`` (nt, nsites)
+        (``station_gains``) on visibilities (nt, [S,] nvis), the same on every Stokes plane; complex128.  A host function."""
+        vis = np.asarray(vis).astype(np.complex128)
+        gains = np.asarray(gains, dtype=np.complex128)
+        if gains.shape != (self.nt, len(self.array)):
+            raise AttributeError('gains should have the shape ({}, {}), got {}'.format(self.nt, len(self.array), gains.shape))
+        factor = gains[:, self.pairs[:, 0]] * np.conj(gains[:, self.pairs[:, 1]])
+        return vis * self._per_baseline(vis, factor)
 
     # -- closure sets
     def _stations_up(self, f):
@@ -554,8 +655,16 @@ class Observation(object):
 
         A baseline, triangle or quadrangle that a frame does not observe -- and one with a leg of zero amplitude -- gets the
         target 0 and the sigma +inf: every term of the losses divides by sigma, so it adds exactly 0 to the loss and to the
-        gradient.  AttributeError when no frame observes a triangle / quadrangle that ``dtype`` needs."""
+        gradient.  AttributeError when no frame observes a triangle / quadrangle that ``dtype`` needs.
+
+        The polarimetric terms 'pvis', 'm' and 'pvis+m' take ``vis`` (nt, S >= 3, nvis) of the planes I, Q, U[, V] and give one
+        complex128 target and one sigma (nt, nvis) per term (``PolDFT``).  'pvis': Q~ + i U~ with sqrt(2) sigma.  'm': P / I~ with
+        sigma sqrt(2 + |m|^2) / |I~|, |I~| debiased with ``debias`` -- first-order propagation of equal thermal noise on the three
+        planes.  An unobserved baseline and one with I~ == 0 (or debiased to 0) get the target 0 and the sigma +inf.  The two
+        families do not mix in one dtype: 'cphase+m' is an AttributeError; add the steps (``TrainStep.__add__``)."""
         terms = tuple(str(dtype).split('+'))
+        if any(t in POL_TERMS for t in terms):
+            return self._pol_data(vis, terms, dtype, debias)
         if terms != ('vis',) and (terms != tuple(t for t in CLOSURE_TERMS if t in terms) or len(set(terms)) != len(terms)):
             raise AttributeError("dtype ({}) should be 'vis' or a '+'-joined set of {} in that order".format(dtype, CLOSURE_TERMS))
         vis = np.asarray(vis).astype(np.complex128)
@@ -592,14 +701,58 @@ class Observation(object):
         return out
 
 
-def observe_same(movie, obs, fov, thermal_noise=True, seed=None, device=None):
-    """Synthetic visibilities of ``movie`` (nt, [S,] H, W), one frame per scan of ``obs`` (an ``Observation``), over ``fov`` radians:
-    the clean visibilities from ``DirectDFT.observe`` on the device (``HipError`` without one), plus ``obs.add_thermal_noise`` with
-    ``thermal_noise``; 0 where the baseline is not up.  Returns complex64 NumPy (nt, [S,] nvis).  The reference hands the movie
-    to ehtim, which also corrupts with station gains and D-terms: those are out of scope here -- the closure terms are what this
-    package offers against gains."""
-    movie = np.asarray(movie) if not hasattr(movie, 'detach') else movie
-    vis = obs.dft(fov, tuple(movie.shape[-2:])).observe(movie, device=device).cpu().numpy()
+    def _pol_data(self, vis, terms, dtype, debias):
+        if terms != tuple(t for t in POL_TERMS if t in terms) or len(set(terms)) != len(terms):
+            if all(t in POL_TERMS + CLOSURE_TERMS + ('vis',) for t in terms) and not all(t in POL_TERMS for t in terms):
+                raise AttributeError("dtype ({}) mixes the polarimetric terms {} with another family: build one step per family and add "
+                                     "them (TrainStep.__add__)".format(dtype, POL_TERMS))
+            raise AttributeError("dtype ({}) should be a '+'-joined set of {} in that order".format(dtype, POL_TERMS))
+        vis = np.asarray(vis).astype(np.complex128)
+        if vis.ndim != 3 or vis.shape[1] < 3:
+            raise AttributeError("dtype='{}' needs vis (nt, S >= 3, nvis) of the planes I, Q, U; got {}".format(dtype, vis.shape))
+        self._per_baseline(vis, self.up)
+        out = {'triangles': None, 'quadrangles': None}
+        vI, P = vis[:, 0], vis[:, 1] + 1j * vis[:, 2]
+        if 'pvis' in terms:
+            out['pvis'] = (np.where(self.up, P, 0.0), np.where(self.up, np.sqrt(2.0) * self.sigma, np.inf))
+        if 'm' in terms:
+            amp = np.abs(vI)
+            amp_db = np.sqrt(np.maximum(amp ** 2 - self.sigma ** 2, 0.0)) if debias else amp
+            ok = self.up & (amp > 0) & (amp_db > 0)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                m = np.where(ok, P / np.where(ok, vI, 1.0), 0.0)
+                sig = self.sigma * np.sqrt(2.0 + np.abs(m) ** 2) / amp_db
+            out['m'] = (m, np.where(ok, sig, np.inf))
+        return out
+
+
+def station_gains(obs, amp_sigma=0.1, phase_sigma=np.pi, seed=None):
+    """Random complex station gains (nt, nsites) complex128 for ``Observation.apply_gains`` / ``observe_same``:
+    (1 + amp_sigma n_1) exp(i phase_sigma n_2) per frame and station, from one call
+    ``np.random.default_rng(seed).standard_normal((nt, nsites, 2))``: [..., 0] is n_1, [..., 1] is n_2.  The default phase_sigma
+    leaves no phase information.  A host function; the numbers stand for no particular site."""
+    n = np.random.default_rng(seed).standard_normal((obs.nt, len(obs.array), 2))
+    return (1.0 + float(amp_sigma) * n[..., 0]) * np.exp(1j * float(phase_sigma) * n[..., 1])
+
+
+def observe_host(vis, obs, thermal_noise=True, seed=None, gains=None):
+    """The host part of ``observe_same``: clean visibilities ``vis`` (nt, [S,] nvis) -> station ``gains`` (None: none), then
+    thermal noise, 0 where the baseline is not up; complex64 NumPy."""
+    if gains is not None:
+        vis = obs.apply_gains(vis, gains)
     if thermal_noise:
         return obs.add_thermal_noise(vis, seed)
     return np.where(obs._per_baseline(vis, obs.up), vis, 0.0).astype(np.complex64)
+
+
+def observe_same(movie, obs, fov, thermal_noise=True, seed=None, device=None, gains=None):
+    """Synthetic visibilities of ``movie`` (nt, [S,] H, W), one frame per scan of ``obs`` (an ``Observation``), over ``fov`` radians:
+    the clean visibilities from ``DirectDFT.observe`` on the device (``HipError`` without one), plus ``obs.add_thermal_noise`` with
+    ``thermal_noise``; 0 where the baseline is not up.  Returns complex64 NumPy (nt, [S,] nvis).  ``gains`` (nt, nsites) complex
+    (``station_gains``) multiply the clean visibilities before the thermal noise, V[f, s, k] G[f, a_k] conj(G[f, b_k]), the same on
+    every Stokes plane (``Observation.apply_gains``).  The closure terms on Stokes I and the fractional polarisation 'm'
+    (``PolDFT``) do not see such gains; 'vis', 'amp' and 'pvis' do.  The reference hands the movie to ehtim, which also corrupts
+    with D-terms and with gains that differ between the two polarisations: those are out of scope here."""
+    movie = np.asarray(movie) if not hasattr(movie, 'detach') else movie
+    vis = obs.dft(fov, tuple(movie.shape[-2:])).observe(movie, device=device).cpu().numpy()
+    return observe_host(vis, obs, thermal_noise, seed, gains)

@@ -502,6 +502,25 @@ class TrainStep(object):
         return cls('+'.join(terms), args, network.gradient_step_eht, network.test_eht, scale)
 
     @classmethod
+    def eht_pol(cls, t_frames, uv, fov, npix, data, weights=None, scale=1.0):
+        """Training step on the polarimetric EHT terms from the baselines' (u, v) coordinates: ``data`` = {'pvis': (target, sigma),
+        'm': (target, sigma)} (either or both), targets complex (nt, nvis) and sigmas (nt, nvis), the loss
+        ``scale * sum_d weights[d] chi^2_d`` with P = Q~ + i U~ and m = P / I~ per frame and baseline.  The ray-tracing arguments
+        must render the Stokes planes I, Q, U[, V].  'm' does not see station gains common to the planes of a baseline; for the
+        Stokes-I structure add a closure step: ``TrainStep.eht_obs(.., 'cphase+logcamp') + TrainStep.eht_obs(.., 'm')`` renders and
+        steps once per step.  See ``observation.PolDFT``."""
+        terms = [t for t in observation.POL_TERMS if t in data]
+        if not terms or len(terms) != len(data):
+            raise AttributeError('data should name terms of {}, got {}'.format(observation.POL_TERMS, sorted(data)))
+        op = observation.PolDFT(uv, fov, npix, weights=weights)
+        target = op.pack({t: np.asarray(data[t][0]).astype(np.complex64) for t in terms})
+        sigma = op.pack({t: np.broadcast_to(np.asarray(data[t][1]), np.shape(data[t][0])) for t in terms})
+        if target.ndim != 2:
+            raise AttributeError('polarimetric targets are (nt, nvis): one per frame and baseline, got {}'.format(target.shape))
+        args = TemporalBatchedArgs(t_frames, [target, sigma, op])
+        return cls('+'.join(terms), args, network.gradient_step_eht, network.test_eht, scale)
+
+    @classmethod
     def eht_obs(cls, t_frames, obs, vis, image_fov, image_size, dtype='vis', scale=1.0, count='min', weights=None, debias=True):
         """Training step on an ``observation.Observation`` (``observation.empty_eht_obs``) and its complex visibilities ``vis``
         (nt, [S,] nvis) (``observation.observe_same``, or measured ones in the observation's baseline order) -- what
@@ -509,8 +528,11 @@ class TrainStep(object):
         ``dtype``: 'vis', 'amp' or 'cphase' alone run through ``TrainStep.eht_uv``; 'logcamp' and '+'-joined sets such as
         'cphase+logcamp' through ``TrainStep.eht_closure`` (``weights`` belong to those).  ``count`` and ``debias``: the closure
         sets and the amplitude debiasing of ``Observation.data``.  Stokes planes share ``uv``.  Baselines and closure quantities
-        that a frame does not observe carry sigma = +inf: no loss, no gradient."""
+        that a frame does not observe carry sigma = +inf: no loss, no gradient.  'pvis', 'm' and 'pvis+m' (``vis`` of the planes
+        I, Q, U[, V]) run through ``TrainStep.eht_pol``; they take ``weights`` as well."""
         data = obs.data(vis, dtype, count=count, debias=debias)
+        if any(t in observation.POL_TERMS for t in str(dtype).split('+')):
+            return cls.eht_pol(t_frames, obs.uv, image_fov, image_size, {t: data[t] for t in dtype.split('+')}, weights=weights, scale=scale)
         if dtype in ('vis', 'amp', 'cphase'):
             if weights is not None:
                 raise AttributeError("weights belong to 'logcamp' and '+'-joined dtypes; a single '{}' takes scale".format(dtype))

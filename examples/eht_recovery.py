@@ -7,7 +7,14 @@ Tutorial 2 inside), with nothing but this package -- no ehtim, no astropy:
   Optimizer.run  ->  the 3-D emission sampled back.
 
     python examples/eht_recovery.py [--dtype vis] [--array ngEHT] [--size 32] [--iters 1000] [--render out] [--tracer hip]
+    python examples/eht_recovery.py --stokes --gains          # a polarised movie behind unknown station gains
 
+--stokes observes a polarised movie (Stokes I, Q, U through the transported factors J of a vertical field) and fits what station
+gains cannot touch: TrainStep.eht_obs(.., 'cphase+logcamp') on the I plane (the Q and U planes of its data get sigma = +inf) plus
+TrainStep.eht_obs(.., 'm'), the visibility-domain fractional polarisation (Q~ + iU~) / I~ -- two losses, a render and an Adam step
+each (TrainStep.__add__).  The same data are then fitted on the calibrated 'vis' of the three planes for contrast.  --gains
+corrupts the clean visibilities with random complex station gains (observation.station_gains: 10 % amplitudes, random phases,
+common to the Stokes planes) before the thermal noise: the first fit does not see them, the second fits them as if they were sky.
 --array names a table under tests/golden/eht_arrays/ (ngEHT, EHT2017) or is the path of one in the same text format.
 --render PATH also renders the recovered volume through visualization.VolumeVisualizer and saves PATH.npy (PATH.png with
 matplotlib).  What is and is not ehtim here: see observation.empty_eht_obs and INTEGRATION.md.
@@ -43,8 +50,9 @@ def main():
     ap.add_argument('--count', default='min', choices=['min', 'max'], help='closure sets per frame: an independent set or all')
     ap.add_argument('--seed', type=int, default=0, help='seed of the thermal noise')
     ap.add_argument('--tracer', default='numpy', choices=['numpy', 'hip'], help='where the geodesics are integrated: on the host or on the GPU')
+    ap.add_argument('--stokes', action='store_true', help="a polarised movie (I, Q, U): fit 'cphase+logcamp' on I plus 'm', then 'vis' for contrast")
+    ap.add_argument('--gains', action='store_true', help='corrupt the visibilities with random complex station gains (seed: --seed + 1)')
     args = ap.parse_args()
-    import torch
 
     fov_M, spin, inclination, nt = 16.0, 0.2, np.deg2rad(60.0), args.frames
     flux_scale = 0.1                                            # image-plane fluxes of a `reasonable` size in Jy
@@ -61,7 +69,14 @@ def main():
         resolution=(64, 64, 64), rot_axis=[0.0, 0.0, 1.0], rot_angle=0.0, orbit_radius=5.5, std=0.7, r_isco=constants.isco_pro(spin),
         fov=(fov_M, 'GM/c^2')).data)
     t_frames = np.linspace(tstart, tstop, nt) * units.hr
-    movie = bhnerf.emission.image_plane_dynamics((emission_0, fov_M), geos, Omega, t_frames, t_injection, J=1.0, doppler=True)
+    rmin = float(np.asarray(geos.r).min())
+    J = 1.0
+    if args.stokes:       # transported Stokes factors [I, Q, U] of a vertical field; the I factor of unit mean over the recovery domain,
+        #                   so that the fluxes are of the unpolarised movie's size
+        J = np.nan_to_num(kgeo.emission_factors(geos, Omega, dict(arad=0.0, avert=1.0, ator=0.0), V_frac=0.0)[1], nan=0.0)
+        inside = (np.nan_to_num(np.asarray(geos.r), nan=np.inf) < rmax) & (np.abs(np.nan_to_num(np.asarray(geos.z))) < z_width) & (J[0] > 0)
+        J = J / J[0][inside].mean()
+    movie = bhnerf.emission.image_plane_dynamics((emission_0, fov_M), geos, Omega, t_frames, t_injection, J=J, doppler=True)
 
     # Tutorial 2: the empty observation of the station table and the synthetic data.  The scans sit at the movie's frame times.
     path = args.array if os.path.exists(args.array) else os.path.join(ROOT, 'tests', 'golden', 'eht_arrays', args.array + '.txt')
@@ -69,18 +84,39 @@ def main():
                   'array': observation.Array.load_txt(path)}
     obs = observation.empty_eht_obs(times=np.linspace(tstart, tstop, nt), **obs_params)
     fov_rad = fov_M * RAD_PER_M
-    vis = observation.observe_same(movie, obs, fov_rad, thermal_noise=True, seed=args.seed)
+    gains = observation.station_gains(obs, seed=args.seed + 1) if args.gains else None
+    vis = observation.observe_same(movie, obs, fov_rad, thermal_noise=True, seed=args.seed, gains=gains)
     up = obs.up[0].sum()
-    snr = np.abs(vis[obs.up]) / obs.sigma[obs.up]
+    snr = np.abs(vis[:, 0] if args.stokes else vis)[obs.up] / obs.sigma[obs.up]
+    flux = (movie[:, 0] if args.stokes else movie).sum((-1, -2))                      # Stokes I
     print('%s: %d stations, %d of %d baselines up in frame 0, |uv| up to %.1f Glambda; movie %s of %.3g .. %.3g Jy, median SNR %.0f'
           % (os.path.basename(path), len(obs.array), up, obs.nvis, np.sqrt((obs.uv[obs.up] ** 2).sum(-1)).max() / 1e9, movie.shape,
-             movie.sum((-1, -2)).min(), movie.sum((-1, -2)).max(), np.median(snr)))
+             flux.min(), flux.max(), np.median(snr)))
+    if args.gains:
+        print('station gains: |G| %.2f .. %.2f, random phases, common to the Stokes planes' % (np.abs(gains).min(), np.abs(gains).max()))
 
     # Tutorial 4: the training step on the observation, the optimisation and the recovered volume
-    train_step = optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype=args.dtype, count=args.count)
-    rmin = float(np.asarray(geos.r).min())
+    rt = network.raytracing_args(geos, Omega, t_injection, t_frames[0], J=J)
+    if not args.stokes:
+        train_step = optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype=args.dtype, count=args.count)
+        fit(args, "'%s'" % args.dtype, train_step, geos, rt, rmin, rmax, z_width, fov_M, render=args.render)
+        return
+    # what the gains cannot touch: the closure quantities of Stokes I (the Q and U planes of that step carry no weight) plus 'm'
+    data = obs.data(vis, 'cphase+logcamp', count=args.count)
+    for term in ('cphase', 'logcamp'):
+        data[term][1][:, 1:] = np.inf
+    closure = optimization.TrainStep.eht_closure(t_frames, obs.uv, fov_rad, args.size, obs.pairs, {t: data[t] for t in ('cphase', 'logcamp')},
+                                                 triangles=data['triangles'], quadrangles=data['quadrangles'])
+    robust = closure + optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype='m')
+    fit(args, "'cphase+logcamp' on I + 'm'", robust, geos, rt, rmin, rmax, z_width, fov_M, render=args.render)
+    # for contrast: the calibrated visibilities of the three planes
+    fit(args, "'vis'", optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype='vis'), geos, rt, rmin, rmax, z_width, fov_M)
+
+
+def fit(args, label, train_step, geos, rt, rmin, rmax, z_width, fov_M, render=None):
+    """One optimisation from fresh parameters: chi^2 before and after, the time per iteration, where the recovered emission peaks."""
+    import torch
     predictor = network.NeRF_Predictor(rmax, rmin, rmax, z_width, net_depth=4, net_width=args.width, mode=args.mode)
-    rt = network.raytracing_args(geos, Omega, t_injection, t_frames[0], J=1.0)
     opt = optimization.Optimizer({'num_iters': args.iters, 'lr_init': 1e-3, 'lr_final': 1e-4}, predictor, rt)
     first = optimization.total_movie_loss(args.batch, opt.state, train_step, rt)
     t0 = time.perf_counter()
@@ -89,15 +125,15 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     last = optimization.total_movie_loss(args.batch, opt.state, train_step, rt)
-    print("'%s' chi2 per frame %.4g -> %.4g   (%d iterations in %.1f s = %.2f ms/iteration)" % (args.dtype, first, last, args.iters, dt, 1e3 * dt / args.iters))
+    print('%s chi2 per frame %.4g -> %.4g   (%d iterations in %.1f s = %.2f ms/iteration)' % (label, first, last, args.iters, dt, 1e3 * dt / args.iters))
     n = 64
     ax = np.linspace(-rmax, rmax, n)
     vol = network.sample_3d_grid(predictor.apply, opt.state.params, fov=fov_M, resolution=n)
     i = np.unravel_index(np.argmax(vol), vol.shape)
     print('recovered emission peaks at (x, y, z) = (%.1f, %.1f, %.1f) M; truth (5.5, 0.0, 0.0) at the first frame' % (ax[i[0]], ax[i[1]], ax[i[2]]))
-    if args.render:
+    if render:
         from image_plane_recovery import render_volume
-        render_volume(args.render, predictor, opt.state.params, rmax)
+        render_volume(render, predictor, opt.state.params, rmax)
 
 
 if __name__ == '__main__':

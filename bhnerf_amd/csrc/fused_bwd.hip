@@ -655,7 +655,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
             for (int l = 1; l <= a.depth; ++l) {
                 const bool out = l == a.depth;
                 const bool sk = (a.skip_mask >> l) & 1;              // (odd depths: also the output layer)
-                const float *bl = bias_lds + l * W;
+                const float *bl = bias_lds + RS::opaque(l * W);
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     if (out && m > 0) break;
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) void chain_kernel(BwdArgs A) {
                     // bias rows of the next tile: (l, m+1), or the first tile of the next sequence part
                     const float *bn = (out || (m == MT - 1 && l + 1 > a.depth)) ? nullptr : bl + 32 * (m + 1);
                     if (out) bn = bias_lds;                           // next tile, layer 0
-                    const f32x16 acc = ring_step<W, Pol, RG, TapePost<Pol, true>, NFR>(ch, chn, ap, act, enc, sk, bn, post, dj, 0,
+                    const f32x16 acc = ring_step<W, Pol, RG, TapePost<Pol, true>, NFR, false, ENCR>(ch, chn, ap, act, enc, sk, bn, post, dj, 0,
                                                                                        encblk + 2 * (out ? MT : m) * Pol::FRAG_BYTES);
                     // without the h_1 emission the interval after this layer's first DMA issue holds no store: the
                     // three step ends that count it allow one emission less in flight (small widths: none)

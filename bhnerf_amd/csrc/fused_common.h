@@ -652,7 +652,8 @@ struct PackPost {
 // sequences that never use the encoded-input block (the transposed image of the delta chain: `with_enc` must be false)
 // ZB: every tile of the sequence starts from a ZERO accumulator (the delta chain): no bias rows are read and ap.bias -- sixteen
 // registers that would hold zeros across the step boundary -- is not used
-template <int W, class Pol, class RG, class Post, int NFR = W / 16 + 2, bool ZB = false>
+// ENCW: the step reads the tile's two encoded-input weight fragments at `encw` (below) -- in EVERY step, used or not
+template <int W, class Pol, class RG, class Post, int NFR = W / 16 + 2, bool ZB = false, bool ENCW = false>
 // `dbg`: always 0 (bits 1 / 2 skipped the MFMAs / the post work in measurement builds; kept, see RingState::dbg)
 // `encw` (NFR == KS with an encoded-input block, i.e. the forward kernels whose ring copies only the hidden fragments of a chunk):
 // the tile's two encoded-input weight fragments in the RESIDENT block the kernel filled at its start (EncBlock below)
@@ -662,10 +663,12 @@ DEVI f32x16 ring_step(const char *ch, const char *chn, APipe<Pol> &ap, const typ
     const int lane = threadIdx.x & 63;
     constexpr int KS = W / 16, NF = NFR, PF = Pol::LDS_PREFETCH;
     static_assert(NF == KS + 2 || (NF == KS && KS >= PF - 1), "chunk fragments (the prefetch reaches PF - 1 fragments into the next chunk)");
+    static_assert(!ENCW || NF == KS, "the resident block is read by the KS-fragment streams");
+    // The two fragments are read whether the layer has a skip input or not (`encw` always points into the resident block) and used
+    // under `with_enc`: read under it as well they were a branch at the top of every step and, in the layers without a skip input,
+    // eight v_mov of zeros.  A KS-fragment stream without the block (the delta chain): with_enc is false.
     typename Pol::frag ew0 = Pol::zero(), ew1 = Pol::zero();
-    if constexpr (NF == KS) {
-        if (with_enc) { ew0 = Pol::lds_frag(encw, 0, lane); ew1 = Pol::lds_frag(encw, 1, lane); }     // (read here: landed long before the last k-step)
-    }
+    if constexpr (ENCW) { ew0 = Pol::lds_frag(encw, 0, lane); ew1 = Pol::lds_frag(encw, 1, lane); }     // (read here: landed long before the last k-step)
     typename Pol::frag a[PF];
 #pragma unroll
     for (int i = 0; i < PF - 1; ++i) a[i] = ap.f[i];
@@ -689,7 +692,7 @@ DEVI f32x16 ring_step(const char *ch, const char *chn, APipe<Pol> &ap, const typ
         if (with_enc && do_mma) acc = Pol::mma(a[t % PF], enc[t - KS], acc);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (NF == KS) {
+    if constexpr (ENCW) {
         if (with_enc && do_mma) { acc = Pol::mma(ew0, enc[0], acc); acc = Pol::mma(ew1, enc[1], acc); }
     }
     if (do_post) post.finish();
@@ -867,7 +870,9 @@ struct RingState {
     DEVI const char *chn() const { return ring + opaque(o_nxt); }
     DEVI unsigned next_src() {
         unsigned src;
-        if (issue_c < NCA) src = (unsigned)issue_c * CB;
+        // (a kernel streams one part of the sequence only: nlb == 0 in the forward kernels, NCA == 0 in the delta chain, constants
+        //  after inlining -- the other part and the test fold away; issue_c >= 0 is nothing the compiler knows)
+        if (nlb == 0 || (NCA != 0 && issue_c < NCA)) src = (unsigned)issue_c * CB;
         else {
             const int i = issue_c - NCA;
             src = off_b + (unsigned)((nlb - 1 - i / MT) * MT + i % MT) * CB;
@@ -1016,7 +1021,7 @@ DEVI void hidden_layer(RS &rs, APipe<Pol> &ap, typename Pol::frag (&src)[W / 16]
         PackPost<Pol> post(pend, m == 0 ? src[KS - 2] : dst[2 * (m > 0 ? m - 1 : 0)], m == 0 ? src[KS - 1] : dst[2 * (m > 0 ? m - 1 : 0) + 1]);
         const char *encw = nullptr;                     // (only the KS-fragment streams read the resident encoded-input block)
         if constexpr (NFR == KS) encw = encblk + 2 * m * Pol::FRAG_BYTES;
-        const f32x16 acc = ring_step<W, Pol, RG, PackPost<Pol>, NFR>(ch, chn, ap, src, enc, sk, bl + 32 * (m + 1), post, dj, rs.dbg, encw);
+        const f32x16 acc = ring_step<W, Pol, RG, PackPost<Pol>, NFR, false, NFR == KS>(ch, chn, ap, src, enc, sk, bl + 32 * (m + 1), post, dj, rs.dbg, encw);
         rs.step_end();
         pend = acc;
     }

@@ -192,10 +192,10 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
         float outv;
         {
             // one copy of the layer code (the fully unrolled 3-layer body did not fit the instruction cache:
-            // every step then paid ~1000 cycles of instruction fetch); the price is 56 v_mov per layer
+            // every step then paid ~1000 cycles of instruction fetch); the price is 28 v_mov_b64 behind every layer but the last
 #pragma nounroll
             for (int l = 1; l < a.depth; ++l) {
-                hidden_layer<W, Pol, RG, RS, NFR>(rs, ap, act, next, enc, (a.skip_mask >> l) & 1, bias_lds + l * W, pend, encblk);
+                hidden_layer<W, Pol, RG, RS, NFR>(rs, ap, act, next, enc, (a.skip_mask >> l) & 1, bias_lds + RS::opaque(l * W), pend, encblk);
 #pragma unroll
                 for (int ks = 0; ks < KS - 2; ++ks) act[ks] = next[ks];      // the pending tile lands in act[KS-2], act[KS-1]
             }
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(Pol::NTHREADS) __attribute__((amdgpu_waves_per_eu(P
             const char *ch = rs.ch(), *chn = rs.chn();
             const DmaJob dj = rs.job();
             PackPost<Pol> post(pend, act[KS - 2], act[KS - 1]);
-            const f32x16 acc = ring_step<W, Pol, RG, PackPost<Pol>, NFR>(ch, chn, ap, act, enc, (a.skip_mask >> a.depth) & 1, bias_lds /* next tile, layer 0 */, post, dj, 0,
+            const f32x16 acc = ring_step<W, Pol, RG, PackPost<Pol>, NFR, false, ENCR>(ch, chn, ap, act, enc, (a.skip_mask >> a.depth) & 1, bias_lds /* next tile, layer 0 */, post, dj, 0,
                                                                          encblk + 2 * MT * Pol::FRAG_BYTES);
             outv = acc[0];
             rs.step_end();

@@ -130,8 +130,10 @@ def problem_checksum(prob):
 
 
 def random_problem_inputs(width, depth, S, deg, nudge=0.0, drop_ties=False, shape=RANDOM_PROBLEM_SHAPE, domain=RANDOM_PROBLEM_DOMAIN,
-                          jitter=RANDOM_PROBLEM_JITTER):
-    """random_problem without its float64 reference."""
+                          jitter=RANDOM_PROBLEM_JITTER, do_skip=True):
+    """random_problem without its float64 reference.  do_skip False: the network without skip connections (its layers draw other
+    shapes; conftest.relu_tie_count walks the skip network, so no ties are counted and none can be dropped)."""
+    assert do_skip or not drop_ties
     rng = np.random.default_rng(width + depth)
     H, Wd, G, B = shape
     geo, r = tilted_ray_grid(H, Wd, G, jitter)
@@ -140,7 +142,7 @@ def random_problem_inputs(width, depth, S, deg, nudge=0.0, drop_ties=False, shap
     t_frames = np.sort(rng.uniform(0, 1, B)); t_inj = -(1000.0 - 4.0)
     geo = {k: f32r(v) for k, v in geo.items()}
     J = f32r(J) if S else None
-    tree = onp.he_uniform_params(rng, depth, width, 3 + 6 * deg, dtype=np.float32)
+    tree = onp.he_uniform_params(rng, depth, width, 3 + 6 * deg, do_skip=do_skip, dtype=np.float32)
     nrng = np.random.default_rng(977)
     for i in range(depth + 1):
         d = tree['MLP_0']['Dense_%d' % i]
@@ -153,7 +155,7 @@ def random_problem_inputs(width, depth, S, deg, nudge=0.0, drop_ties=False, shap
              hparams=np.array(list(domain) + [deg, depth, width, 1.0]))
     for i in range(depth + 1):
         g['kernel%d' % i] = tree['MLP_0']['Dense_%d' % i]['kernel']; g['bias%d' % i] = tree['MLP_0']['Dense_%d' % i]['bias']
-    ties, tied = relu_tie_count(g, return_points=True)
+    ties, tied = relu_tie_count(g, return_points=True) if do_skip else (0, None)
     dropped, ties_left = 0, ties
     if drop_ties:                            # tie adjudication: the tied ray samples no longer reach the image
         g = without_samples(g, tied)

@@ -11,6 +11,10 @@ forward run the same ring step on the same packed weights).
 The slab count of the weight-gradient kernel and the grouping of its sums follow the number of compute units, so the recorded bits
 are those of a 256-CU device (MI355X); on any other device the test skips.
 
+The other training paths (fused 4x128, the W_out fold at widths 32 ... 128, the generic tape backward, the 8-bit tape, f32, the general
+path) are pinned the same way by tests/test_gpu_step_same_bits.py, which also holds the first step of the cases below to the bf16
+emulator; tests/same_bits.py is what the two files share.
+
 Cases (all 4 x 256-class networks in bf16, posenc degree 3, built by mlp_problems.random_problem_inputs):
     full_tiles     depth 4, 2 frames, 8 x 5 = 40 rays x 64 samples, all-active domain: 80 groups = 10 tiles of 8 per frame, fewer
                    tiles than workgroups, the last tile of each frame full
@@ -21,8 +25,6 @@ Cases (all 4 x 256-class networks in bf16, posenc degree 3, built by mlp_problem
     depth3         depth 3 (the smallest depth with the ga0 chain), 2 frames, 37 rays x 64 samples
     depth5         depth 5 (odd depth: the output layer takes the skip input), 2 frames, 37 rays x 64 samples
     frame_groups   depth 4, 3 frames, 37 rays x 64 samples, workspace capped to a tape of 2 frames: groups of 2 + 1"""
-import ctypes as C
-import hashlib
 import json
 import os
 import sys
@@ -31,17 +33,16 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, golden_tree
-from gpu_support import dev, predictor_of, ray_args  # noqa: F401
-from mlp_problems import RANDOM_PROBLEM_DOMAIN, RANDOM_PROBLEM_SHAPE, random_problem_inputs
+import same_bits
+from conftest import GOLDEN
+from gpu_support import dev  # noqa: F401
+from mlp_problems import RANDOM_PROBLEM_DOMAIN, RANDOM_PROBLEM_SHAPE
+from same_bits import ARRAYS, CUS, mismatches, record_of
 
 pytestmark = pytest.mark.gpu
 
 FIXTURE = os.path.join(GOLDEN, 'w256_same_bits.json')
 ALL_ACTIVE = (8.0, 0.0, np.inf, np.inf)
-SAMPLE = 1024
-CUS = 256
-ARRAYS = ('loss', 'images', 'grad', 'params', 'adam_m', 'adam_v')
 # name: depth, Stokes planes, (rays H, rays W, samples, frames), domain, loss, frames of tape the workspace is capped to (None: all)
 CASES = {
     'full_tiles': dict(depth=4, S=0, shape=(8, 5, 64, 2), domain=ALL_ACTIVE, dt='full', cap=None),
@@ -57,70 +58,17 @@ LAYOUT = {'full_tiles': (80, False), 'ragged_tile': (74, False), 'stokes3_lc': (
           'depth5': (74, False), 'frame_groups': (74, False)}
 
 
-def bits(t):
-    """A float32 tensor / array as a flat uint32 numpy array."""
-    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    assert a.dtype == np.float32, a.dtype
-    return np.ascontiguousarray(a).reshape(-1).view(np.uint32)
-
-
-def sample_of(u):
-    stride = max(1, -(-u.size // SAMPLE))
-    return stride, u[::stride][:SAMPLE]
-
-
-def record_of(u):
-    stride, s = sample_of(u)
-    return dict(n=int(u.size), sha256=hashlib.sha256(u.tobytes()).hexdigest(), stride=stride, sample=''.join('%08x' % v for v in s))
-
-
-def run_case(dev, name):
-    """Two gradient steps of the case `name` on a fresh predictor -> {array name: uint32 bits}; asserts the layout the case is listed
-    for and render == render_train on the parameters the two steps left."""
-    from bhnerf_amd import _hip, engine as E, network, units
-    from oracle import oracle_np as onp
-    c = CASES[name]
-    H, Wd, G, B = c['shape']
-    prob = random_problem_inputs(256, c['depth'], c['S'], 3, shape=c['shape'], domain=c['domain'])
-    g, S = prob['g'], c['S']
-    pred, rt = predictor_of(g, 'bf16', dev), ray_args(g)
-    eng = pred.engine()
-    geom = pred.geometry(rt['coords'], rt['Omega'], rt['t_geos'], rt['J'] if S else None, rt['g'], rt['dtau'], rt['Sigma'])
-    groups = (geom.P_eff + 31) // 32
+def check_layout(name, eng, geom, groups, flags):
     assert (groups, geom.compact is not None) == LAYOUT[name], (name, groups, geom.compact is not None)
     if geom.compact is not None:
         assert geom.compact['ray_span'] <= 2, (name, geom.compact['ray_span'])
-    if c['cap'] is not None:
-        eng.max_workspace_bytes = int(_hip.lib().bhn_render_bwd_workspace_bytes(C.byref(eng.model), eng.mode, c['cap'], geom.P_eff, dev.index or 0))
-        assert not eng.fits_tape(B, geom.P_eff) and eng.tape_group(B, geom.P_eff) == c['cap'] < B, name
-    else:
-        assert eng.fits_tape(B, geom.P_eff), name
-    flags = eng.tape_info(groups)['flags']
     assert not flags['general'] and not flags['fused128'] and flags['ga0_chain'] and flags['drop_ga'], (name, flags)
-    if c['dt'] == 'full':
-        tg = [prob[k] for k in ('target', 'sigma', 'offset')]
-    else:                                   # light curves: one value per frame and Stokes plane
-        rng = np.random.default_rng(41)
-        tg = [rng.uniform(0, 1e-1, (B, S)), rng.uniform(0.5, 2.0, (B, S)), np.zeros((B, S))]
-    state = pred.init_state(network.ParamTree(golden_tree(g)), num_iters=2, lr_init=1e-3, lr_final=1e-4)
-    for _ in range(2):
-        loss, state, images = network.gradient_step_image(
-            state, units.hr, c['dt'], tg[0], tg[1], tg[2], g['t_frames'], rt['coords'], rt['Omega'], rt['J'], rt['g'], rt['dtau'],
-            rt['Sigma'], rt['t_start_obs'], rt['t_geos'], rt['t_injection'], 1.0)
-    out = dict(loss=bits(loss), images=bits(images), grad=bits(state.grad[:eng.nparams]), params=bits(state.flat), adam_m=bits(state.m),
-               adam_v=bits(state.v))
-    assert state.step == 2 and np.isfinite(out['loss'].view(np.float32)).all() and out['grad'].any() and out['images'].any(), name
-    # the inference forward against the training forward, frame group by frame group
-    tM0 = E.frame_offsets(g['t_frames'], rt['t_start_obs'], rt['t_injection'], onp.GM_C3_SGRA_HR, dev)
-    eng.pack(state.flat)
-    nb = c['cap'] or B
-    for b0 in range(0, B, nb):
-        infer = bits(eng.render(geom, tM0[b0:b0 + nb]))
-        train = bits(eng.render_train(geom, tM0[b0:b0 + nb]))
-        diff = np.nonzero(infer != train)[0]
-        assert diff.size == 0, '%s frames %d..: render and render_train differ in %d of %d image values, first at %d (%08x / %08x)' % (
-            name, b0, diff.size, infer.size, diff[0], infer[diff[0]], train[diff[0]])
-    return out
+
+
+def run_case(dev, name, first=None, drop=None, steps=2):
+    """Two gradient steps of the case `name` on a fresh predictor -> {array name: uint32 bits}; asserts the layout the case is listed
+    for and render == render_train on the parameters the two steps left (same_bits.run_case)."""
+    return same_bits.run_case(dev, name, CASES[name], check_layout, first, drop, steps)
 
 
 @pytest.fixture(scope='module')
@@ -137,23 +85,7 @@ def test_step_keeps_its_bits(dev, recorded, name):
     assert recorded['compute_units'] == CUS and sorted(recorded['cases']) == sorted(CASES)
     out = run_case(dev, name)
     want = recorded['cases'][name]
-    bad = []
-    for k in ARRAYS:
-        got = record_of(out[k])
-        if got['sha256'] == want[k]['sha256'] and got['n'] == want[k]['n']:
-            continue
-        msg = '%s: %d values (recorded %d), sha256 differs' % (k, got['n'], want[k]['n'])
-        if got['n'] == want[k]['n']:
-            stride, s = sample_of(out[k])
-            ref = np.array([int(want[k]['sample'][8 * i:8 * i + 8], 16) for i in range(len(want[k]['sample']) // 8)], dtype=np.uint32)
-            d = np.nonzero(s != ref)[0]
-            if d.size:
-                i = int(d[0])
-                msg += '; first differing sampled element: index %d, %08x (%.9g) against the recorded %08x (%.9g); %d of %d sampled differ' % (
-                    i * stride, s[i], s[i:i + 1].view(np.float32)[0], ref[i], ref[i:i + 1].view(np.float32)[0], d.size, s.size)
-            else:
-                msg += '; every sampled element (stride %d) is equal' % stride
-        bad.append(msg)
+    bad = mismatches(out, want, ARRAYS)
     assert not bad, '%s: %s' % (name, ' | '.join(bad))
 
 

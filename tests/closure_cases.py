@@ -59,13 +59,14 @@ def closure_loss(images, A, data, terms, weights, scale, tri, sign, quad):
 _CASES, _REFS = {}, {}
 
 
-def case(name, Sx=0):
+def case(name, Sx=0, spec=None):
     """Everything about one input set, computed once and left unchanged: the operator pieces (uv, pairs, triangles, quadrangles,
-    tri, sign, quad), images (B, [Sx,] H, W) float32, data {term: (target, sigma)} float32 and the float64 visibilities."""
-    key = (name, Sx)
+    tri, sign, quad), images (B, [Sx,] H, W) float32, data {term: (target, sigma)} float32 and the float64 visibilities.
+    spec: an explicit (H, W, B, seed, stations) under a name of the caller's instead of a row of CASES (tests/eht_edge_cases.py)."""
+    key = (name, Sx) if spec is None else (name, Sx, tuple(spec))
     if key in _CASES:
         return _CASES[key]
-    H, W, B, seed, ns = CASES[name]
+    H, W, B, seed, ns = spec if spec is not None else CASES[name]
     rng = np.random.default_rng(seed)
     pos = rng.normal(size=(B, ns, 2)) * 3e9
     pairs = np.array([(i, j) for i in range(ns) for j in range(i + 1, ns)])

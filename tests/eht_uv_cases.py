@@ -95,13 +95,15 @@ def closure_phases(vis, tri, sign):
 _CASES = {}
 
 
-def case(name, Sx=0):
+def case(name, Sx=0, spec=None, fov=FOV):
     """Everything about one input set, computed once and left unchanged: a dict with the operator pieces (uv, pairs, triangles,
-    tri, sign), images (B, [Sx,] H, W) float32, per dtype (target, sigma) and the float64 reference (loss, grad, vis) at scale 1."""
-    key = (name, Sx)
+    tri, sign), images (B, [Sx,] H, W) float32, per dtype (target, sigma) and the float64 reference (loss, grad, vis) at scale 1.
+    spec: an explicit (H, W, B, seed, stations) under a name of the caller's instead of a row of CASES (tests/eht_edge_cases.py);
+    fov: the field of view, for such a case."""
+    key = (name, Sx) if spec is None else (name, Sx, tuple(spec), fov)
     if key in _CASES:
         return _CASES[key]
-    H, W, B, seed, ns = BIG if name == 'big' else CASES[name]
+    H, W, B, seed, ns = spec if spec is not None else BIG if name == 'big' else CASES[name]
     rng = np.random.default_rng(seed)
     pos = rng.normal(size=(B, ns, 2)) * 3e9
     pairs = np.array([(i, j) for i in range(ns) for j in range(i + 1, ns)])
@@ -110,7 +112,7 @@ def case(name, Sx=0):
     tri, sign = observation.closure_table(pairs, triangles)
     shape = (B, Sx, H, W) if Sx else (B, H, W)
     images, truth = blobs(rng, shape), blobs(rng, shape)
-    A = dense128(uv, FOV, H, W)
+    A = dense128(uv, fov, H, W)
     vis_truth = table_loss(truth, A, np.zeros(shape[:-2] + (len(pairs),), dtype=np.complex128), 1.0, 1.0, 'vis')[2]
     s_vis = (0.05 * np.abs(vis_truth).mean() * rng.uniform(0.5, 1.5, vis_truth.shape)).astype(np.float32)
     cp = closure_phases(vis_truth, tri, sign)
@@ -120,7 +122,7 @@ def case(name, Sx=0):
     ref = {d: table_loss(images, A, t, s, 1.0, d, tri, sign) for d, (t, s) in data.items()}
     amp = np.abs(ref['vis'][2])
     out = dict(name=name, H=H, W=W, B=B, ns=ns, Sx=Sx, uv=uv, pairs=pairs, triangles=triangles, tri=tri, sign=sign, images=images,
-               data=data, ref=ref, A128=A, min_amp=float(amp.min() / amp.max()))
+               data=data, ref=ref, A128=A, min_amp=float(amp.min() / amp.max()), fov=fov)
     _CASES[key] = out
     return out
 
@@ -128,8 +130,8 @@ def case(name, Sx=0):
 def operator(c, dtype):
     """The DirectDFT of a case for one dtype: with the triangle table for 'cphase', without otherwise."""
     if dtype == 'cphase':
-        return observation.DirectDFT(c['uv'], FOV, (c['H'], c['W']), triangles=c['triangles'], pairs=c['pairs'])
-    return observation.DirectDFT(c['uv'], FOV, (c['H'], c['W']))
+        return observation.DirectDFT(c['uv'], c.get('fov', FOV), (c['H'], c['W']), triangles=c['triangles'], pairs=c['pairs'])
+    return observation.DirectDFT(c['uv'], c.get('fov', FOV), (c['H'], c['W']))
 
 
 def rel_max(got, want):

@@ -73,13 +73,14 @@ def pol_loss(images, A, data, terms, weights, scale, mutant=None):
 _CASES, _REFS = {}, {}
 
 
-def case(name, Sx):
+def case(name, Sx, spec=None):
     """Everything about one input set, computed once and left unchanged: uv, pairs, images (B, Sx, H, W) float32, data {term:
-    (target complex64 (B, nvis), sigma float32 (B, nvis))}, the dense A and the float64 visibilities of the images."""
-    key = (name, Sx)
+    (target complex64 (B, nvis), sigma float32 (B, nvis))}, the dense A and the float64 visibilities of the images.
+    spec: an explicit (H, W, B, seed, stations) under a name of the caller's instead of a row of CASES (tests/eht_edge_cases.py)."""
+    key = (name, Sx) if spec is None else (name, Sx, tuple(spec))
     if key in _CASES:
         return _CASES[key]
-    H, W, B, seed, ns = CASES[name]
+    H, W, B, seed, ns = spec if spec is not None else CASES[name]
     rng = np.random.default_rng(seed)
     pos = rng.normal(size=(B, ns, 2)) * 3e9
     pairs = np.array([(i, j) for i in range(ns) for j in range(i + 1, ns)])

@@ -1,7 +1,7 @@
 """ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
 (include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h), libbhnerf_eql.so (include/bhnerf_eql.h), libbhnerf_flow.so
-(include/bhnerf_flow.h), libbhnerf_rec.so (include/bhnerf_rec.h), libbhnerf_cls.so (include/bhnerf_cls.h) and libbhnerf_pol.so
-(include/bhnerf_pol.h).
+(include/bhnerf_flow.h), libbhnerf_rec.so (include/bhnerf_rec.h), libbhnerf_cls.so (include/bhnerf_cls.h), libbhnerf_pol.so
+(include/bhnerf_pol.h) and libbhnerf_reg.so (include/bhnerf_reg.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -216,6 +216,16 @@ POL_SIGNATURES = {
     'bhn_pol_chi2': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _D, _D, _PT, _PT, _F, _P, _P, _P, _SZ, _P]),
 }
 POL_LIBRARY = (POL_LIB_PATH, POL_SIGNATURES, 'bhn_pol_last_error', None)
+
+# libbhnerf_reg.so (include/bhnerf_reg.h): the volume priors tv, tsv and l1 on the recovered 3-D emission, the tenth library
+REG_LIB_PATH = os.path.join(CSRC, 'libbhnerf_reg.so')
+_F3 = C.POINTER(C.c_float)
+REG_SIGNATURES = {
+    'bhn_reg_last_error': (C.c_char_p, []),
+    'bhn_reg_ws_bytes': (_SZ, [_I32, _I32, _I32, _I32]),
+    'bhn_reg_loss': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _F3, _F3, _F, _F, _P, _P, _P, _P, _SZ, _P]),
+}
+REG_LIBRARY = (REG_LIB_PATH, REG_SIGNATURES, 'bhn_reg_last_error', None)
 _loaded = {}                 # path -> handle
 
 
@@ -226,7 +236,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec', 'libbhnerf_cls', 'libbhnerf_pol']), CSRC))
+        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec', 'libbhnerf_cls', 'libbhnerf_pol', 'libbhnerf_reg']), CSRC))
     return LIB_PATH
 
 
@@ -310,6 +320,11 @@ def pol_lib():
     return _lib('libbhnerf_pol', POL_LIBRARY)
 
 
+def reg_lib():
+    """The loaded volume-prior library."""
+    return _lib('libbhnerf_reg', REG_LIBRARY)
+
+
 def check(rc):
     _check('libbhnerf_hip', rc)
 
@@ -344,6 +359,10 @@ def cls_check(rc):
 
 def pol_check(rc):
     _check('libbhnerf_pol', rc, POL_LIBRARY)
+
+
+def reg_check(rc):
+    _check('libbhnerf_reg', rc, REG_LIBRARY)
 
 
 def stream_ptr(device=None):

@@ -706,8 +706,52 @@ def chi2_eht_pol(images, op, target, sigma, scale, dtype, want_grad=True):
     return loss[:1], (dimg.reshape(images.shape) if want_grad else None)
 
 
+def chi2_volume(volumes, op, scale, mask=None, want_grad=True):
+    """scale * sum_d w_d term_d over the terms tv, tsv, l1 of a ``regularization.VolumePrior`` on `volumes`: N volumes on the
+    operator's lattice, (N, nx, ny, nz), (nx, ny, nz) or flat, a float32 device tensor -- the emission a training step sampled,
+    or ``sample_3d_grid`` output moved to the device (the prior as a metric).  `mask`: (nx, ny, nz) of {0, 1}, shared by the
+    volumes, None for all ones; differences across its boundary are not counted (bhn_reg_loss).  Returns (loss[1], dvolumes
+    shaped like volumes or None); the four floats {total, tv, tsv, l1} stay on the device as ``op.last_terms``, the unscaled sums
+    per volume (3, N) as ``op.last_per_volume``.  AttributeError for every shape mismatch and for a normalised prior on an empty
+    mask, before any launch."""
+    V = op.num_voxels
+    if not isinstance(volumes, torch.Tensor) or int(volumes.numel()) == 0 or int(volumes.numel()) % V != 0:
+        raise AttributeError('volumes {} are not volumes of {} x {} x {} voxels'.format(tuple(np.shape(volumes)), *op.dims))
+    if mask is not None and int(np.prod(np.shape(mask))) != V:
+        raise AttributeError('mask {} is not one of {} x {} x {} voxels'.format(tuple(np.shape(mask)), *op.dims))
+    weights = op.call_weights(mask)
+    _hip.require_device(volumes)
+    N = int(volumes.numel()) // V
+    dev, lib = volumes.device, _hip.reg_lib()
+    vol = volumes.reshape(N, V).to(torch.float32).contiguous()
+    if mask is not None and not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype == torch.uint8 and mask.is_contiguous()):
+        # (a training step hands over the geometry's own mask, which is taken as it is)
+        mask = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(mask))
+        mask = mask.to(dev).ne(0).to(torch.uint8).contiguous()
+    key = (N,) + tuple(op.dims)
+    nbytes = _REG_WS_BYTES.get(key)
+    if nbytes is None:
+        nbytes = _REG_WS_BYTES[key] = int(lib.bhn_reg_ws_bytes(*key))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((4,), dtype=torch.float32, device=dev)
+    per_volume = torch.empty((3, N), dtype=torch.float32, device=dev)
+    dvol = torch.empty_like(vol) if want_grad else None
+    f3 = C.c_float * 3
+    args = (vol.data_ptr(), N, *op.dims, _hip.ptr(mask), f3(*op.spacing), f3(*weights), float(op.eps), float(scale), loss.data_ptr(),
+            per_volume.data_ptr(), dvol.data_ptr() if want_grad else None, ws.data_ptr(), nbytes, _hip.stream_ptr(dev))
+    if dev.index is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            rc = lib.bhn_reg_loss(*args)
+    else:
+        rc = lib.bhn_reg_loss(*args)
+    _hip.reg_check(rc)
+    op.last_terms, op.last_per_volume = loss, per_volume
+    return loss[:1], (dvol.reshape(volumes.shape) if want_grad else None)
+
+
 _CLS_WS_BYTES = {}
 _POL_WS_BYTES = {}
+_REG_WS_BYTES = {}
 _TABLE_RANGE = {}               # id of a checked table -> (the table, what lies outside [0, nvis) or None)
 
 

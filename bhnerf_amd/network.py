@@ -17,7 +17,7 @@ import numpy as np
 import torch
 import yaml
 
-from . import _hip, checkpoints, constants, engine, observation, units, utils
+from . import _hip, checkpoints, constants, engine, observation, regularization, units, utils
 
 safe_sin = lambda x: (torch.sin(torch.remainder(x, 100 * np.pi)) if isinstance(x, torch.Tensor)
                       else np.sin(x % (100 * np.pi)))                       # network.py:16
@@ -514,6 +514,20 @@ def _pass(eng, geom, tM0, images, chi2, grad, taped):
     return loss, images
 
 
+def _finish_step(state, buf, n, loss, train):
+    """The tail of a step: training, the all-reduce of buf[:n] and Adam; testing, the ranks' losses gathered.  Returns the
+    vector of per-rank losses."""
+    rank, world = _world()
+    if train:
+        return _exchange_and_apply(state, buf, n, loss, rank, world)
+    if world > 1:
+        import torch.distributed as dist
+        parts = [torch.empty_like(loss) for _ in range(world)]
+        dist.all_gather(parts, loss)
+        return torch.cat(parts)
+    return loss
+
+
 def _slot_images(images, geom):
     """(B,Sx,R) -> (1, B, [S], *spatial): the leading axis is this process's "device" slot of the reference's pmap output."""
     return images.reshape((1, images.shape[0]) + ((geom.S,) if geom.S else ()) + geom.spatial)
@@ -558,17 +572,7 @@ def _step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, 
                           part if b0 else buf[:n], True)[0]
             if b0:
                 buf[:n] += part
-    rank, world = _world()
-    if train:
-        loss_vec = _exchange_and_apply(state, buf, n, loss, rank, world)
-    elif world > 1:
-        import torch.distributed as dist
-        parts = [torch.empty_like(loss) for _ in range(world)]
-        dist.all_gather(parts, loss)
-        loss_vec = torch.cat(parts)
-    else:
-        loss_vec = loss
-    return loss_vec, state, _slot_images(images, geom)
+    return _finish_step(state, buf, n, loss, train), state, _slot_images(images, geom)
 
 
 def gradient_step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, Omega, J, g, dtau, Sigma,
@@ -604,6 +608,46 @@ def test_eht(state, t_units, dtype, target, sigma, A, t_frames, coords, Omega, J
 
 
 test_eht.__test__ = False
+
+
+def _step_volume(state, t_units, dtype, op, t_start_obs, scale, train):
+    """Per-process body of gradient_step_volume / test_volume: pack -> `_pass` on the operator's lattice (one sample per "ray",
+    g = dtau = Sigma = 1: the render IS the emission) with the prior as its chi2 -> all-reduce -> Adam."""
+    if dtype != 'volume' or not isinstance(op, regularization.VolumePrior):
+        raise AttributeError('volume dtype ({}) takes a regularization.VolumePrior, got {}'.format(dtype, type(op).__name__))
+    pred = state.predictor
+    eng = pred.engine()
+    geom = pred.geometry(op.coords, 0.0, 0.0)
+    # one frame at t_start_obs, t_injection = 0: sample_3d_grid's convention (no warp, nothing before injection)
+    t0, _ = _time_origin(t_start_obs, t_units)
+    tM0, _ = _frame_offsets(np.array([t0]), t_units, t_start_obs, 0.0, eng.device)
+    eng.pack(state.flat)
+    taped = train and eng.fits_tape(1, geom.P_eff)      # (else the backward re-runs the forward: bhn_render_bwd takes any size)
+    chi2 = lambda im: engine.chi2_volume(im, op, scale, mask=geom.dom, want_grad=train)
+    n = eng.nparams
+    buf = state.grad_buffer() if train else None
+    loss, images = _pass(eng, geom, tM0, None, chi2, buf[:n] if train else None, taped)
+    op.last_volume = images.reshape(op.dims)
+    return _finish_step(state, buf, n, loss, train), state, torch.zeros((), dtype=torch.float32, device=eng.device)
+
+
+def gradient_step_volume(state, t_units, dtype, target, sigma, op, t_frames, coords, Omega, J, g, dtau, Sigma,
+                         t_start_obs, t_geos, t_injection, scale):
+    """Gradient step on a prior on the emission volume (`op`: a regularization.VolumePrior; dtype 'volume'): the step functions'
+    positional signature, of which the ray set (coords .. Sigma, t_geos, t_injection), the frame times and target / sigma are
+    ignored -- the emission is sampled on the operator's own lattice at t_start_obs, unwarped, as sample_3d_grid samples it, and
+    the predictor's domain on that lattice is the mask.  Returns (loss[ndev], state, a 0-d zero tensor): a prior has no images,
+    and the zero lets TrainStep.__call__'s sum over terms keep the data term's."""
+    return _step_volume(state, t_units, dtype, op, t_start_obs, scale, True)
+
+
+def test_volume(state, t_units, dtype, target, sigma, op, t_frames, coords, Omega, J, g, dtau, Sigma,
+                t_start_obs, t_geos, t_injection, scale):
+    """Forward-only twin of gradient_step_volume."""
+    return _step_volume(state, t_units, dtype, op, t_start_obs, scale, False)
+
+
+test_volume.__test__ = False
 
 
 def sample_3d_grid(apply_fn, params, t_frame=0, t_start_obs=0, Omega=0, fov=None, coords=None, resolution=64, chunk=-1):

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import _hip, checkpoints, engine, network, observation, units
+from . import _hip, checkpoints, engine, network, observation, regularization, units
 
 try:  # progress bar is optional
     from tqdm.auto import tqdm
@@ -564,9 +564,37 @@ class TrainStep(object):
             target, sigma = np.deg2rad(target), np.deg2rad(sigma)
         return cls.eht_arrays(t_frames, target, sigma, A, dtype, scale)
 
+    @classmethod
+    def volume_prior(cls, fov, resolution=64, weights=None, eps=1e-6, scale=1.0, coords=None, normalize=True):
+        """Training step on a prior on the recovered 3-D emission: the terms 'tv', 'tsv', 'l1' of ``regularization.VolumePrior``
+        on the lattice ``fov`` (M) x ``resolution`` (or a regular ``coords``), the loss ``scale * sum_d weights[d] term_d``.  Used
+        as ``TrainStep.image(...) + TrainStep.volume_prior(...)``: like every term of a sum it takes its own Adam step; alone, a
+        prior-only step runs.  It ignores the frame indices and the ray set.  In test mode it adds its loss ONCE PER CALL, whatever
+        the number of frames of the call: ``total_movie_loss`` therefore counts it once per chunk of the movie."""
+        op = regularization.VolumePrior(fov, resolution, coords, weights, eps, normalize)
+        return cls('volume', StaticArgs(op), network.gradient_step_volume, network.test_volume, scale)
+
     @property
     def t_units(self):
         return self.args[0].t_units
+
+
+class StaticArgs(object):
+    """The arguments of a term that has no per-frame data (TrainStep.volume_prior): one operator in the place of a loss's third
+    per-frame array.  The interface of TemporalBatchedArgs as far as TrainStep and Optimizer use it."""
+
+    num_frames = 1
+    t_units = units.hr
+
+    def __init__(self, op):
+        self.op = op
+
+    def sample(self, batchsize, replace=False):
+        """There is nothing to draw: indices that __getitem__ ignores (a prior-only step runs)."""
+        return np.zeros(batchsize, dtype=np.int64)
+
+    def __getitem__(self, key):
+        return [None, None, self.op, np.zeros(1)]           # target, sigma, the operator, frame times
 
 
 class TemporalBatchedArgs(object):

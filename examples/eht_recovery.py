@@ -8,6 +8,7 @@ Tutorial 2 inside), with nothing but this package -- no ehtim, no astropy:
 
     python examples/eht_recovery.py [--dtype vis] [--array ngEHT] [--size 32] [--iters 1000] [--render out] [--tracer hip]
     python examples/eht_recovery.py --stokes --gains          # a polarised movie behind unknown station gains
+    python examples/eht_recovery.py --tv 1e3 [--tv-res 32]    # the data term plus a total-variation prior on the emission volume
 
 --stokes observes a polarised movie (Stokes I, Q, U through the transported factors J of a vertical field) and fits what station
 gains cannot touch: TrainStep.eht_obs(.., 'cphase+logcamp') on the I plane (the Q and U planes of its data get sigma = +inf) plus
@@ -17,7 +18,10 @@ corrupts the clean visibilities with random complex station gains (observation.s
 common to the Stokes planes) before the thermal noise: the first fit does not see them, the second fits them as if they were sky.
 --array names a table under tests/golden/eht_arrays/ (ngEHT, EHT2017) or is the path of one in the same text format.
 --render PATH also renders the recovered volume through visualization.VolumeVisualizer and saves PATH.npy (PATH.png with
-matplotlib).  What is and is not ehtim here: see observation.empty_eht_obs and INTEGRATION.md.
+matplotlib).  --tv W adds TrainStep.volume_prior (the smoothed total variation of the emission on a --tv-res^3 lattice over the
+field of view, a mean over the in-domain voxels, times W) to whatever objective the flags select: a second loss with a render of
+the lattice and an Adam step of its own.  The chi^2 printed is the data term's alone, and every fit ends with the tv of the
+recovered 64^3 volume (engine.chi2_volume as a metric), so that runs with and without the prior compare.  What is and is not ehtim here: see observation.empty_eht_obs and INTEGRATION.md.
 """
 import argparse
 import os
@@ -52,6 +56,8 @@ def main():
     ap.add_argument('--tracer', default='numpy', choices=['numpy', 'hip'], help='where the geodesics are integrated: on the host or on the GPU')
     ap.add_argument('--stokes', action='store_true', help="a polarised movie (I, Q, U): fit 'cphase+logcamp' on I plus 'm', then 'vis' for contrast")
     ap.add_argument('--gains', action='store_true', help='corrupt the visibilities with random complex station gains (seed: --seed + 1)')
+    ap.add_argument('--tv', type=float, default=0.0, metavar='W', help='weight of a total-variation prior on the emission volume (0: none)')
+    ap.add_argument('--tv-res', type=int, default=32, metavar='N', help='the prior samples the emission on an N x N x N lattice over the field of view')
     args = ap.parse_args()
 
     fov_M, spin, inclination, nt = 16.0, 0.2, np.deg2rad(60.0), args.frames
@@ -113,24 +119,37 @@ def main():
     fit(args, "'vis'", optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype='vis'), geos, rt, rmin, rmax, z_width, fov_M)
 
 
-def fit(args, label, train_step, geos, rt, rmin, rmax, z_width, fov_M, render=None):
-    """One optimisation from fresh parameters: chi^2 before and after, the time per iteration, where the recovered emission peaks."""
+def fit(args, label, data_step, geos, rt, rmin, rmax, z_width, fov_M, render=None):
+    """One optimisation from fresh parameters: chi^2 of the data before and after, the time per iteration, where the recovered
+    emission peaks and its total variation."""
     import torch
+    from bhnerf_amd import engine, regularization
+    train_step = data_step
+    if args.tv > 0:
+        train_step = data_step + optimization.TrainStep.volume_prior(fov_M, resolution=args.tv_res, weights={'tv': 1.0}, scale=args.tv)
+        label += ' + %g tv at %d^3' % (args.tv, args.tv_res)
     predictor = network.NeRF_Predictor(rmax, rmin, rmax, z_width, net_depth=4, net_width=args.width, mode=args.mode)
     opt = optimization.Optimizer({'num_iters': args.iters, 'lr_init': 1e-3, 'lr_final': 1e-4}, predictor, rt)
-    first = optimization.total_movie_loss(args.batch, opt.state, train_step, rt)
+    first = optimization.total_movie_loss(args.batch, opt.state, data_step, rt)
     t0 = time.perf_counter()
     opt.run(args.batch, train_step, rt, log_fns=[optimization.LogFn(
         lambda o: print('iter %5d  chi2/frame %.4g' % (o.step, float(np.mean(o.loss)))), max(50, args.iters // 10))])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    last = optimization.total_movie_loss(args.batch, opt.state, train_step, rt)
+    last = optimization.total_movie_loss(args.batch, opt.state, data_step, rt)
     print('%s chi2 per frame %.4g -> %.4g   (%d iterations in %.1f s = %.2f ms/iteration)' % (label, first, last, args.iters, dt, 1e3 * dt / args.iters))
     n = 64
     ax = np.linspace(-rmax, rmax, n)
     vol = network.sample_3d_grid(predictor.apply, opt.state.params, fov=fov_M, resolution=n)
     i = np.unravel_index(np.argmax(vol), vol.shape)
     print('recovered emission peaks at (x, y, z) = (%.1f, %.1f, %.1f) M; truth (5.5, 0.0, 0.0) at the first frame' % (ax[i[0]], ax[i[1]], ax[i[2]]))
+    # the prior as a metric: mean smoothed |grad e| over the recovery domain of the 64^3 volume
+    x, y, z = np.meshgrid(ax, ax, ax, indexing='ij')
+    r = np.sqrt(x ** 2 + y ** 2 + z ** 2)
+    domain = ((r >= rmin) & (r <= rmax) & (np.abs(z) <= z_width)).astype(np.uint8)
+    metric = regularization.VolumePrior(fov=fov_M, resolution=n, weights={'tv': 1.0})
+    tv = engine.chi2_volume(torch.as_tensor(vol, device=opt.state.flat.device), metric, 1.0, mask=domain, want_grad=False)[0]
+    print('tv of the recovered volume (mean |grad e| over %d in-domain voxels of %d^3): %.4e per M, peak emission %.4e' % (domain.sum(), n, float(tv), vol.max()))
     if render:
         from image_plane_recovery import render_volume
         render_volume(render, predictor, opt.state.params, rmax)

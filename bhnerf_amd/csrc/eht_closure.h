@@ -5,7 +5,7 @@
 // One visibility pass serves up to three real-valued terms, in the canonical order amp, cphase, logcamp:
 //     loss = scale (w_amp chi^2_amp + w_cphase chi^2_cphase + w_logcamp chi^2_logcamp).
 // 'amp' and 'cphase' are eht_term_amp / eht_term_cphase / eht_gather_weight / eht_gather_gv of eht_uv.h unchanged, handed the
-// term's effective scale.  'logcamp' is the log closure amplitude of a quadrangle of baselines (legs 0, 1 over legs 2, 3):
+// term's effective scale (eht_term_scale, csrc/eht_terms.h).  'logcamp' is the log closure amplitude of a quadrangle of baselines (legs 0, 1 over legs 2, 3):
 //     y = 1/2 (log m_0 + log m_1 - log m_2 - log m_3),  m_l = |V_l|^2,   term ((y - target) / sigma)^2.
 // |V_ab| = |V_ba|: the table needs no signs.
 #ifndef BHNERF_EHT_CLOSURE_H
@@ -46,11 +46,6 @@ EHT_HD bool cls_make_plan(int32_t N, int32_t nvis, int32_t ncp, int32_t nca, int
     p->bytes = o;
     return true;
 }
-
-// The effective scale of a term: scale w_d, formed once on the host and rounded once to float32 (weight 1 changes no bit).
-EHT_HD float cls_effective_scale(float scale, double weight) { return (float)((double)scale * weight); }
-
-EHT_HD bool cls_weight_ok(double w) { return w >= 0.0 && w < 1e300; }      // false for a negative, infinite or NaN weight
 
 // Log closure amplitude of quadrangle q of plane n from the table; *dy = dL/dy = 2 scale d / sigma.  A leg of zero amplitude
 // takes the quadrangle out of the loss and of the gradient (the rule of the zero gradient at |vis| = 0, extended: frames before

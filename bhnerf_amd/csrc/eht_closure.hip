@@ -7,28 +7,23 @@
 //   cls_loss_kernel      one workgroup per plane: a visibility = its row splits' partial sums in order, KEPT in the workspace;
 //                        'amp' one lane per visibility, its gv into a buffer of its own; then one lane per triangle leaves
 //                        dL/dphi and one lane per quadrangle dL/dy, in lane-stride loops; three block sums per plane
-//   cls_loss_sum_kernel  the planes' sums of each term in order, and their total
+//   eht_terms_sum_kernel the planes' sums of each term in order, and their total (csrc/eht_terms.h, as are the terms of a call)
 //   cls_gather_kernel    one wave per (plane, baseline): the triangle and the quadrangle table scanned in 64-lane slices with a
 //                        butterfly sum each; gv = gv_amp + gv_cphase + gv_logcamp
-//   eht_adjoint_kernel   as in csrc/eht_uv.hip
+//   eht_adjoint_kernel   as in csrc/eht_uv.hip (eht_launch_adjoint)
 // No atomics, no allocation, no synchronisation: every sum has one fixed order that does not depend on how many frames a call
 // holds.  With dimages NULL the last two are not launched.
 #include <hip/hip_runtime.h>
 
 #include "../../include/bhnerf_cls.h"
 #include "eht_closure.h"
+#include "eht_terms.h"
 #include "eht_uv_kernels.h"
 #include "side_lib.h"
 
 extern "C" const char *bhn_cls_last_error(void) { return side_last_error(); }
 
-// the terms of a call as the kernels take them: device pointers and effective scales, 0 / NULL for an absent term
-struct ClsTerms {
-    const float *target[CLS_TERMS];
-    const float *sigma[CLS_TERMS];
-    float scale[CLS_TERMS];
-    int present[CLS_TERMS];
-};
+typedef EhtTerms<CLS_TERMS> ClsTerms;
 
 // A lane adds its terms in order, the workgroup adds the lanes in a fixed order (eht_block_sum_256, the order of eht_loss_kernel):
 // terms[d, n] does not depend on the planes computed with it.  `vis` is written and, after the barrier, read by this workgroup.
@@ -73,24 +68,6 @@ __global__ __launch_bounds__(256) void cls_loss_kernel(const EhtC *__restrict__ 
     }
 }
 
-// loss[1 + d] = the planes' sums of term d in the order of eht_loss_sum_kernel; loss[0] = amp + cphase + logcamp in that order
-__global__ __launch_bounds__(256) void cls_loss_sum_kernel(float *__restrict__ loss, const float *__restrict__ terms, int n) {
-    __shared__ float red[CLS_TERMS][4];
-    float tot[CLS_TERMS];
-#pragma unroll
-    for (int d = 0; d < CLS_TERMS; ++d) {
-        float acc = 0.f;
-        for (int i = threadIdx.x; i < n; i += 256) acc += terms[(size_t)d * n + i];
-        tot[d] = eht_block_sum_256(acc, red[d]);
-    }
-    if (threadIdx.x == 0) {
-        loss[1 + CLS_AMP] = tot[CLS_AMP];
-        loss[1 + CLS_CPHASE] = tot[CLS_CPHASE];
-        loss[1 + CLS_LOGCAMP] = tot[CLS_LOGCAMP];
-        loss[0] = (tot[CLS_AMP] + tot[CLS_CPHASE]) + tot[CLS_LOGCAMP];
-    }
-}
-
 // one wave per (plane, baseline); the lanes share a table, their sums are added in a butterfly (the order of eht_gather_kernel)
 __global__ __launch_bounds__(256) void cls_gather_kernel(const EhtC *__restrict__ vis, ClsPlan p, ClsTerms a, const int32_t *__restrict__ tri,
                                                          const int8_t *__restrict__ tri_sign, const int32_t *__restrict__ quad,
@@ -127,25 +104,17 @@ extern "C" size_t bhn_cls_ws_bytes(int32_t N, int32_t nvis, int32_t ncp, int32_t
     return cls_make_plan(N, nvis, ncp, nca, H, W, &p) ? p.bytes : 0;
 }
 
-// a present term: its arrays and its weight
-static int cls_term_check(const bhn_cls_term *t, const char *name) {
-    if (!t) return BHN_OK;
-    BHN_CHECK_ARG(t->target && t->sigma, "term '%s' with a null target or sigma", name);
-    BHN_CHECK_ARG(cls_weight_ok(t->weight), "term '%s': weight %g must be finite and >= 0", name, t->weight);
-    return BHN_OK;
-}
-
 extern "C" int bhn_cls_chi2(const float *images, const double *uv, int32_t N, int32_t Sx, int32_t nvis, int32_t H, int32_t W,
                             double psize_x, double psize_y, const bhn_cls_term *amp, const bhn_cls_term *cphase,
                             const bhn_cls_term *logcamp, const int32_t *tri, const int8_t *tri_sign, int32_t ncp, const int32_t *quad,
                             int32_t nca, float scale, float *loss, float *dimages, void *ws, size_t ws_bytes, void *stream) {
     ClsPlan p;
-    const bhn_cls_term *in[CLS_TERMS] = {amp, cphase, logcamp};
+    ClsTerms a;
+    const bhn_cls_term *const in[CLS_TERMS] = {amp, cphase, logcamp};
     static const char *const names[CLS_TERMS] = {"amp", "cphase", "logcamp"};
     BHN_CHECK_ARG(images && uv && ws && loss, "null pointer");
     BHN_CHECK_ARG(amp || cphase || logcamp, "no term present");
-    for (int d = 0; d < CLS_TERMS; ++d)
-        if (int rc = cls_term_check(in[d], names[d])) return rc;
+    if (int rc = eht_terms_take(in, names, scale, &a)) return rc;
     BHN_CHECK_ARG(!cphase || (ncp >= 1 && tri && tri_sign), "closure phases need a triangle table (ncp = %d, tri %s)", ncp,
                   tri && tri_sign ? "given" : "NULL");
     BHN_CHECK_ARG(!logcamp || (nca >= 1 && quad), "log closure amplitudes need a quadrangle table (nca = %d, quad %s)", nca,
@@ -160,13 +129,6 @@ extern "C" int bhn_cls_chi2(const float *images, const double *uv, int32_t N, in
         return side_fail(BHN_EWORKSPACE, "workspace of %zu bytes, bhn_cls_ws_bytes(%d, %d, %d, %d, %d, %d) = %zu", ws_bytes, N, nvis, ncp, nca, H, W,
                          p.bytes);
 
-    ClsTerms a;
-    for (int d = 0; d < CLS_TERMS; ++d) {
-        a.present[d] = in[d] ? 1 : 0;
-        a.target[d] = in[d] ? in[d]->target : nullptr;
-        a.sigma[d] = in[d] ? in[d]->sigma : nullptr;
-        a.scale[d] = in[d] ? cls_effective_scale(scale, in[d]->weight) : 0.f;
-    }
     hipStream_t st = (hipStream_t)stream;
     char *w = static_cast<char *>(ws);
     EhtC *vis = reinterpret_cast<EhtC *>(w + p.e.off_vis), *gva = reinterpret_cast<EhtC *>(w + p.off_gva);
@@ -180,17 +142,13 @@ extern "C" int bhn_cls_chi2(const float *images, const double *uv, int32_t N, in
     hipLaunchKernelGGL(cls_loss_kernel, dim3((unsigned)N), dim3(256), 0, st, reinterpret_cast<const EhtC *>(w + p.e.off_part), p, a, vis, tri,
                        tri_sign, quad, amp_only ? gv : gva, dphi, dy, terms, dimages ? 1 : 0);
     if (int rc = side_launched("cls_loss_kernel")) return rc;
-    hipLaunchKernelGGL(cls_loss_sum_kernel, dim3(1), dim3(256), 0, st, loss, terms, (int)N);
-    if (int rc = side_launched("cls_loss_sum_kernel")) return rc;
+    hipLaunchKernelGGL(eht_terms_sum_kernel<CLS_TERMS>, dim3(1), dim3(256), 0, st, loss, terms, (int)N, (int)N);
+    if (int rc = side_launched("eht_terms_sum_kernel")) return rc;
     if (!dimages) return BHN_OK;
     if (!amp_only) {
         hipLaunchKernelGGL(cls_gather_kernel, dim3((unsigned)((N * nvis + 3) / 4)), dim3(256), 0, st, vis, p, a, tri, tri_sign, quad, gva, dphi, dy,
                            gv);
         if (int rc = side_launched("cls_gather_kernel")) return rc;
     }
-    hipLaunchKernelGGL(eht_adjoint_kernel, dim3((unsigned)((W + p.e.block - 1) / p.e.block), (unsigned)((H + EHT_ADJ_ROWS - 1) / EHT_ADJ_ROWS),
-                                                (unsigned)N),
-                       dim3((unsigned)p.e.block), 0, st, gv, reinterpret_cast<const EhtC *>(w + p.e.off_eu),
-                       reinterpret_cast<const EhtC *>(w + p.e.off_ev), p.e, Sx, dimages);
-    return side_launched("eht_adjoint_kernel");
+    return eht_launch_adjoint(gv, w, p.e, Sx, dimages, st);
 }

@@ -13,7 +13,7 @@
 #ifndef BHNERF_EHT_POL_H
 #define BHNERF_EHT_POL_H
 
-#include "eht_closure.h"          // cls_effective_scale, cls_weight_ok: the effective scale of a term is formed as there
+#include "eht_uv.h"
 
 #define POL_PVIS 0                // the canonical order of the terms: loss[1 + d], the order gv and the total are added in
 #define POL_M 1

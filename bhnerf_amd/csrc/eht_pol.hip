@@ -7,26 +7,21 @@
 //   pol_loss_kernel      one workgroup per FRAME, lanes strided over the baselines: a lane combines the row splits' partial sums
 //                        of the Sx planes of its baseline in order (kept in the workspace), computes both terms and leaves gv of
 //                        all Sx planes; two block sums per frame
-//   pol_loss_sum_kernel  the frames' sums of each term in order, and their total
-//   eht_adjoint_kernel   as in csrc/eht_uv.hip
+//   eht_terms_sum_kernel the frames' sums of each term in order, and their total (csrc/eht_terms.h, as are the terms of a call)
+//   eht_adjoint_kernel   as in csrc/eht_uv.hip (eht_launch_adjoint)
 // The terms are per baseline: no gather stage.  No atomics, no allocation, no synchronisation: every sum has one fixed order that
 // does not depend on how many frames a call holds.  With dimages NULL the adjoint is not launched and gv is not written.
 #include <hip/hip_runtime.h>
 
 #include "../../include/bhnerf_pol.h"
 #include "eht_pol.h"
+#include "eht_terms.h"
 #include "eht_uv_kernels.h"
 #include "side_lib.h"
 
 extern "C" const char *bhn_pol_last_error(void) { return side_last_error(); }
 
-// the terms of a call as the kernels take them: device pointers and effective scales, 0 / NULL for an absent term
-struct PolTerms {
-    const float *target[POL_TERMS];
-    const float *sigma[POL_TERMS];
-    float scale[POL_TERMS];
-    int present[POL_TERMS];
-};
+typedef EhtTerms<POL_TERMS> PolTerms;
 
 // A lane adds its baselines in order, the workgroup adds the lanes in a fixed order (eht_block_sum_256): terms[d, b] does not
 // depend on the frames computed with it.  Every index is below N nvis (planes b Sx + s < N, k < nvis) or B nvis (b < B).
@@ -68,46 +63,21 @@ __global__ __launch_bounds__(256) void pol_loss_kernel(const EhtC *__restrict__ 
     }
 }
 
-// loss[1 + d] = the frames' sums of term d in the order of eht_loss_sum_kernel; loss[0] = pvis + m
-__global__ __launch_bounds__(256) void pol_loss_sum_kernel(float *__restrict__ loss, const float *__restrict__ terms, int N, int B) {
-    __shared__ float red[POL_TERMS][4];
-    float tot[POL_TERMS];
-#pragma unroll
-    for (int d = 0; d < POL_TERMS; ++d) {
-        float acc = 0.f;
-        for (int i = threadIdx.x; i < B; i += 256) acc += terms[(size_t)d * N + i];
-        tot[d] = eht_block_sum_256(acc, red[d]);
-    }
-    if (threadIdx.x == 0) {
-        loss[1 + POL_PVIS] = tot[POL_PVIS];
-        loss[1 + POL_M] = tot[POL_M];
-        loss[0] = tot[POL_PVIS] + tot[POL_M];
-    }
-}
-
 extern "C" size_t bhn_pol_ws_bytes(int32_t N, int32_t nvis, int32_t H, int32_t W) {
     PolPlan p;
     return pol_make_plan(N, nvis, H, W, &p) ? p.bytes : 0;
-}
-
-// a present term: its arrays and its weight
-static int pol_term_check(const bhn_pol_term *t, const char *name) {
-    if (!t) return BHN_OK;
-    BHN_CHECK_ARG(t->target && t->sigma, "term '%s' with a null target or sigma", name);
-    BHN_CHECK_ARG(cls_weight_ok(t->weight), "term '%s': weight %g must be finite and >= 0", name, t->weight);
-    return BHN_OK;
 }
 
 extern "C" int bhn_pol_chi2(const float *images, const double *uv, int32_t N, int32_t Sx, int32_t nvis, int32_t H, int32_t W,
                             double psize_x, double psize_y, const bhn_pol_term *pvis, const bhn_pol_term *m, float scale, float *loss,
                             float *dimages, void *ws, size_t ws_bytes, void *stream) {
     PolPlan p;
-    const bhn_pol_term *in[POL_TERMS] = {pvis, m};
+    PolTerms a;
+    const bhn_pol_term *const in[POL_TERMS] = {pvis, m};
     static const char *const names[POL_TERMS] = {"pvis", "m"};
     BHN_CHECK_ARG(images && uv && ws && loss, "null pointer");
     BHN_CHECK_ARG(pvis || m, "no term present");
-    for (int d = 0; d < POL_TERMS; ++d)
-        if (int rc = pol_term_check(in[d], names[d])) return rc;
+    if (int rc = eht_terms_take(in, names, scale, &a)) return rc;
     BHN_CHECK_ARG(pol_stokes_ok(Sx), "the polarimetric terms need the planes I, Q, U[, V]: Sx must be 3 or 4 (Sx = %d)", Sx);
     const char *why = eht_sizes_error(N, Sx, nvis, 0, H, W, psize_x, psize_y);
     BHN_CHECK_ARG(!why, "%s (N %d, Sx %d, nvis %d, H %d, W %d, pixel %g x %g rad)", why, N, Sx, nvis, H, W, psize_x, psize_y);
@@ -116,13 +86,6 @@ extern "C" int bhn_pol_chi2(const float *images, const double *uv, int32_t N, in
     if (ws_bytes < p.bytes)
         return side_fail(BHN_EWORKSPACE, "workspace of %zu bytes, bhn_pol_ws_bytes(%d, %d, %d, %d) = %zu", ws_bytes, N, nvis, H, W, p.bytes);
 
-    PolTerms a;
-    for (int d = 0; d < POL_TERMS; ++d) {
-        a.present[d] = in[d] ? 1 : 0;
-        a.target[d] = in[d] ? in[d]->target : nullptr;
-        a.sigma[d] = in[d] ? in[d]->sigma : nullptr;
-        a.scale[d] = in[d] ? cls_effective_scale(scale, in[d]->weight) : 0.f;
-    }
     hipStream_t st = (hipStream_t)stream;
     char *w = static_cast<char *>(ws);
     EhtC *vis = reinterpret_cast<EhtC *>(w + p.e.off_vis), *gv = reinterpret_cast<EhtC *>(w + p.off_gv);
@@ -133,12 +96,8 @@ extern "C" int bhn_pol_chi2(const float *images, const double *uv, int32_t N, in
     hipLaunchKernelGGL(pol_loss_kernel, dim3((unsigned)B), dim3(256), 0, st, reinterpret_cast<const EhtC *>(w + p.e.off_part), p, (int)Sx, a, vis,
                        gv, terms, dimages ? 1 : 0);
     if (int rc = side_launched("pol_loss_kernel")) return rc;
-    hipLaunchKernelGGL(pol_loss_sum_kernel, dim3(1), dim3(256), 0, st, loss, terms, (int)N, B);
-    if (int rc = side_launched("pol_loss_sum_kernel")) return rc;
+    hipLaunchKernelGGL(eht_terms_sum_kernel<POL_TERMS>, dim3(1), dim3(256), 0, st, loss, terms, (int)N, B);
+    if (int rc = side_launched("eht_terms_sum_kernel")) return rc;
     if (!dimages) return BHN_OK;
-    hipLaunchKernelGGL(eht_adjoint_kernel, dim3((unsigned)((W + p.e.block - 1) / p.e.block), (unsigned)((H + EHT_ADJ_ROWS - 1) / EHT_ADJ_ROWS),
-                                                (unsigned)N),
-                       dim3((unsigned)p.e.block), 0, st, gv, reinterpret_cast<const EhtC *>(w + p.e.off_eu),
-                       reinterpret_cast<const EhtC *>(w + p.e.off_ev), p.e, Sx, dimages);
-    return side_launched("eht_adjoint_kernel");
+    return eht_launch_adjoint(gv, w, p.e, Sx, dimages, st);
 }

@@ -2,8 +2,8 @@
 // coordinates of the baselines, without the dense DFT matrices of bhn_chi2_eht (csrc/simple_kernels.hip).
 //
 // csrc/eht_uv.h holds the plan (workspace layout, row splits) and the per-element arithmetic, shared with the CPU build of
-// tools/eht_uv_host.cpp; csrc/eht_uv_kernels.h holds the twiddle, forward, combine and adjoint kernels and eht_forward, shared with
-// libbhnerf_cls.so (csrc/eht_closure.hip).  The launches of a call, all on the caller's stream:
+// tools/eht_uv_host.cpp; csrc/eht_uv_kernels.h holds the twiddle, forward, combine and adjoint kernels with their launches (eht_forward,
+// eht_launch_adjoint), shared with libbhnerf_cls.so and libbhnerf_pol.so.  The launches of a call, all on the caller's stream:
 //   eht_twiddle_kernel   Eu (B, nvis, W), Ev (B, nvis, H) into the workspace: float64 phase, reduced to turns, rounded to complex64
 //   eht_fwd_kernel       grid (baseline blocks of EHT_KB, row splits, planes): a lane owns image columns; a pixel is loaded into
 //                        a register once and multiplies the Ev of all EHT_KB baselines, the column sums are then rotated by Eu and
@@ -14,7 +14,7 @@
 //                        'cphase' one lane per triangle, phi from the index table
 //   eht_loss_sum_kernel  the planes' loss sums in order
 //   eht_gather_kernel    'cphase' only: a baseline's gradient gathered from its triangles, one wave per (plane, baseline)
-//   eht_adjoint_kernel   grid (column blocks, EHT_ADJ_ROWS-row strips, planes): per pixel a loop over the baselines
+//   eht_adjoint_kernel   (eht_launch_adjoint) grid (column blocks, EHT_ADJ_ROWS-row strips, planes): per pixel a loop over the baselines
 // No atomics, no allocation, no synchronisation: every sum has one fixed order, and that order does not depend on how many frames
 // a call holds.  The image is read nvis / EHT_KB times in the forward pass (from L2 after the first), the tables are the only
 // other traffic: nothing of size nvis x H x W is ever read or written.
@@ -22,7 +22,7 @@
 
 #include "../../include/bhnerf_eht.h"
 #include "eht_uv.h"
-#include "eht_uv_kernels.h"      // the kernels shared with libbhnerf_cls.so, eht_forward
+#include "eht_uv_kernels.h"      // the kernels shared with libbhnerf_cls.so and libbhnerf_pol.so, eht_forward, eht_launch_adjoint
 #include "side_lib.h"
 
 extern "C" const char *bhn_eht_last_error(void) { return side_last_error(); }
@@ -136,8 +136,5 @@ extern "C" int bhn_eht_chi2_uv(const float *images, const double *uv, int32_t N,
         hipLaunchKernelGGL(eht_gather_kernel, dim3((unsigned)((N * nvis + 3) / 4)), dim3(256), 0, st, vis, p, tri, tri_sign, dphi);
         if (int rc = side_launched("eht_gather_kernel")) return rc;
     }
-    hipLaunchKernelGGL(eht_adjoint_kernel, dim3((unsigned)((W + p.block - 1) / p.block), (unsigned)((H + EHT_ADJ_ROWS - 1) / EHT_ADJ_ROWS), (unsigned)N),
-                       dim3((unsigned)p.block), 0, st, vis, reinterpret_cast<const EhtC *>(w + p.off_eu),
-                       reinterpret_cast<const EhtC *>(w + p.off_ev), p, Sx, dimages);
-    return side_launched("eht_adjoint_kernel");
+    return eht_launch_adjoint(vis, w, p, Sx, dimages, st);
 }

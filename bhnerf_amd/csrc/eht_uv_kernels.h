@@ -1,7 +1,7 @@
-// The device kernels that libbhnerf_eht.so (csrc/eht_uv.hip) and libbhnerf_cls.so (csrc/eht_closure.hip) share: twiddle tables,
-// forward partial sums, their combination, the 256-lane block sum and the adjoint, with eht_forward, the launches of the first
-// three.  One text for both libraries: the visibilities and the adjoint of the two are the same arithmetic in the same order,
-// so V and dimages of one are bitwise those of the other.  HIP only; the plan and the per-element arithmetic are csrc/eht_uv.h.
+// The device kernels that libbhnerf_eht.so (csrc/eht_uv.hip), libbhnerf_cls.so (csrc/eht_closure.hip) and libbhnerf_pol.so
+// (csrc/eht_pol.hip) share: twiddle tables, forward partial sums, their combination, the 256-lane block sum and the adjoint, with
+// eht_forward, the launches of the first three, and eht_launch_adjoint, the launch of the last.  One text for the libraries: the
+// visibilities and the adjoint of each are the same arithmetic in the same order, so V and dimages of one are bitwise another's.  HIP only; the plan and the per-element arithmetic are csrc/eht_uv.h.
 #ifndef BHNERF_EHT_UV_KERNELS_H
 #define BHNERF_EHT_UV_KERNELS_H
 
@@ -112,6 +112,15 @@ static int eht_forward(const float *images, const double *uv, const EhtPlan &p, 
     if (!vis) return BHN_OK;                               // (bhn_eht_chi2_uv combines in its loss stage)
     hipLaunchKernelGGL(eht_combine_kernel, dim3((unsigned)((p.N * p.nvis + 255) / 256)), dim3(256), 0, st, part, p, vis);
     return side_launched("eht_combine_kernel");
+}
+
+// the adjoint of gv (N, nvis) into dimages, from the twiddle tables eht_forward left in the workspace
+static int eht_launch_adjoint(const EhtC *gv, const char *ws, const EhtPlan &p, int32_t Sx, float *dimages, hipStream_t st) {
+    hipLaunchKernelGGL(eht_adjoint_kernel, dim3((unsigned)((p.W + p.block - 1) / p.block), (unsigned)((p.H + EHT_ADJ_ROWS - 1) / EHT_ADJ_ROWS),
+                                                (unsigned)p.N),
+                       dim3((unsigned)p.block), 0, st, gv, reinterpret_cast<const EhtC *>(ws + p.off_eu),
+                       reinterpret_cast<const EhtC *>(ws + p.off_ev), p, Sx, dimages);
+    return side_launched("eht_adjoint_kernel");
 }
 
 #endif /* BHNERF_EHT_UV_KERNELS_H */

@@ -526,6 +526,31 @@ def eht_vis_uv(movie, op):
     return torch.view_as_complex(out).reshape(lead + (op.nvis,))
 
 
+_WS_BYTES = {}                  # (library, the sizes of a call) -> bytes of workspace
+
+
+def _term_call(name, lib, entry, check, key, head, nloss, like, want_grad, outputs=()):
+    """The one call path of the weighted-term losses: ``entry(*head, loss, *outputs, gradient or NULL, ws, ws_bytes, stream)`` of
+    the library `name` ('eht' | 'cls' | 'pol' | 'reg') on fresh buffers -- the workspace of ``bhn_<name>_ws_bytes(*key)`` (asked
+    once per key), `nloss` floats of loss and, with `want_grad`, a gradient like `like` -- on the device of `like`, then
+    ``check(rc)``.  Returns (loss, gradient or None)."""
+    nbytes = _WS_BYTES.get((name, key))
+    if nbytes is None:
+        nbytes = _WS_BYTES[name, key] = int(getattr(lib, 'bhn_%s_ws_bytes' % name)(*key))
+    dev = like.device
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((nloss,), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(like) if want_grad else None
+    args = head + (loss.data_ptr(),) + outputs + (grad.data_ptr() if want_grad else None, ws.data_ptr(), nbytes, _hip.stream_ptr(dev))
+    if dev.index is not None and dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            rc = entry(*args)
+    else:                                  # (the usual case: no device switch around a call of a few tens of microseconds)
+        rc = entry(*args)
+    check(rc)
+    return loss, grad
+
+
 def chi2_eht_uv(images, op, target, sigma, scale, dtype, want_grad=True):
     """chi2_eht from an observation.DirectDFT: the loss and its image gradient from the (u, v) coordinates (bhn_eht_chi2_uv),
     no dense matrix anywhere.  Raises the AttributeErrors of the dense path for a wrong count, before any launch."""
@@ -547,39 +572,49 @@ def chi2_eht_uv(images, op, target, sigma, scale, dtype, want_grad=True):
     dev, lib = img.device, _hip.eht_lib()
     tgt = _eht_uv_array(target, dev, torch.complex64 if dtype == 'vis' else torch.float32, None)
     sig = _eht_uv_array(sigma, dev, torch.float32, tuple(target.shape))
-    key = (N, op.nvis, op.ncp, op.H, op.W)
-    nbytes = _EHT_WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = _EHT_WS_BYTES[key] = int(lib.bhn_eht_ws_bytes(*key))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-    loss = torch.empty((1,), dtype=torch.float32, device=dev)
-    dimg = torch.empty_like(img) if want_grad else None
     psy, psx = op.psize
-    args = (img.data_ptr(), op.uv.data_ptr(), N, Sx, op.nvis, op.H, op.W, psx, psy, code, tgt.data_ptr(), sig.data_ptr(), float(scale),
-            _hip.ptr(op.tri), _hip.ptr(op.tri_sign), op.ncp, loss.data_ptr(), dimg.data_ptr() if want_grad else None, ws.data_ptr(), nbytes,
-            _hip.stream_ptr(dev))
-    if dev.index is not None and dev.index != torch.cuda.current_device():
-        with torch.cuda.device(dev):
-            rc = lib.bhn_eht_chi2_uv(*args)
-    else:                                  # (the usual case: no device switch around a call of a few tens of microseconds)
-        rc = lib.bhn_eht_chi2_uv(*args)
-    _hip.eht_check(rc)
+    head = (img.data_ptr(), op.uv.data_ptr(), N, Sx, op.nvis, op.H, op.W, psx, psy, code, tgt.data_ptr(), sig.data_ptr(), float(scale),
+            _hip.ptr(op.tri), _hip.ptr(op.tri_sign), op.ncp)
+    loss, dimg = _term_call('eht', lib, lib.bhn_eht_chi2_uv, _hip.eht_check, (N, op.nvis, op.ncp, op.H, op.W), head, 1, img, want_grad)
     return loss, (dimg.reshape(images.shape) if want_grad else None)
 
 
-_EHT_WS_BYTES = {}
+def terms_of(dtype, canonical):
+    """The terms of a '+'-joined dtype over the names `canonical`, in that order and each at most once -> a tuple of names; None
+    for anything else."""
+    if not isinstance(dtype, str):
+        return None
+    terms = tuple(dtype.split('+'))
+    if terms and terms == tuple(t for t in canonical if t in terms) and len(set(terms)) == len(terms):
+        return terms
+    return None
 
 
 def closure_terms(dtype):
     """The terms of a combined closure dtype: a '+'-joined string of 'amp', 'cphase', 'logcamp' in that (canonical) order, each
     at most once -- 'logcamp', 'cphase+logcamp', 'amp+cphase', 'amp+cphase+logcamp', 'amp', ... -> a tuple of names; None for
     anything else."""
-    if not isinstance(dtype, str):
-        return None
-    terms = tuple(dtype.split('+'))
-    if terms and terms == tuple(t for t in observation.CLOSURE_TERMS if t in terms) and len(set(terms)) == len(terms):
-        return terms
-    return None
+    return terms_of(dtype, observation.CLOSURE_TERMS)
+
+
+def pol_terms(dtype):
+    """The terms of a polarimetric dtype: 'pvis', 'm' or 'pvis+m' (the canonical order, each at most once) -> a tuple of names;
+    None for anything else."""
+    return terms_of(dtype, observation.POL_TERMS)
+
+
+def _term_structs(struct_type, terms, sizes, tgt, sig, weights):
+    """A term's columns of `tgt` and `sig` (rows, the terms' sizes side by side) as arrays of their own, what the libraries take:
+    ({term: struct_type(target, sigma, weight)}, the tensors the structs point into, to be held across the call)."""
+    structs, keep, o = {}, [], 0
+    for t in terms:
+        tt, ss = tgt[:, o:o + sizes[t]], sig[:, o:o + sizes[t]]
+        if len(terms) > 1:
+            tt, ss = tt.contiguous(), ss.contiguous()
+        keep += [tt, ss]
+        structs[t] = struct_type(tt.data_ptr(), ss.data_ptr(), float(weights[t]))
+        o += sizes[t]
+    return structs, keep
 
 
 def chi2_closure_uv(images, op, target, sigma, scale, dtype, want_grad=True):
@@ -609,46 +644,16 @@ def chi2_closure_uv(images, op, target, sigma, scale, dtype, want_grad=True):
     dev, lib = img.device, _hip.cls_lib()
     tgt = _eht_uv_array(target, dev, torch.float32, None).reshape(N, nterm)
     sig = _eht_uv_array(sigma, dev, torch.float32, tuple(target.shape)).reshape(N, nterm)
-    structs, keep, o = {}, [], 0
-    for t in terms:                                          # a term's columns as an array of its own: what the library takes
-        tt, ss = tgt[:, o:o + sizes[t]], sig[:, o:o + sizes[t]]
-        if len(terms) > 1:
-            tt, ss = tt.contiguous(), ss.contiguous()
-        keep += [tt, ss]
-        structs[t] = _hip.bhn_cls_term(tt.data_ptr(), ss.data_ptr(), float(op.weights[t]))
-        o += sizes[t]
+    structs, keep = _term_structs(_hip.bhn_cls_term, terms, sizes, tgt, sig, op.weights)
     ncp, nca = (op.ncp if 'cphase' in terms else 0), (op.nca if 'logcamp' in terms else 0)
-    key = (N, op.nvis, ncp, nca, op.H, op.W)
-    nbytes = _CLS_WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = _CLS_WS_BYTES[key] = int(lib.bhn_cls_ws_bytes(*key))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-    loss = torch.empty((4,), dtype=torch.float32, device=dev)
-    dimg = torch.empty_like(img) if want_grad else None
     psy, psx = op.psize
-    ref = lambda t: C.byref(structs[t]) if t in structs else None
-    args = (img.data_ptr(), op_dev.uv.data_ptr(), N, Sx, op.nvis, op.H, op.W, psx, psy, ref('amp'), ref('cphase'), ref('logcamp'),
+    head = (img.data_ptr(), op_dev.uv.data_ptr(), N, Sx, op.nvis, op.H, op.W, psx, psy,
+            *(C.byref(structs[t]) if t in structs else None for t in observation.CLOSURE_TERMS),
             _hip.ptr(op_dev.tri) if ncp else None, _hip.ptr(op_dev.tri_sign) if ncp else None, ncp, _hip.ptr(op_dev.quad) if nca else None, nca,
-            float(scale), loss.data_ptr(), dimg.data_ptr() if want_grad else None, ws.data_ptr(), nbytes, _hip.stream_ptr(dev))
-    if dev.index is not None and dev.index != torch.cuda.current_device():
-        with torch.cuda.device(dev):
-            rc = lib.bhn_cls_chi2(*args)
-    else:
-        rc = lib.bhn_cls_chi2(*args)
-    _hip.cls_check(rc)
+            float(scale))
+    loss, dimg = _term_call('cls', lib, lib.bhn_cls_chi2, _hip.cls_check, (N, op.nvis, ncp, nca, op.H, op.W), head, 4, img, want_grad)
     op.last_terms = loss
     return loss[:1], (dimg.reshape(images.shape) if want_grad else None)
-
-
-def pol_terms(dtype):
-    """The terms of a polarimetric dtype: 'pvis', 'm' or 'pvis+m' (the canonical order, each at most once) -> a tuple of names;
-    None for anything else."""
-    if not isinstance(dtype, str):
-        return None
-    terms = tuple(dtype.split('+'))
-    if terms and terms == tuple(t for t in observation.POL_TERMS if t in terms) and len(set(terms)) == len(terms):
-        return terms
-    return None
 
 
 def chi2_eht_pol(images, op, target, sigma, scale, dtype, want_grad=True):
@@ -678,30 +683,11 @@ def chi2_eht_pol(images, op, target, sigma, scale, dtype, want_grad=True):
     dev, lib = img.device, _hip.pol_lib()
     tgt = _eht_uv_array(target, dev, torch.complex64, None)
     sig = _eht_uv_array(sigma, dev, torch.float32, (B, nterm))
-    structs, keep = {}, []
-    for i, t in enumerate(terms):                            # a term's columns as an array of its own: what the library takes
-        tt, ss = tgt[:, i * nvis:(i + 1) * nvis], sig[:, i * nvis:(i + 1) * nvis]
-        if len(terms) > 1:
-            tt, ss = tt.contiguous(), ss.contiguous()
-        keep += [tt, ss]
-        structs[t] = _hip.bhn_pol_term(tt.data_ptr(), ss.data_ptr(), float(op.weights[t]))
-    key = (N, nvis, op.H, op.W)
-    nbytes = _POL_WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = _POL_WS_BYTES[key] = int(lib.bhn_pol_ws_bytes(*key))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-    loss = torch.empty((3,), dtype=torch.float32, device=dev)
-    dimg = torch.empty_like(img) if want_grad else None
+    structs, keep = _term_structs(_hip.bhn_pol_term, terms, op.term_sizes(), tgt, sig, op.weights)
     psy, psx = op.psize
-    ref = lambda t: C.byref(structs[t]) if t in structs else None
-    args = (img.data_ptr(), op_dev.uv.data_ptr(), N, Sx, nvis, op.H, op.W, psx, psy, ref('pvis'), ref('m'), float(scale), loss.data_ptr(),
-            dimg.data_ptr() if want_grad else None, ws.data_ptr(), nbytes, _hip.stream_ptr(dev))
-    if dev.index is not None and dev.index != torch.cuda.current_device():
-        with torch.cuda.device(dev):
-            rc = lib.bhn_pol_chi2(*args)
-    else:
-        rc = lib.bhn_pol_chi2(*args)
-    _hip.pol_check(rc)
+    head = (img.data_ptr(), op_dev.uv.data_ptr(), N, Sx, nvis, op.H, op.W, psx, psy,
+            *(C.byref(structs[t]) if t in structs else None for t in observation.POL_TERMS), float(scale))
+    loss, dimg = _term_call('pol', lib, lib.bhn_pol_chi2, _hip.pol_check, (N, nvis, op.H, op.W), head, 3, img, want_grad)
     op.last_terms = loss
     return loss[:1], (dimg.reshape(images.shape) if want_grad else None)
 
@@ -728,30 +714,15 @@ def chi2_volume(volumes, op, scale, mask=None, want_grad=True):
         # (a training step hands over the geometry's own mask, which is taken as it is)
         mask = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(mask))
         mask = mask.to(dev).ne(0).to(torch.uint8).contiguous()
-    key = (N,) + tuple(op.dims)
-    nbytes = _REG_WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = _REG_WS_BYTES[key] = int(lib.bhn_reg_ws_bytes(*key))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-    loss = torch.empty((4,), dtype=torch.float32, device=dev)
     per_volume = torch.empty((3, N), dtype=torch.float32, device=dev)
-    dvol = torch.empty_like(vol) if want_grad else None
     f3 = C.c_float * 3
-    args = (vol.data_ptr(), N, *op.dims, _hip.ptr(mask), f3(*op.spacing), f3(*weights), float(op.eps), float(scale), loss.data_ptr(),
-            per_volume.data_ptr(), dvol.data_ptr() if want_grad else None, ws.data_ptr(), nbytes, _hip.stream_ptr(dev))
-    if dev.index is not None and dev.index != torch.cuda.current_device():
-        with torch.cuda.device(dev):
-            rc = lib.bhn_reg_loss(*args)
-    else:
-        rc = lib.bhn_reg_loss(*args)
-    _hip.reg_check(rc)
+    head = (vol.data_ptr(), N, *op.dims, _hip.ptr(mask), f3(*op.spacing), f3(*weights), float(op.eps), float(scale))
+    loss, dvol = _term_call('reg', lib, lib.bhn_reg_loss, _hip.reg_check, (N,) + tuple(op.dims), head, 4, vol, want_grad,
+                            outputs=(per_volume.data_ptr(),))
     op.last_terms, op.last_per_volume = loss, per_volume
     return loss[:1], (dvol.reshape(volumes.shape) if want_grad else None)
 
 
-_CLS_WS_BYTES = {}
-_POL_WS_BYTES = {}
-_REG_WS_BYTES = {}
 _TABLE_RANGE = {}               # id of a checked table -> (the table, what lies outside [0, nvis) or None)
 
 

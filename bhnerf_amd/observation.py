@@ -110,17 +110,24 @@ class DirectDFT(object):
         """(psize_y, psize_x) in radians."""
         return self.fov[0] / self.H, self.fov[1] / self.W
 
-    def _like(self, uv, tri=None, tri_sign=None):
-        out = object.__new__(DirectDFT)
+    def _like(self, uv, move=None):
+        """The operator on another ``uv``, with whatever of the tables and weights this one has (a subclass adds ``quad``,
+        ``weights``); ``move``: what takes a table to where ``uv`` now is (None: the tables as they are)."""
+        out = object.__new__(type(self))
         out.uv, out.H, out.W, out.fov = uv, self.H, self.W, self.fov
-        out.tri, out.tri_sign = (self.tri, self.tri_sign) if tri is None else (tri, tri_sign)
+        for k in ('tri', 'tri_sign', 'quad'):
+            if hasattr(self, k):
+                table = getattr(self, k)
+                setattr(out, k, table if table is None or move is None else move(table))
+        if hasattr(self, 'weights'):
+            out.weights = dict(self.weights)
         return out
 
     def to(self, device):
-        """The operator with ``uv`` (float64) and the closure table on ``device``."""
+        """The operator with ``uv`` (float64) and the closure tables on ``device``."""
         import torch
-        mv = lambda a: None if a is None else torch.as_tensor(a, device=device)
-        return self._like(mv(self.uv), mv(self.tri), mv(self.tri_sign))
+        mv = lambda a: torch.as_tensor(a, device=device)
+        return self._like(mv(self.uv), mv)
 
     def take(self, indices):
         """The operator of a batch of frames: on a device an ``index_select`` of the float64 ``uv``."""
@@ -166,6 +173,68 @@ class DirectDFT(object):
 CLOSURE_TERMS = ('amp', 'cphase', 'logcamp')         # the canonical order of the terms of a combined closure loss
 
 
+def term_weights(canonical, weights, default):
+    """{term: w >= 0} over the terms ``canonical`` from ``weights`` ({term: w} or None), ``default`` where not given;
+    AttributeError for an unknown term and for a weight that is negative or not finite."""
+    weights = dict(weights or {})
+    unknown = sorted(set(weights) - set(canonical))
+    if unknown:
+        raise AttributeError('weights name unknown terms {} (known: {})'.format(unknown, ', '.join(canonical)))
+    out = {k: float(weights.get(k, default)) for k in canonical}
+    if not all(np.isfinite(w) and w >= 0 for w in out.values()):
+        raise AttributeError('weights must be finite and >= 0, got {}'.format(out))
+    return out
+
+
+class TermSet(object):
+    """What the operators of ONE weighted objective ``scale * sum_d w_d chi^2_d`` share (a mixin): ``TERMS``, the canonical order
+    of the terms, and ``term_sizes()``, {term: entries along the last axis} of the terms the operator can serve, give the weights
+    and the layout of the data -- the terms' arrays concatenated along the last axis in the canonical order."""
+    TERMS = ()
+
+    def _weights(self, weights, default=1.0):
+        return term_weights(self.TERMS, weights, default)
+
+    def pack(self, data):
+        """{term: x, ...} -> the arrays concatenated along the last axis in the canonical order (only the terms named)."""
+        sizes = self.term_sizes()
+        unknown = sorted(set(data) - set(self.TERMS))
+        if unknown or not data:
+            raise AttributeError('pack takes terms of {}, got {}'.format(self.TERMS, sorted(data)))
+        parts = []
+        for name in self.TERMS:
+            if name in data:
+                x = np.asarray(data[name])
+                if name not in sizes or x.ndim < 1 or x.shape[-1] != sizes[name]:
+                    raise AttributeError("term '{}' of shape {} does not end in the operator's {} entries".format(
+                        name, x.shape, sizes.get(name, 0)))
+                parts.append(x)
+        return np.concatenate(parts, axis=-1)
+
+    def split(self, array, terms=None):
+        """The inverse of ``pack``: {term: its slice of the last axis}.  ``terms``: the names (any iterable, or a '+'-joined string);
+        None: the one set of this operator's terms whose sizes add up to the last axis (terms of equal size have to be named)."""
+        sizes = self.term_sizes()
+        n = int(array.shape[-1])
+        if terms is None:
+            from itertools import combinations
+            fits = [c for r in range(1, len(sizes) + 1) for c in combinations([t for t in self.TERMS if t in sizes], r)
+                    if sum(sizes[t] for t in c) == n]
+            if len(fits) != 1:
+                raise AttributeError('a last axis of {} entries names {} sets of terms of {}: pass terms'.format(n, len(fits), sizes))
+            terms = fits[0]
+        elif isinstance(terms, str):
+            terms = terms.split('+')
+        terms = [t for t in self.TERMS if t in set(terms)]
+        if not terms or any(t not in sizes for t in terms) or sum(sizes[t] for t in terms) != n:
+            raise AttributeError('a last axis of {} entries is not the terms {} of {}'.format(n, terms, sizes))
+        out, o = {}, 0
+        for t in terms:
+            out[t] = array[..., o:o + sizes[t]]
+            o += sizes[t]
+        return out
+
+
 def closure_quadrangles(nsites):
     """The independent log closure amplitudes of every station quadruple a<b<c<d of an array with nsites stations, two per
     quadruple: (ab cd | ac bd) and (ad bc | ac bd).  Returns (nca, 4, 2) station pairs: legs 0 and 1 the numerator, legs 2 and 3
@@ -200,7 +269,7 @@ def quadrangle_table(pairs, quadrangles):
     return quad
 
 
-class ClosureDFT(DirectDFT):
+class ClosureDFT(TermSet, DirectDFT):
     """A ``DirectDFT`` that carries the closure tables of ONE weighted objective over the real-valued terms 'amp', 'cphase' and
     'logcamp' (libbhnerf_cls.so): one render, one visibility pass and one gradient for ``scale * sum_d w_d chi^2_d``.
 
@@ -208,6 +277,7 @@ class ClosureDFT(DirectDFT):
     ``closure_quadrangles``) together with ``pairs`` (nvis, 2), or without ``pairs`` the ready tables ``(tri, tri_sign)`` and
     ``quad`` (nca, 4).  ``weights``: {'amp' | 'cphase' | 'logcamp': w_d >= 0}, 1.0 where not given.  The data of a combined dtype
     such as 'cphase+logcamp' are the terms' arrays concatenated along the last axis in the canonical order (``pack``)."""
+    TERMS = CLOSURE_TERMS
 
     def __init__(self, uv, fov, npix, pairs=None, triangles=None, quadrangles=None, weights=None):
         import torch
@@ -224,17 +294,6 @@ class ClosureDFT(DirectDFT):
             self.quad = quad.to(torch.int32).contiguous() if keep else np.ascontiguousarray(q, dtype=np.int32)
         self.weights = self._weights(weights)
 
-    @staticmethod
-    def _weights(weights):
-        weights = dict(weights or {})
-        unknown = sorted(set(weights) - set(CLOSURE_TERMS))
-        if unknown:
-            raise AttributeError('weights name unknown terms {} (known: {})'.format(unknown, ', '.join(CLOSURE_TERMS)))
-        out = {k: float(weights.get(k, 1.0)) for k in CLOSURE_TERMS}
-        if not all(np.isfinite(w) and w >= 0 for w in out.values()):
-            raise AttributeError('weights must be finite and >= 0, got {}'.format(out))
-        return out
-
     @property
     def nca(self):
         return 0 if self.quad is None else int(self.quad.shape[0])
@@ -247,20 +306,6 @@ class ClosureDFT(DirectDFT):
         if self.quad is not None:
             sizes['logcamp'] = self.nca
         return sizes
-
-    def _like(self, uv, tri=None, tri_sign=None, quad=None):
-        out = object.__new__(type(self))
-        out.uv, out.H, out.W, out.fov = uv, self.H, self.W, self.fov
-        out.tri, out.tri_sign = (self.tri, self.tri_sign) if tri is None else (tri, tri_sign)
-        out.quad = self.quad if quad is None else quad
-        out.weights = dict(self.weights)
-        return out
-
-    def to(self, device):
-        """The operator with ``uv`` (float64) and the closure tables on ``device``."""
-        import torch
-        mv = lambda a: None if a is None else torch.as_tensor(a, device=device)
-        return self._like(mv(self.uv), mv(self.tri), mv(self.tri_sign), mv(self.quad))
 
     @staticmethod
     def _host(a):
@@ -286,51 +331,11 @@ class ClosureDFT(DirectDFT):
         quad = self._host(self.quad)
         return logamp[..., quad[:, 0]] + logamp[..., quad[:, 1]] - logamp[..., quad[:, 2]] - logamp[..., quad[:, 3]]
 
-    def pack(self, data):
-        """{'cphase': x, 'logcamp': y, ...} -> the arrays concatenated along the last axis in the canonical order (amp, cphase,
-        logcamp; only the terms named)."""
-        sizes = self.term_sizes()
-        parts = []
-        unknown = sorted(set(data) - set(CLOSURE_TERMS))
-        if unknown or not data:
-            raise AttributeError('pack takes terms of {}, got {}'.format(CLOSURE_TERMS, sorted(data)))
-        for name in CLOSURE_TERMS:
-            if name in data:
-                x = np.asarray(data[name])
-                if name not in sizes or x.shape[-1] != sizes[name]:
-                    raise AttributeError("term '{}' of shape {} does not end in the operator's {} entries".format(
-                        name, x.shape, sizes.get(name, 0)))
-                parts.append(x)
-        return np.concatenate(parts, axis=-1)
-
-    def split(self, array, terms=None):
-        """The inverse of ``pack``: {term: its slice of the last axis}.  ``terms``: the names (any iterable, or a '+'-joined string);
-        None: the one set of this operator's terms whose sizes add up to the last axis."""
-        sizes = self.term_sizes()
-        n = int(array.shape[-1])
-        if terms is None:
-            from itertools import combinations
-            fits = [c for r in range(1, len(sizes) + 1) for c in combinations([t for t in CLOSURE_TERMS if t in sizes], r)
-                    if sum(sizes[t] for t in c) == n]
-            if len(fits) != 1:
-                raise AttributeError('a last axis of {} entries names {} sets of terms of {}: pass terms'.format(n, len(fits), sizes))
-            terms = fits[0]
-        elif isinstance(terms, str):
-            terms = terms.split('+')
-        terms = [t for t in CLOSURE_TERMS if t in set(terms)]
-        if not terms or any(t not in sizes for t in terms) or sum(sizes[t] for t in terms) != n:
-            raise AttributeError('a last axis of {} entries is not the terms {} of {}'.format(n, terms, sizes))
-        out, o = {}, 0
-        for t in terms:
-            out[t] = array[..., o:o + sizes[t]]
-            o += sizes[t]
-        return out
-
 
 POL_TERMS = ('pvis', 'm')                           # the canonical order of the polarimetric terms
 
 
-class PolDFT(DirectDFT):
+class PolDFT(TermSet, DirectDFT):
     """A ``DirectDFT`` for ONE weighted objective over the polarimetric terms 'pvis' and 'm' (libbhnerf_pol.so), which couple the
     Stokes planes I, Q, U[, V] of a frame: with P = Q~ + i U~ per frame and baseline,
 
@@ -340,29 +345,17 @@ class PolDFT(DirectDFT):
 
     ``weights``: {'pvis' | 'm': w_d >= 0}, 1.0 where not given.  Targets are complex (nt, nvis), sigmas real (nt, nvis) -- one per
     frame and baseline, not per plane; the data of 'pvis+m' are the terms' arrays concatenated along the last axis in the
-    canonical order (``pack``).  ``observe`` is ``DirectDFT``'s."""
+    canonical order (``pack``; ``split`` without names takes a last axis of 2 nvis entries only: 'pvis' and 'm' have the same
+    size).  ``observe`` is ``DirectDFT``'s."""
+    TERMS = POL_TERMS
 
     def __init__(self, uv, fov, npix, weights=None):
         DirectDFT.__init__(self, uv, fov, npix)
         self.weights = self._weights(weights)
 
-    @staticmethod
-    def _weights(weights):
-        weights = dict(weights or {})
-        unknown = sorted(set(weights) - set(POL_TERMS))
-        if unknown:
-            raise AttributeError('weights name unknown terms {} (known: {})'.format(unknown, ', '.join(POL_TERMS)))
-        out = {k: float(weights.get(k, 1.0)) for k in POL_TERMS}
-        if not all(np.isfinite(w) and w >= 0 for w in out.values()):
-            raise AttributeError('weights must be finite and >= 0, got {}'.format(out))
-        return out
-
-    def _like(self, uv, tri=None, tri_sign=None):
-        out = object.__new__(type(self))
-        out.uv, out.H, out.W, out.fov = uv, self.H, self.W, self.fov
-        out.tri = out.tri_sign = None
-        out.weights = dict(self.weights)
-        return out
+    def term_sizes(self):
+        """{term: entries along the last axis}: one per baseline for either term."""
+        return {t: self.nvis for t in POL_TERMS}
 
     @staticmethod
     def _planes(vis):
@@ -381,35 +374,6 @@ class PolDFT(DirectDFT):
         vis = self._planes(vis)
         with np.errstate(divide='ignore', invalid='ignore'):
             return (vis[..., 1, :] + 1j * vis[..., 2, :]) / vis[..., 0, :]
-
-    def pack(self, data):
-        """{'m': y, 'pvis': x} -> the arrays concatenated along the last axis in the canonical order (pvis, m; only the terms named)."""
-        unknown = sorted(set(data) - set(POL_TERMS))
-        if unknown or not data:
-            raise AttributeError('pack takes terms of {}, got {}'.format(POL_TERMS, sorted(data)))
-        parts = []
-        for name in POL_TERMS:
-            if name in data:
-                x = np.asarray(data[name])
-                if x.ndim < 1 or x.shape[-1] != self.nvis:
-                    raise AttributeError("term '{}' of shape {} does not end in the operator's {} baselines".format(name, x.shape, self.nvis))
-                parts.append(x)
-        return np.concatenate(parts, axis=-1)
-
-    def split(self, array, terms=None):
-        """The inverse of ``pack``: {term: its slice of the last axis}.  ``terms``: the names (any iterable, or a '+'-joined string);
-        None: both terms for a last axis of 2 nvis entries (one term alone has to be named: 'pvis' and 'm' have the same size)."""
-        n = int(array.shape[-1])
-        if terms is None:
-            if n != 2 * self.nvis:
-                raise AttributeError('a last axis of {} entries does not name its terms ({} baselines): pass terms'.format(n, self.nvis))
-            terms = POL_TERMS
-        elif isinstance(terms, str):
-            terms = terms.split('+')
-        terms = [t for t in POL_TERMS if t in set(terms)]
-        if not terms or len(terms) * self.nvis != n:
-            raise AttributeError('a last axis of {} entries is not the terms {} of {} baselines'.format(n, terms, self.nvis))
-        return {t: array[..., i * self.nvis:(i + 1) * self.nvis] for i, t in enumerate(terms)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,8 @@ loss kernel with a gradient in the sampled volume, and the fused backward carrie
 """
 import numpy as np
 
+from .observation import term_weights
+
 REG_TERMS = ('tv', 'tsv', 'l1')                     # the canonical order of the terms
 
 
@@ -61,13 +63,7 @@ class VolumePrior:
         self.spacing = tuple(_regular_axis(a, n) for a, n in zip(axes, 'xyz'))
         # (3, nx, ny, nz, 1): one sample per "ray".  ONE array for the life of the operator: the geometry cache keys on its identity
         self.coords = np.ascontiguousarray(coords[..., None], dtype=np.float32)
-        weights = {'tv': 1.0} if weights is None else dict(weights)
-        unknown = sorted(set(weights) - set(REG_TERMS))
-        if unknown:
-            raise AttributeError('weights name unknown terms {} (known: {})'.format(unknown, ', '.join(REG_TERMS)))
-        self.weights = tuple(float(weights.get(k, 0.0)) for k in REG_TERMS)
-        if not all(np.isfinite(w) and w >= 0 for w in self.weights):
-            raise AttributeError('weights {} must be finite and >= 0'.format(weights))
+        self.weights = tuple(term_weights(REG_TERMS, {'tv': 1.0} if weights is None else weights, 0.0).values())
         self.eps = float(eps)
         if self.weights[0] != 0 and not (np.isfinite(self.eps) and self.eps > 0):
             raise AttributeError('eps ({}) must be positive and finite when the tv weight is not 0'.format(eps))

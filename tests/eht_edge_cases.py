@@ -108,7 +108,7 @@ def _cases():
     add('s24', (8, 8, 1, 0, 24), 'eht_loss_kernel, cls_loss_kernel, pol_loss_kernel: nvis 276, ncp 2024, nca 21252 -- the second trip of `k += 256`, '
         'and of the triangle and quadrangle loops', ('first_256_baselines',), dict(nvis=276, ncp=2024, nca=21252, kblocks=35, RS=1),
         cls_Sx=(0,), pol=((8, 8, 1, 0, 24), 3, 4))
-    add('n260', (16, 16, 260, 8, 4), 'eht_loss_sum_kernel, cls_loss_sum_kernel (260 planes), pol_loss_sum_kernel (257 frames): the second trip of '
+    add('n260', (16, 16, 260, 8, 4), 'eht_loss_sum_kernel, eht_terms_sum_kernel<3> (260 planes), eht_terms_sum_kernel<2> (257 frames): the second trip of '
         '`i += 256`; eht_twiddle_kernel: a grid over 260 frames', ('first_256_planes',), dict(N=260, RS=2), cls_Sx=(0,), pol=((8, 8, 257, 30, 4), 3))
     add('turns', (12, 20, 1, 1, 5), 'eht_twiddle: `t -= rint(t)` with thousands of whole turns in u x (field of view 10000 x FOV)', ('float32_phase',),
         dict(block=64, RS=2), uv=('vis', 'amp'), fov=10000.0 * E.FOV)
@@ -286,7 +286,7 @@ def pol_reference(name, Sx, mutant=None):
         return P.pol_loss(d['images'], A[:, :LANES], data, terms, w, P.SCALE)[:3] + (None,)
     total, grad, parts, vis = P.pol_loss(d['images'], A, d['data'], terms, w, P.SCALE)
     if mutant == 'first_256_planes':
-        assert d['B'] > LANES                               # frames: pol_loss_sum_kernel strides over them
+        assert d['B'] > LANES                               # frames: eht_terms_sum_kernel<2> strides over them
         total, _, parts, _ = P.pol_loss(d['images'][:LANES], A[:LANES], {t: (v[0][:LANES], v[1][:LANES]) for t, v in d['data'].items()}, terms, w, P.SCALE)
     return total, _adjoint_slip(grad, mutant), parts, vis
 

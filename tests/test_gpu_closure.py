@@ -102,7 +102,7 @@ def test_parity_with_float64(dev, name, Sx, want_grad):
 
 
 def _plane_sum(values):
-    """float32 sum over axis 0 in the order of cls_loss_sum_kernel (eht_loss_sum_kernel's): lane i of 256 adds the planes i, i + 256,
+    """float32 sum over axis 0 in the order of eht_terms_sum_kernel<3> (eht_loss_sum_kernel's): lane i of 256 adds the planes i, i + 256,
     ...; each wave of 64 lanes adds its lanes in an xor butterfly (offsets 32 down to 1); the four waves are added in order."""
     values = np.asarray(values, dtype=np.float32)
     lanes = np.zeros((256,) + values.shape[1:], dtype=np.float32)

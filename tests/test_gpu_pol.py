@@ -117,7 +117,7 @@ def test_bitwise_reproducible_and_independent_of_the_batch(dev):
         assert torch.equal(loss, loss2) and torch.equal(dimg, dimg2) and three.tobytes() == three2.tobytes()
         assert _chi2(c, dtype, dev, want_grad=False, op=op)[2].tobytes() == three.tobytes()                     # forward only: the same floats
         # every frame alone (B = 1) is its row of the B = 3 call, bit for bit; B = 3 adds the frames' terms in the one fixed order
-        # of pol_loss_sum_kernel (three lanes of one wave: the xor butterfly pairs lane 0 with lane 2 first, then with lane 1)
+        # of eht_terms_sum_kernel<2> (three lanes of one wave: the xor butterfly pairs lane 0 with lane 2 first, then with lane 1)
         tgt, sig = P.packed(c, dtype)
         alone = []
         for b in range(3):

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "eht_closure.h"
+#include "eht_terms.h"
 
 template <typename T>
 static bool read_n(FILE *f, std::vector<T> &v, size_t n) {
@@ -69,8 +70,8 @@ int main(int argc, char **argv) {
     }
     float eff[CLS_TERMS];
     for (int d = 0; d < CLS_TERMS; ++d) {
-        if (has[d] && !cls_weight_ok(head[12 + d])) { fprintf(stderr, "bad weight\n"); return 1; }
-        eff[d] = has[d] ? cls_effective_scale(scale, head[12 + d]) : 0.f;
+        if (has[d] && !eht_weight_ok(head[12 + d])) { fprintf(stderr, "bad weight\n"); return 1; }
+        eff[d] = has[d] ? eht_term_scale(scale, head[12 + d]) : 0.f;
     }
     const size_t count[CLS_TERMS] = {(size_t)N * nvis, (size_t)N * ncp, (size_t)N * nca}, npix = (size_t)N * H * W;
     std::vector<double> uv;
@@ -129,7 +130,7 @@ int main(int argc, char **argv) {
             }
         for (int d = 0; d < CLS_TERMS; ++d) terms[(size_t)d * N + n] = eff[d] * tot[d];
     }
-    for (int d = 0; d < CLS_TERMS; ++d) {                                               // cls_loss_sum_kernel
+    for (int d = 0; d < CLS_TERMS; ++d) {                                               // eht_terms_sum_kernel
         float tot = 0.f;
         for (int n = 0; n < N; ++n) tot += terms[(size_t)d * N + n];
         loss[1 + d] = tot;

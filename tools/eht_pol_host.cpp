@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "eht_pol.h"
+#include "eht_terms.h"
 
 template <typename T>
 static bool read_n(FILE *f, std::vector<T> &v, size_t n) {
@@ -68,8 +69,8 @@ int main(int argc, char **argv) {
     }
     float eff[POL_TERMS];
     for (int d = 0; d < POL_TERMS; ++d) {
-        if (has[d] && !cls_weight_ok(head[10 + d])) { fprintf(stderr, "bad weight\n"); return 1; }
-        eff[d] = has[d] ? cls_effective_scale(scale, head[10 + d]) : 0.f;
+        if (has[d] && !eht_weight_ok(head[10 + d])) { fprintf(stderr, "bad weight\n"); return 1; }
+        eff[d] = has[d] ? eht_term_scale(scale, head[10 + d]) : 0.f;
     }
     const int B = N / Sx;
     const size_t count = (size_t)B * nvis, npix = (size_t)N * H * W;
@@ -120,7 +121,7 @@ int main(int argc, char **argv) {
         }
         for (int d = 0; d < POL_TERMS; ++d) terms[(size_t)d * N + b] = eff[d] * tot[d];
     }
-    for (int d = 0; d < POL_TERMS; ++d) {                                               // pol_loss_sum_kernel
+    for (int d = 0; d < POL_TERMS; ++d) {                                               // eht_terms_sum_kernel
         float tot = 0.f;
         for (int b = 0; b < B; ++b) tot += terms[(size_t)d * N + b];
         loss[1 + d] = tot;

@@ -1,7 +1,7 @@
 """ctypes binding of libbhnerf_hip.so (include/bhnerf_hip.h), libbhnerf_kerr.so (include/bhnerf_kerr.h), libbhnerf_eht.so
 (include/bhnerf_eht.h), libbhnerf_grf.so (include/bhnerf_grf.h), libbhnerf_eql.so (include/bhnerf_eql.h), libbhnerf_flow.so
 (include/bhnerf_flow.h), libbhnerf_rec.so (include/bhnerf_rec.h), libbhnerf_cls.so (include/bhnerf_cls.h), libbhnerf_pol.so
-(include/bhnerf_pol.h) and libbhnerf_reg.so (include/bhnerf_reg.h).
+(include/bhnerf_pol.h), libbhnerf_reg.so (include/bhnerf_reg.h) and libbhnerf_jnt.so (include/bhnerf_jnt.h).
 
 PyTorch is used only as the owner of device memory and streams: every call passes raw
 ``data_ptr()`` addresses and the current HIP stream handle through the C ABI.  There is no CPU
@@ -226,6 +226,24 @@ REG_SIGNATURES = {
     'bhn_reg_loss': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _F3, _F3, _F, _F, _P, _P, _P, _P, _SZ, _P]),
 }
 REG_LIBRARY = (REG_LIB_PATH, REG_SIGNATURES, 'bhn_reg_last_error', None)
+
+# libbhnerf_jnt.so (include/bhnerf_jnt.h): the fan-in of a joint training step (ordered sums of gradients, the terms' losses), the
+# eleventh library
+JNT_LIB_PATH = os.path.join(CSRC, 'libbhnerf_jnt.so')
+BHN_JNT_MAX_TERMS = 8
+BHN_JNT_MAX_BLOCKS = 1024    # the cap of the grid of bhn_jnt_sum (include/bhnerf_jnt.h)
+
+
+class bhn_jnt_ptrs(C.Structure):
+    _fields_ = [('p', C.c_void_p * BHN_JNT_MAX_TERMS)]
+
+
+_JP = C.POINTER(bhn_jnt_ptrs)
+JNT_SIGNATURES = {
+    'bhn_jnt_last_error': (C.c_char_p, []),
+    'bhn_jnt_sum': (C.c_int, [_JP, _I32, _I64, _P, _JP, _P, _P]),
+}
+JNT_LIBRARY = (JNT_LIB_PATH, JNT_SIGNATURES, 'bhn_jnt_last_error', None)
 _loaded = {}                 # path -> handle
 
 
@@ -236,7 +254,7 @@ def build(verbose=False):
         print(res.stdout[-4000:])
         print(res.stderr[-4000:])
     if res.returncode != 0:
-        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec', 'libbhnerf_cls', 'libbhnerf_pol', 'libbhnerf_reg']), CSRC))
+        raise HipError('building %s failed (make -C %s)' % (' / '.join(name + '.so' for name in list(LIBRARIES) + ['libbhnerf_flow', 'libbhnerf_rec', 'libbhnerf_cls', 'libbhnerf_pol', 'libbhnerf_reg', 'libbhnerf_jnt']), CSRC))
     return LIB_PATH
 
 
@@ -325,6 +343,11 @@ def reg_lib():
     return _lib('libbhnerf_reg', REG_LIBRARY)
 
 
+def jnt_lib():
+    """The loaded joint-step fan-in library."""
+    return _lib('libbhnerf_jnt', JNT_LIBRARY)
+
+
 def check(rc):
     _check('libbhnerf_hip', rc)
 
@@ -363,6 +386,10 @@ def pol_check(rc):
 
 def reg_check(rc):
     _check('libbhnerf_reg', rc, REG_LIBRARY)
+
+
+def jnt_check(rc):
+    _check('libbhnerf_jnt', rc, JNT_LIBRARY)
 
 
 def stream_ptr(device=None):

@@ -1,4 +1,4 @@
-// Host-side skeleton of a side library (libbhnerf_kerr.so, libbhnerf_eht.so, libbhnerf_grf.so, libbhnerf_eql.so, libbhnerf_flow.so, libbhnerf_rec.so, libbhnerf_cls.so, libbhnerf_pol.so, libbhnerf_reg.so): the per-thread error message, the
+// Host-side skeleton of a side library (libbhnerf_kerr.so, libbhnerf_eht.so, libbhnerf_grf.so, libbhnerf_eql.so, libbhnerf_flow.so, libbhnerf_rec.so, libbhnerf_cls.so, libbhnerf_pol.so, libbhnerf_reg.so, libbhnerf_jnt.so): the per-thread error message, the
 // argument check and, under hipcc, the launch check and the grid size of a one-lane-per-element launch.
 //
 // No HIP dependency outside the __HIPCC__ block: tools/side_lib_host.cpp compiles the rest with a plain C++ compiler and runs it

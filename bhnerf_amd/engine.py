@@ -723,6 +723,50 @@ def chi2_volume(volumes, op, scale, mask=None, want_grad=True):
     return loss[:1], (dvol.reshape(volumes.shape) if want_grad else None)
 
 
+def _jnt_ptrs(tensors):
+    """The tensors' addresses by value in a bhn_jnt_ptrs; float32, contiguous, on one device."""
+    if not 1 <= len(tensors) <= _hip.BHN_JNT_MAX_TERMS:
+        raise AttributeError('a joint step sums 1 to {} terms, got {}'.format(_hip.BHN_JNT_MAX_TERMS, len(tensors)))
+    _hip.require_device(*tensors)
+    s = _hip.bhn_jnt_ptrs()
+    for k, t in enumerate(tensors):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != tensors[0].device:
+            raise AttributeError('contiguous float32 tensors on one device expected')
+        s.p[k] = t.data_ptr()
+    return s
+
+
+def joint_sum(parts, out=None):
+    """``((parts[0] + parts[1]) + ...)`` element by element in float32, left to right, in ONE launch (bhn_jnt_sum) -> `out` (a new
+    tensor shaped like parts[0] when None; it may BE one of the parts).  The fan-in of a joint training step: the terms'
+    d loss / d images, then the groups' gradients."""
+    n = int(parts[0].numel()) if len(parts) else 0
+    if any(int(t.numel()) != n for t in parts):
+        raise AttributeError('parts of one size expected, got {}'.format([int(t.numel()) for t in parts]))
+    src = _jnt_ptrs(parts)
+    if out is None:
+        out = torch.empty_like(parts[0])
+    _jnt_ptrs([out])
+    if int(out.numel()) != n or out.device != parts[0].device:
+        raise AttributeError('out of {} elements for parts of {}'.format(int(out.numel()), n))
+    dev = out.device
+    if n:                            # (an empty tensor has no address to hand over)
+        with torch.cuda.device(dev):
+            _hip.jnt_check(_hip.jnt_lib().bhn_jnt_sum(C.byref(src), len(parts), n, _hip.ptr(out), None, None, _hip.stream_ptr(dev)))
+    return out
+
+
+def joint_losses(losses):
+    """The terms' device-resident losses (K tensors, the first element of each) -> K + 1 floats on the device: their left-to-right
+    float32 sum, then the K losses (bhn_jnt_sum with n = 0).  One launch, no host read."""
+    src = _jnt_ptrs(losses)
+    dev = losses[0].device
+    out = torch.empty((len(losses) + 1,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):     # (n = 0: the source pointers are checked, not read)
+        _hip.jnt_check(_hip.jnt_lib().bhn_jnt_sum(C.byref(src), len(losses), 0, None, C.byref(src), _hip.ptr(out), _hip.stream_ptr(dev)))
+    return out
+
+
 _TABLE_RANGE = {}               # id of a checked table -> (the table, what lies outside [0, nvis) or None)
 
 

@@ -533,13 +533,30 @@ def _slot_images(images, geom):
     return images.reshape((1, images.shape[0]) + ((geom.S,) if geom.S else ()) + geom.spatial)
 
 
+def _check_ray_dtype(dtype, offset, eht):
+    """AttributeError for a dtype that the image-plane (`eht` False) / EHT step functions do not take."""
+    if dtype not in (engine.EHT_DTYPES if eht else ('full', 'lc')) and not (eht and (_closure_dtype(dtype, offset) or _pol_dtype(dtype, offset))):
+        raise AttributeError('{} dtype ({}) not supported'.format('eht' if eht else 'image', dtype))
+
+
+def _ray_chi2(geom, B, dtype, target, sigma, offset, scale, want_grad, eht, dev):
+    """The chi2 of `_pass` for one term on the rendered images of B frames -- images -> (loss[1], d loss / d images or None) --
+    and `staged`, which gives an image-plane term's operands in the kernel's layout.  For the EHT losses ``offset`` carries the
+    DFT matrices / the (u, v) operator.  Shared by `_step_image` and `_step_joint`."""
+    staged = lambda: _image_operands(geom, B, dtype, (target, sigma, offset), dev)
+    if eht:
+        chi2 = lambda im: engine.chi2_eht(im, offset, target, sigma, scale, dtype, want_grad=want_grad)
+    else:       # (host arrays are staged after the forward has been enqueued: the copy runs under it)
+        chi2 = lambda im: engine.chi2_image(im, *staged(), scale, dtype, want_grad=want_grad)
+    return chi2, staged
+
+
 def _step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, Omega, J, g, dtau, Sigma,
                 t_start_obs, t_geos, t_injection, scale, train, eht=False):
     """Per-process body of gradient_step_image/_eht and test_image/_eht with no torch.autograd in the
     loop: pack -> `_pass` (fused render -> chi^2 kernel -> fused backward) -> all-reduce -> Adam.  For the EHT
     losses ``offset`` carries the DFT matrices A."""
-    if dtype not in (engine.EHT_DTYPES if eht else ('full', 'lc')) and not (eht and (_closure_dtype(dtype, offset) or _pol_dtype(dtype, offset))):
-        raise AttributeError('{} dtype ({}) not supported'.format('eht' if eht else 'image', dtype))
+    _check_ray_dtype(dtype, offset, eht)
     pred = state.predictor
     eng = pred.engine()
     dev = eng.device
@@ -549,11 +566,7 @@ def _step_image(state, t_units, dtype, target, sigma, offset, t_frames, coords, 
     eng.pack(state.flat)
     taped = train and eng.fits_tape(B, geom.P_eff)      # record the tape while rendering: no recompute later
     group = eng.tape_group(B, geom.P_eff) if (train and not taped and not eht) else 0
-    staged = lambda: _image_operands(geom, B, dtype, (target, sigma, offset), dev)
-    if eht:
-        chi2 = lambda im: engine.chi2_eht(im, offset, target, sigma, scale, dtype, want_grad=train)
-    else:       # (host arrays are staged after the forward has been enqueued: the copy runs under it)
-        chi2 = lambda im: engine.chi2_image(im, *staged(), scale, dtype, want_grad=train)
+    chi2, staged = _ray_chi2(geom, B, dtype, target, sigma, offset, scale, train, eht, dev)
     n = eng.nparams
     buf = state.grad_buffer() if train else None
     if not group:
@@ -610,24 +623,42 @@ def test_eht(state, t_units, dtype, target, sigma, A, t_frames, coords, Omega, J
 test_eht.__test__ = False
 
 
+def _check_volume_term(dtype, op):
+    """AttributeError unless (dtype, op) is a volume term: 'volume' on a regularization.VolumePrior."""
+    if dtype != 'volume' or not isinstance(op, regularization.VolumePrior):
+        raise AttributeError('volume dtype ({}) takes a regularization.VolumePrior, got {}'.format(dtype, type(op).__name__))
+
+
+def _lattice(pred, eng, op, t_units, t_start_obs):
+    """(geometry, tM0) of a prior's lattice: one sample per "ray", one frame at t_start_obs, t_injection = 0 -- sample_3d_grid's
+    convention (no warp, nothing before injection)."""
+    geom = pred.geometry(op.coords, 0.0, 0.0)
+    t0, _ = _time_origin(t_start_obs, t_units)
+    tM0, _ = _frame_offsets(np.array([t0]), t_units, t_start_obs, 0.0, eng.device)
+    return geom, tM0
+
+
+def _lattice_pass(eng, geom, tM0, op, scale, grad, train):
+    """`_pass` on a prior's lattice with the prior as its chi2, the gradient into `grad` (None: no backward) -> loss[1].  Shared
+    by `_step_volume` and `_step_joint`."""
+    taped = train and eng.fits_tape(1, geom.P_eff)      # (else the backward re-runs the forward: bhn_render_bwd takes any size)
+    chi2 = lambda im: engine.chi2_volume(im, op, scale, mask=geom.dom, want_grad=train)
+    loss, images = _pass(eng, geom, tM0, None, chi2, grad, taped)
+    op.last_volume = images.reshape(op.dims)
+    return loss
+
+
 def _step_volume(state, t_units, dtype, op, t_start_obs, scale, train):
     """Per-process body of gradient_step_volume / test_volume: pack -> `_pass` on the operator's lattice (one sample per "ray",
     g = dtau = Sigma = 1: the render IS the emission) with the prior as its chi2 -> all-reduce -> Adam."""
-    if dtype != 'volume' or not isinstance(op, regularization.VolumePrior):
-        raise AttributeError('volume dtype ({}) takes a regularization.VolumePrior, got {}'.format(dtype, type(op).__name__))
+    _check_volume_term(dtype, op)
     pred = state.predictor
     eng = pred.engine()
-    geom = pred.geometry(op.coords, 0.0, 0.0)
-    # one frame at t_start_obs, t_injection = 0: sample_3d_grid's convention (no warp, nothing before injection)
-    t0, _ = _time_origin(t_start_obs, t_units)
-    tM0, _ = _frame_offsets(np.array([t0]), t_units, t_start_obs, 0.0, eng.device)
+    geom, tM0 = _lattice(pred, eng, op, t_units, t_start_obs)
     eng.pack(state.flat)
-    taped = train and eng.fits_tape(1, geom.P_eff)      # (else the backward re-runs the forward: bhn_render_bwd takes any size)
-    chi2 = lambda im: engine.chi2_volume(im, op, scale, mask=geom.dom, want_grad=train)
     n = eng.nparams
     buf = state.grad_buffer() if train else None
-    loss, images = _pass(eng, geom, tM0, None, chi2, buf[:n] if train else None, taped)
-    op.last_volume = images.reshape(op.dims)
+    loss = _lattice_pass(eng, geom, tM0, op, scale, buf[:n] if train else None, train)
     return _finish_step(state, buf, n, loss, train), state, torch.zeros((), dtype=torch.float32, device=eng.device)
 
 
@@ -648,6 +679,111 @@ def test_volume(state, t_units, dtype, target, sigma, op, t_frames, coords, Omeg
 
 
 test_volume.__test__ = False
+
+
+JOINT_KINDS = ('image', 'eht', 'volume')
+
+
+class JointOperands(tuple):
+    """The third operands of a joint step (optimization.TrainStep.joint), one entry per term, with what the step functions'
+    positional signature has no place for: ``terms``, per term (kind of JOINT_KINDS, dtype, scale), and ``owner``, the object
+    whose ``last_terms`` a step sets (None: nobody's)."""
+
+    def __new__(cls, thirds, terms, owner=None):
+        self = super().__new__(cls, thirds)
+        self.terms = tuple((str(kind), str(dtype), float(scale)) for kind, dtype, scale in terms)
+        self.owner = owner
+        if len(self.terms) != len(self) or any(kind not in JOINT_KINDS for kind, _, _ in self.terms):
+            raise AttributeError('one (kind, dtype, scale) with kind of {} per operand expected'.format(JOINT_KINDS))
+        return self
+
+
+def _step_joint(state, t_units, dtype, targets, sigmas, thirds, t_frames, coords, Omega, J, g, dtau, Sigma,
+                t_start_obs, t_geos, t_injection, scale, train):
+    """Per-process body of gradient_step_joint / test_joint: pack once -> the RAY GROUP (every 'image' / 'eht' term): ONE `_pass`
+    whose chi2 runs each term's own chi2 on the rendered images and adds their d loss / d images left to right in one launch
+    (engine.joint_sum) -> each 'volume' term's own lattice pass, as `_step_volume` runs it -> the groups' gradients added left to
+    right, the ray group first (engine.joint_sum) -> the terms' losses and their sum, on the device (engine.joint_losses) -> ONE
+    `_finish_step`: one all-reduce, one Adam.  When the tape does not fit, the backward re-runs the forward (render + render_bwd);
+    there is no frame-grouped path here."""
+    if dtype != 'joint' or not isinstance(thirds, JointOperands):
+        raise AttributeError('joint dtype ({}) takes network.JointOperands, got {}'.format(dtype, type(thirds).__name__))
+    if float(scale) != 1.0:
+        raise AttributeError('a joint step has scale 1: its terms carry their own ({})'.format(scale))
+    terms, K = thirds.terms, len(thirds)
+    if not (len(targets) == len(sigmas) == K) or not 1 <= K <= _hip.BHN_JNT_MAX_TERMS:
+        raise AttributeError('one target and one sigma per term and 1 to {} terms expected, got {}'.format(_hip.BHN_JNT_MAX_TERMS, K))
+    for k, (kind, dt, _) in enumerate(terms):
+        if kind == 'volume':
+            _check_volume_term(dt, thirds[k])
+        else:
+            _check_ray_dtype(dt, thirds[k], kind == 'eht')
+    ray = [k for k in range(K) if terms[k][0] != 'volume']
+    pred = state.predictor
+    eng = pred.engine()
+    dev = eng.device
+    n = eng.nparams
+    eng.pack(state.flat)
+    buf = state.grad_buffer() if train else None
+    losses, parts, images = [None] * K, [], None
+    if ray:
+        geom = pred.geometry(coords, Omega, t_geos, _stokes_or_none(J), g, dtau, Sigma)
+        tM0, _ = _frame_offsets(t_frames, t_units, t_start_obs, t_injection, dev)
+        B = int(tM0.numel())
+        taped = train and eng.fits_tape(B, geom.P_eff)
+        each = [_ray_chi2(geom, B, terms[k][1], targets[k], sigmas[k], thirds[k], terms[k][2], train, terms[k][0] == 'eht', dev)[0] for k in ray]
+
+        def chi2(im):
+            grads = []
+            for k, fn in zip(ray, each):
+                losses[k], d = fn(im)
+                grads.append(d)
+            if not train or len(grads) == 1:
+                return None, grads[0]
+            return None, engine.joint_sum(grads, out=grads[0])        # ((d_0 + d_1) + d_2) ..., into the first term's buffer
+
+        images = _pass(eng, geom, tM0, None, chi2, buf[:n] if train else None, taped)[1]
+        if train:
+            parts.append(buf[:n])
+    for k in range(K):
+        if terms[k][0] != 'volume':
+            continue
+        vgeom, vtM0 = _lattice(pred, eng, thirds[k], t_units, t_start_obs)
+        # the first gradient part of the step goes straight to the buffer, every later one to a part of its own
+        grad = (torch.empty((n,), dtype=torch.float32, device=dev) if parts else buf[:n]) if train else None
+        losses[k] = _lattice_pass(eng, vgeom, vtM0, thirds[k], terms[k][2], grad, train)
+        if train:
+            parts.append(grad)
+    if train and len(parts) > 1:
+        engine.joint_sum(parts, out=buf[:n])                          # (in place: parts[0] is buf[:n])
+    lv = engine.joint_losses(losses)                                  # [total | the K terms], no host read
+    if thirds.owner is not None:
+        thirds.owner.last_terms = lv[1:]
+    out_images = _slot_images(images, geom) if ray else torch.zeros((), dtype=torch.float32, device=dev)
+    return _finish_step(state, buf, n, lv[:1], train), state, out_images
+
+
+def gradient_step_joint(state, t_units, dtype, targets, sigmas, thirds, t_frames, coords, Omega, J, g, dtau, Sigma,
+                        t_start_obs, t_geos, t_injection, scale):
+    """ONE gradient step on the SUM of several terms (optimization.TrainStep.joint; dtype 'joint'): the step functions'
+    positional signature with one tuple entry per term in the target, sigma and third-operand positions, the third a
+    ``JointOperands`` that names each term's kind, dtype and scale.  One render of the ray set for all terms on it, the terms'
+    gradients summed left to right, one all-reduce, one Adam step -- so that the terms' scales weigh against each other, which
+    they do not when every term takes its own Adam step.  Returns (total loss[ndev], state, the ray terms' images[1, b_local,
+    [S], H, W] or a 0-d zero when every term is a prior); the K term losses go to ``thirds.owner.last_terms`` (device)."""
+    return _step_joint(state, t_units, dtype, targets, sigmas, thirds, t_frames, coords, Omega, J, g, dtau, Sigma,
+                       t_start_obs, t_geos, t_injection, scale, True)
+
+
+def test_joint(state, t_units, dtype, targets, sigmas, thirds, t_frames, coords, Omega, J, g, dtau, Sigma,
+               t_start_obs, t_geos, t_injection, scale):
+    """Forward-only twin of gradient_step_joint: one render per group, each term's loss, no state change.  A prior adds its loss
+    once per call (optimization.TrainStep.volume_prior)."""
+    return _step_joint(state, t_units, dtype, targets, sigmas, thirds, t_frames, coords, Omega, J, g, dtau, Sigma,
+                       t_start_obs, t_geos, t_injection, scale, False)
+
+
+test_joint.__test__ = False
 
 
 def sample_3d_grid(apply_fn, params, t_frame=0, t_start_obs=0, Omega=0, fov=None, coords=None, resolution=64, chunk=-1):

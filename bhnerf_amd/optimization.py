@@ -569,14 +569,96 @@ class TrainStep(object):
         """Training step on a prior on the recovered 3-D emission: the terms 'tv', 'tsv', 'l1' of ``regularization.VolumePrior``
         on the lattice ``fov`` (M) x ``resolution`` (or a regular ``coords``), the loss ``scale * sum_d weights[d] term_d``.  Used
         as ``TrainStep.image(...) + TrainStep.volume_prior(...)``: like every term of a sum it takes its own Adam step; alone, a
-        prior-only step runs.  It ignores the frame indices and the ray set.  In test mode it adds its loss ONCE PER CALL, whatever
+        prior-only step runs.  For a prior whose weight is meant to act against the data term use
+        ``TrainStep.joint(TrainStep.image(...), TrainStep.volume_prior(...))``: one Adam step on the summed gradient.  It ignores the frame indices and the ray set.  In test mode it adds its loss ONCE PER CALL, whatever
         the number of frames of the call: ``total_movie_loss`` therefore counts it once per chunk of the movie."""
         op = regularization.VolumePrior(fov, resolution, coords, weights, eps, normalize)
         return cls('volume', StaticArgs(op), network.gradient_step_volume, network.test_volume, scale)
 
+    @classmethod
+    def joint(cls, *steps):
+        """ONE training step on the SUM of the terms of `steps` (TrainSteps of any constructor of this class; sums built with
+        ``+`` and earlier joints are flattened, in order): one render of the ray set for every term on it, the terms' gradients
+        added left to right in float32, one all-reduce and ONE Adam step (``network.gradient_step_joint``).  Where ``a + b`` lets
+        every term take an Adam step of its own -- which moves the parameters by about the learning rate whatever the term's
+        ``scale`` -- the scales of a joint step weigh the terms against each other: the form for a prior whose weight is meant
+        to act.  The result has one loss (``num_losses == 1``, dtype 'joint', scale 1.0: the terms keep their own scales) and is
+        a term like any other: ``TrainStep.joint(a, b) + c`` has two.  It returns the total loss; the latest per-term losses
+        stay on the device as ``last_terms`` (K floats, in the order of the terms).  All frame-bearing terms must have the same
+        frame times (values and unit): ValueError otherwise; the volume priors have none.  At most 8 terms.  The captured
+        HIP-graph step (``use_graph``) stays single-loss only: a joint step runs eagerly."""
+        terms = []
+        for step in steps:
+            for k in range(step.num_losses):
+                if step.grad_pmap[k] is network.gradient_step_joint:
+                    terms += step.args[k].terms
+                    continue
+                kind = _JOINT_KIND.get(step.grad_pmap[k])
+                if kind is None:
+                    raise ValueError('a joint step takes the terms of this class, not {}'.format(step.grad_pmap[k]))
+                terms.append((kind, str(step.dtype[k]), step.args[k], float(step.scale[k])))
+        return cls('joint', JointArgs(terms), network.gradient_step_joint, network.test_joint, 1.0)
+
+    @property
+    def last_terms(self):
+        """The per-term losses of the latest call of this step's (first) joint term: a device tensor of K floats, None before
+        the first call or without a joint term."""
+        for a in self.args:
+            if isinstance(a, JointArgs):
+                return a.last_terms
+        return None
+
     @property
     def t_units(self):
         return self.args[0].t_units
+
+
+_JOINT_KIND = {network.gradient_step_image: 'image', network.gradient_step_eht: 'eht', network.gradient_step_volume: 'volume'}
+
+
+class JointArgs(object):
+    """The arguments of a joint step (TrainStep.joint): the terms' own args objects, batched at the same indices.  ``terms``:
+    per term (kind of network.JOINT_KINDS, dtype, the term's TemporalBatchedArgs / StaticArgs, scale).  The interface of
+    TemporalBatchedArgs as far as TrainStep and Optimizer use it; a joint of priors only behaves like StaticArgs."""
+
+    def __init__(self, terms):
+        self.terms = list(terms)
+        if not 1 <= len(self.terms) <= _hip.BHN_JNT_MAX_TERMS:
+            raise ValueError('a joint step takes 1 to {} terms, got {}'.format(_hip.BHN_JNT_MAX_TERMS, len(self.terms)))
+        framed = [a for kind, _, a, _ in self.terms if kind != 'volume']
+        for a in framed[1:]:
+            if units.unit_name(a.t_units) != units.unit_name(framed[0].t_units):
+                raise ValueError('the terms of a joint step need one unit of time, got {} and {}'.format(framed[0].t_units, a.t_units))
+            if a.num_frames != framed[0].num_frames or not np.array_equal(a.t_values, framed[0].t_values):
+                raise ValueError('the terms of a joint step need the same frame times')
+        self.frames = framed[0] if framed else None           # whose times, sampling and origin stand for all
+        self.last_terms = None
+
+    @property
+    def num_frames(self):
+        return self.frames.num_frames if self.frames is not None else StaticArgs.num_frames
+
+    @property
+    def t_units(self):
+        return self.frames.t_units if self.frames is not None else StaticArgs.t_units
+
+    @property
+    def t_start_obs(self):
+        return self.frames.t_start_obs
+
+    def sample(self, batchsize, replace=False):
+        """The frame batch of the first frame-bearing term (identical on every rank); of priors only, StaticArgs' zeros."""
+        if self.frames is None:
+            return np.zeros(batchsize, dtype=np.int64)
+        return self.frames.sample(batchsize, replace=replace)
+
+    def __getitem__(self, key):
+        """[targets, sigmas, thirds, t_frames]: one tuple entry per term from its own args at `key`; thirds a
+        network.JointOperands that carries the terms' kinds, dtypes and scales."""
+        per = [a[key] for _, _, a, _ in self.terms]
+        thirds = network.JointOperands([p[2] for p in per], [(kind, dtype, scale) for kind, dtype, _, scale in self.terms], owner=self)
+        t_frames = next((p[3] for p, (kind, _, _, _) in zip(per, self.terms) if kind != 'volume'), np.zeros(1))
+        return [tuple(p[0] for p in per), tuple(p[1] for p in per), thirds, t_frames]
 
 
 class StaticArgs(object):

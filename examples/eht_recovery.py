@@ -9,6 +9,7 @@ Tutorial 2 inside), with nothing but this package -- no ehtim, no astropy:
     python examples/eht_recovery.py [--dtype vis] [--array ngEHT] [--size 32] [--iters 1000] [--render out] [--tracer hip]
     python examples/eht_recovery.py --stokes --gains          # a polarised movie behind unknown station gains
     python examples/eht_recovery.py --tv 1e3 [--tv-res 32]    # the data term plus a total-variation prior on the emission volume
+    python examples/eht_recovery.py --tv 1e3 --joint          # the same objective, ONE Adam step per iteration on the summed gradient
 
 --stokes observes a polarised movie (Stokes I, Q, U through the transported factors J of a vertical field) and fits what station
 gains cannot touch: TrainStep.eht_obs(.., 'cphase+logcamp') on the I plane (the Q and U planes of its data get sigma = +inf) plus
@@ -21,7 +22,9 @@ common to the Stokes planes) before the thermal noise: the first fit does not se
 matplotlib).  --tv W adds TrainStep.volume_prior (the smoothed total variation of the emission on a --tv-res^3 lattice over the
 field of view, a mean over the in-domain voxels, times W) to whatever objective the flags select: a second loss with a render of
 the lattice and an Adam step of its own.  The chi^2 printed is the data term's alone, and every fit ends with the tv of the
-recovered 64^3 volume (engine.chi2_volume as a metric), so that runs with and without the prior compare.  What is and is not ehtim here: see observation.empty_eht_obs and INTEGRATION.md.
+recovered 64^3 volume (engine.chi2_volume as a metric), so that runs with and without the prior compare.  --joint builds every
+sum above with TrainStep.joint instead of +: one render of the ray set for all terms on it, the terms' gradients summed, one Adam
+step per iteration -- the form in which the weight of --tv acts against the data term.  What is and is not ehtim here: see observation.empty_eht_obs and INTEGRATION.md.
 """
 import argparse
 import os
@@ -57,6 +60,8 @@ def main():
     ap.add_argument('--stokes', action='store_true', help="a polarised movie (I, Q, U): fit 'cphase+logcamp' on I plus 'm', then 'vis' for contrast")
     ap.add_argument('--gains', action='store_true', help='corrupt the visibilities with random complex station gains (seed: --seed + 1)')
     ap.add_argument('--tv', type=float, default=0.0, metavar='W', help='weight of a total-variation prior on the emission volume (0: none)')
+    ap.add_argument('--joint', action='store_true', help='one Adam step on the summed gradient of the terms (TrainStep.joint) where the default '
+                    'lets every term take a step of its own (+): the weight of --tv then acts against the data term')
     ap.add_argument('--tv-res', type=int, default=32, metavar='N', help='the prior samples the emission on an N x N x N lattice over the field of view')
     args = ap.parse_args()
 
@@ -113,7 +118,8 @@ def main():
         data[term][1][:, 1:] = np.inf
     closure = optimization.TrainStep.eht_closure(t_frames, obs.uv, fov_rad, args.size, obs.pairs, {t: data[t] for t in ('cphase', 'logcamp')},
                                                  triangles=data['triangles'], quadrangles=data['quadrangles'])
-    robust = closure + optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype='m')
+    combine = optimization.TrainStep.joint if args.joint else (lambda a, b: a + b)
+    robust = combine(closure, optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype='m'))
     fit(args, "'cphase+logcamp' on I + 'm'", robust, geos, rt, rmin, rmax, z_width, fov_M, render=args.render)
     # for contrast: the calibrated visibilities of the three planes
     fit(args, "'vis'", optimization.TrainStep.eht_obs(t_frames, obs, vis, fov_rad, args.size, dtype='vis'), geos, rt, rmin, rmax, z_width, fov_M)
@@ -126,8 +132,11 @@ def fit(args, label, data_step, geos, rt, rmin, rmax, z_width, fov_M, render=Non
     from bhnerf_amd import engine, regularization
     train_step = data_step
     if args.tv > 0:
-        train_step = data_step + optimization.TrainStep.volume_prior(fov_M, resolution=args.tv_res, weights={'tv': 1.0}, scale=args.tv)
+        prior = optimization.TrainStep.volume_prior(fov_M, resolution=args.tv_res, weights={'tv': 1.0}, scale=args.tv)
+        train_step = optimization.TrainStep.joint(data_step, prior) if args.joint else data_step + prior
         label += ' + %g tv at %d^3' % (args.tv, args.tv_res)
+    if args.joint:
+        label += ' (joint)'
     predictor = network.NeRF_Predictor(rmax, rmin, rmax, z_width, net_depth=4, net_width=args.width, mode=args.mode)
     opt = optimization.Optimizer({'num_iters': args.iters, 'lr_init': 1e-3, 'lr_final': 1e-4}, predictor, rt)
     first = optimization.total_movie_loss(args.batch, opt.state, data_step, rt)
